@@ -6,11 +6,14 @@ PAF text that is already resident in HBM. Workloads follow BASELINE.json / SURVE
   cfg3 (default): 10M-record stream, mean 2048 cigar ops, `invert | trim | shatter`
   cfg2          :  1M-record stream, mean  512 cigar ops, `shatter`
 Every step takes the next `--batch` records of the stream (rank r of N takes every N-th batch),
-so K steps process K*batch distinct records per GPU (weak scaling). `--gpus N` starts the N ranks itself
+so K steps process K*batch records per GPU (weak scaling), distinct ones up to one pass over the stream
+and its batches again after that. `--gpus N` starts the N ranks itself
 when no launcher did (one process per GPU, RCCL); the ordered write across ranks -- an all-gather of
 every step's output sizes, from which each rank knows its byte range -- runs inside the timed region.
 
-Prints ONE JSON line on rank 0 (see the driver contract): value = records/s over all GPUs;
+Prints ONE JSON line on rank 0 (see the driver contract): value = records/s over all GPUs,
+ms_per_step = wall time of one timed step. A plain run does only that; `--dump-outputs DIR` also writes
+what the last timed step computed, and `--full` adds the figures below, which take runs of their own.
 `roofline` prices one pass of the hot path over one batch: algorithmic bytes = input line bytes +
 output line bytes of the batch (SURVEY 8d) over the summed HIP-event durations of the step's kernels;
 `roofline_by_kernel` prices every record kernel with the bytes it moves itself; `cpu_baseline`
@@ -60,12 +63,18 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed even with one rank, so that the collectives of the N-rank path (RCCL with the nccl backend) run at world size 1")
     ap.add_argument("--pipe", default=None, help="override the workload's command pipe, e.g. 'shatter' (experiments only)")
-    ap.add_argument("--cpu-sample", type=int, default=65536, help="records of the stream timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: HIP events on the kernels and the roofline figures built on them, the CPU legs, the "
+                         "PCIe-inclusive rate and the flat pass's counts (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy: see dump_outputs()")
+    ap.add_argument("--cpu-sample", type=int, default=65536, help="--full: records of the stream timed on the CPU oracle (0 = skip)")
     ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket kernels with HIP events in the timed region")
     ap.add_argument("--mean-ops", type=int, default=0, help="override the workload's mean cigar ops (experiments only)")
-    ap.add_argument("--kernel-events", choices=("dominant", "all", "none"), default="dominant",
-                    help="HIP events inside the timed region: around the launches of the dominant kernel only (default; the other kernels are "
-                         "timed in a short instrumented pass after the timed region), around every kernel (costs a step of a dozen kernels 3 %%), or none")
+    ap.add_argument("--kernel-events", choices=("dominant", "all", "none"), default=None,
+                    help="HIP events inside the timed region: around the launches of the dominant kernel only (default with --full; the other kernels are "
+                         "timed in a short instrumented pass after the timed region), around every kernel (costs a step of a dozen kernels 3 %%), or none "
+                         "(default without --full)")
     ap.add_argument("--pipeline", type=int, default=None,
                     help="stream workloads: contexts that take the batches in turn, each on its own HIP stream, so that the sizing pass of batch k + 1 runs beside "
                          "the writers of batch k (1 = one context, batches strictly one after the other; default 2, 1 for the workload with genomes)")
@@ -86,8 +95,12 @@ def main():
         args.batch = 2_000_000 if tile_wl else 131072
     if args.pipeline is None:
         args.pipeline = 1 if (tile_wl or WORKLOADS[args.workload].get("genomes")) else 2
+    if args.kernel_events is None:
+        args.kernel_events = "dominant" if args.full else "none"
     if args.no_kernel_events:
         args.kernel_events = "none"
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` outside a launcher: start the N ranks here, before anything touches the GPU
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -146,6 +159,11 @@ def main():
         if len(engs) > 1:
             raise SystemExit("--pipeline > 1 is for the stream workloads without genomes (every context would hold its own copy)")
         eng.synth4_setup(wl["seed"], wl["mean_ops"])  # both genomes replicated on every GPU
+    # every step reads batches[step % len(batches)]: the batches held in HBM are one pass over the workload's stream (cfg3: 77 batches
+    # of 131 072 records, 55 GB, generated in about 13 s), so that any --steps fits in memory and sets up in bounded time. A batch is far
+    # larger than the caches: one read again is not warm.
+    stream_batches = -(-wl["total"] // args.batch)  # ceil
+    mine = mine[: -(-stream_batches // world)]
     for _, first, n in mine:
         r0 = first % max(1, wl["total"] - args.batch + 1)  # weak scaling: past the end the stream repeats
         buf, nbytes = eng.synth4(r0, n) if wl.get("genomes") else eng.synth(wl["seed"], wl["mean_ops"], r0, n)
@@ -171,7 +189,7 @@ def main():
     def step(i):
         k = i % len(engs)
         e = engs[k]
-        buf, nbytes, _ = batches[i]
+        buf, nbytes, _ = batches[i % len(batches)]
         info = e.tile_plan(buf, nbytes) if wl.get("tile") else e.plan(stages, buf, nbytes)
         if info.error.code:
             raise RuntimeError(f"synthetic record failed: code {info.error.code} record {info.error.record}")
@@ -216,13 +234,18 @@ def main():
             kernels[name] = (have[0] + ms, have[1] + cnt)
         e.profile(False)
     timed_kernels = dict(kernels)
+    if args.dump_outputs and rank == 0:  # before the instrumented pass below writes into d_out[0] again
+        last = infos[-1]
+        dump_outputs(args.dump_outputs, d_out[(args.warmup + args.steps - 1) % len(engs)][: last.out_bytes],
+                     (last.n_records, last.n_rows, last.in_bytes, last.out_bytes))
     prof_steps = 0
     if args.kernel_events == "dominant":
         # every kernel of a step, bracketed, in a pass of its own behind the timed region: one context, the batches one after the other
         prof_steps = min(args.steps, 8)
         eng.profile(True)
         for i in range(prof_steps):
-            info = eng.plan(stages, batches[args.warmup + i][0], batches[args.warmup + i][1])
+            buf, nbytes, _ = batches[(args.warmup + i) % len(batches)]
+            info = eng.plan(stages, buf, nbytes)
             eng.emit(d_out[0])
         eng.sync()
         kernels = eng.profile_read()
@@ -306,7 +329,7 @@ def main():
                         "dominant_frac": round(per_launch_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                         "algorithmic_bytes_per_launch": int(per_launch_bytes)}
         cpu = cpu_all = e2e = None
-        if args.cpu_sample > 0 and world == 1:  # the CPU leg runs on rank 0 of the one-GPU run only
+        if args.full and args.cpu_sample > 0 and world == 1:  # the CPU leg runs on rank 0 of the one-GPU run only
             if wl.get("genomes"):
                 cpu = cpu_baseline_genomes(eng, wl, stages, min(args.cpu_sample, 16384))
             else:
@@ -338,16 +361,22 @@ def main():
             "ordered_write": {"mode": "per-rank offsets from an all-gather of the step's output sizes", "total_bytes": ordered_total,
                               "rank0_first_offsets": [int(x) for x in my_offsets[:4].tolist()], "verified_against_one_process": verified},
             "whole_path_GBps_per_gpu": round(((job_in + job_out) / world + extra_per_base * aligned_per_record * args.batch * args.steps) / elapsed / 1e9, 1),
-            "roofline": roofline,
-            "roofline_by_kernel": {k: v for k, v in by_kernel.items() if "+" in k or kernels[k][0] >= 0.05 * max(x[0] for x in kernels.values())},
             "whole_path_frac_of_hbm_peak": round(((job_in + job_out) / world + extra_per_base * aligned_per_record * args.batch * args.steps) / elapsed / 1e9 / HBM_PEAK_GBS, 4),
-            "cpu_baseline": cpu,
-            "cpu_baseline_all_cores": cpu_all,
-            "end_to_end": e2e,
-            "kernel_ms": {k: round(v[0] / max(1, v[1]), 4) for k, v in kernels.items()},
-            # the lean pipes are sized by the flat pass (paffy_amd/csrc/flat_kernel.h); what it left to the record kernels in the last plan
-            "flat_pass": dict(zip(("records_left_to_record_kernels", "by_reason"), eng.flat_stats())),
         }
+        if args.full or kernels:
+            line.update({
+                "roofline": roofline,
+                "roofline_by_kernel": {k: v for k, v in by_kernel.items() if "+" in k or kernels[k][0] >= 0.05 * max(x[0] for x in kernels.values())},
+                "kernel_ms": {k: round(v[0] / max(1, v[1]), 4) for k, v in kernels.items()},
+            })
+        if args.full:
+            line.update({
+                "cpu_baseline": cpu,
+                "cpu_baseline_all_cores": cpu_all,
+                "end_to_end": e2e,
+                # the lean pipes are sized by the flat pass (paffy_amd/csrc/flat_kernel.h); what it left to the record kernels in the last plan
+                "flat_pass": dict(zip(("records_left_to_record_kernels", "by_reason"), eng.flat_stats())),
+            })
         print(json.dumps(line), flush=True)
     if dist:
         dist.destroy_process_group()
@@ -391,13 +420,14 @@ def bench_tile(args, wl, rank, world, dist, dev):
             # buffer the allocator then frees and re-allocates everything inside the timed region: 2.3 s instead of 0.73 s per step.)
             torch.cuda.empty_cache()
         batches, first = share(i)
+        share_bytes = sum(n for _, n in batches)  # the list is emptied as its batches are split
         if i == 0:
             head = bytes(batches[0][0][: min(batches[0][1], 4 << 20)].cpu().numpy().tobytes())
             lines = head.split(b"\n")[:-1]
             aligned_per_record = sum(int(l.split(b"\t", 10)[9]) for l in lines) / max(1, len(lines))
         timed = i >= args.warmup
         if i == args.warmup:
-            eng.profile(not args.no_kernel_events)
+            eng.profile(args.kernel_events != "none")
         if dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -420,6 +450,8 @@ def bench_tile(args, wl, rank, world, dist, dev):
         hbm_used_after_step = total_b - free_b
     kernels = eng.profile_read()
     eng.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[1], (args.batch * world, int(last[0]["keys"].shape[0]), share_bytes, int(last[1].numel())))
     red = dev if (dist is not None and args.dist_backend == "nccl") else "cpu"
     # what every rank ended up owning in the last step: the partition by query contig (heaviest contig to the lightest rank) bounds the
     # N-GPU efficiency before any link does, so the line shows it
@@ -470,8 +502,8 @@ def bench_tile(args, wl, rank, world, dist, dev):
             for name, (ms, launches) in kernels.items():
                 if launches > 0 and ms >= 0.05 * kernels[dom][0]:
                     by_kernel[name] = {"avg_kernel_ms": round(ms / launches, 4), "launches_per_step": round(launches / max(1, args.steps), 2)}
-        cpu = cpu_baseline_tile(eng, wl, min(args.cpu_sample, 8192)) if (args.cpu_sample > 0 and world == 1) else None
-        print(json.dumps({
+        cpu = cpu_baseline_tile(eng, wl, min(args.cpu_sample, 8192)) if (args.full and args.cpu_sample > 0 and world == 1) else None
+        line = {
             "metric": "PAF records/sec (tile, records partitioned by query contig + ordered write; BASELINE cfg5); % HBM roofline at 1/2/4/8 GPU",
             "value": round(records / elapsed, 1), "unit": "records/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / max(1, args.steps) * 1e3, 3), "higher_is_better": True,
@@ -491,12 +523,57 @@ def bench_tile(args, wl, rank, world, dist, dev):
                     "share_text_GB": round(in_bytes / max(1, args.steps) / 1e9, 2),
                     "note": "device memory in use by this process (hipMemGetInfo: torch's cache and the library's buffers alike); the peaks are sampled at the phase "
                             "boundaries of the sharded tile with PAFFY_SHARD_TIMING=1; live = in use minus the blocks torch's caching allocator holds empty"},
-            "roofline": roofline, "roofline_by_kernel": by_kernel, "cpu_baseline": cpu,
-            "kernel_ms": {k: round(v[0] / max(1, v[1]), 4) for k, v in kernels.items()},
-        }), flush=True)
+        }
+        if args.full or kernels:
+            line.update({"roofline": roofline, "roofline_by_kernel": by_kernel, "kernel_ms": {k: round(v[0] / max(1, v[1]), 4) for k, v in kernels.items()}})
+        if args.full:
+            line["cpu_baseline"] = cpu
+        print(json.dumps(line), flush=True)
     eng.close()
     if dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, text, counts, n_chunks=4096, n_windows=256, window=16384):
+    """--dump-outputs: what the timed path hands its caller in its last step -- the output PAF text in HBM (u8) and the plan's counts --
+    as .npy files, so that two builds can be compared output for output. The text of a step runs to gigabytes, so it is written as
+      plan_counts.npy          float64 [records, rows, input bytes, output bytes]
+      chunk_byte_sums.npy      float64 [n_chunks]  sum of the bytes of each of n_chunks equal chunks of the whole text (exact)
+      chunk_line_counts.npy    float64 [n_chunks]  newlines in each chunk
+      text_windows.npy         float32 [n_windows, window]  the bytes of windows at seeded offsets (the whole text when it is shorter)
+      text_window_offsets.npy  float64 [n_windows]
+    16 MiB in all at the defaults."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    n = int(text.numel())
+    chunk = max(1, -(-n // n_chunks))
+    sums, lines = [], []
+    per_piece = max(1, (256 << 20) // chunk)  # chunks reduced at a time: bounds the temporaries
+    for a in range(0, n, per_piece * chunk):
+        piece = text[a: min(n, a + per_piece * chunk)]
+        full = piece.numel() // chunk
+        parts = [piece[: full * chunk].view(full, chunk)] if full else []
+        if piece.numel() > full * chunk:
+            parts.append(piece[full * chunk:].view(1, -1))
+        for p in parts:
+            sums.append(p.sum(dim=1, dtype=torch.int64))
+            lines.append((p == 10).sum(dim=1, dtype=torch.int64))
+    if n > window:
+        rng = np.random.default_rng(0x5EED)
+        offs = np.sort(rng.integers(0, n - window + 1, size=min(n_windows, n // window)))
+        idx = torch.from_numpy(offs).to(text.device).view(-1, 1) + torch.arange(window, device=text.device)
+        win = text[idx]
+    else:
+        offs, win = np.zeros(1, dtype=np.int64), text.view(1, -1)
+    arrays = {"plan_counts": np.array(counts, dtype=np.float64),
+              "chunk_byte_sums": (torch.cat(sums).cpu().numpy() if sums else np.zeros(0)).astype(np.float64),
+              "chunk_line_counts": (torch.cat(lines).cpu().numpy() if lines else np.zeros(0)).astype(np.float64),
+              "text_windows": win.cpu().numpy().astype(np.float32),
+              "text_window_offsets": offs.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _free_port():
@@ -639,8 +716,8 @@ def verify_stream(args, wl, eng, stages, rank, world, dist, comm, mine, batches,
     take = [k for k in range(args.warmup + max(0, args.steps - last), args.warmup + args.steps)]
     local = {}
     for k in take:
-        b, _, _ = mine[k]
-        buf, nbytes, _ = batches[k]
+        b, _, _ = mine[k % len(batches)]  # the batch step k read (main: batches[step % len(batches)])
+        buf, nbytes, _ = batches[k % len(batches)]
         info = eng.plan(stages, buf, nbytes)
         out = eng.alloc_out(info.out_bytes)
         eng.emit(out)
