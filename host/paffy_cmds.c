@@ -338,6 +338,78 @@ int paffy_add_mismatches_main(int argc, char *argv[]) {
     return run_stream_cmd(&o, &st, 1, "add_mismatches");
 }
 
+/* impl/paf_dechunk.c: options l:i:o:hqt; -q fixes the query side only, -t the target side only (both: neither, the records are still
+   parsed, checked and written) */
+int paffy_dechunk_main(int argc, char *argv[]) {
+    static struct option opts[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'},
+                                   {"outputFile", required_argument, 0, 'o'}, {"query", no_argument, 0, 'q'},
+                                   {"target", no_argument, 0, 't'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+    cmd_opts o;
+    memset(&o, 0, sizeof(o));
+    int fix_query = 1, fix_target = 1;
+    optind = 1;
+    for (;;) {
+        int idx = 0;
+        int key = getopt_long(argc, argv, "l:i:o:hqt", opts, &idx);
+        if (key == -1) break;
+        switch (key) {
+            case 'l': o.log_level = optarg; break;
+            case 'i': o.in_path = optarg; break;
+            case 'o': o.out_path = optarg; break;
+            case 'q': fix_target = 0; break;
+            case 't': fix_query = 0; break;
+            case 'h':
+            default:
+                usage_common("dechunk", "Map the coordinates of alignments between chunks (names \"name|length|chunk start\") back to the sequences");
+                fprintf(stderr, "-q --query : only fix the query side\n-t --target : only fix the target side\n");
+                usage_tail();
+                return key == 'h' ? 0 : 1;
+        }
+    }
+    paffy_stage st = paffy_stage_dechunk(fix_query, fix_target);
+    return run_stream_cmd(&o, &st, 1, "dechunk");
+}
+
+/* impl/paf_upconvert.c: options l:o:hi: (-i / --inFile); the FASTA files of the extracted subsequences are positional */
+int paffy_upconvert_main(int argc, char *argv[]) {
+    static struct option opts[] = {{"logLevel", required_argument, 0, 'l'}, {"inFile", required_argument, 0, 'i'},
+                                   {"outputFile", required_argument, 0, 'o'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+    cmd_opts o;
+    memset(&o, 0, sizeof(o));
+    optind = 1;
+    for (;;) {
+        int idx = 0;
+        int key = getopt_long(argc, argv, "l:o:hi:", opts, &idx);
+        if (key == -1) break;
+        switch (key) {
+            case 'l': o.log_level = optarg; break;
+            case 'i': o.in_path = optarg; break;
+            case 'o': o.out_path = optarg; break;
+            case 'h':
+            default:
+                fprintf(stderr, "paffy upconvert [fasta_file]xN [options], MI355X build\n"
+                                "Convert the coordinates of alignments to the extracted subsequences (headers \"name|length|start\") that hold them\n");
+                fprintf(stderr, "-i --inFile : PAF file to read (default: stdin)\n-o --outputFile : PAF file to write (default: stdout)\n");
+                usage_tail();
+                return key == 'h' ? 0 : 1;
+        }
+    }
+    host_set_log_level(o.log_level);
+    fasta_set f;
+    memset(&f, 0, sizeof(f));
+    for (int i = optind; i < argc; i++) {
+        host_log_info("Parsing sequence file : %s\n", argv[i]);
+        if (fasta_read(argv[i], &f) != 0) {
+            fprintf(stderr, "paffy upconvert: cannot open %s\n", argv[i]);
+            return 1;
+        }
+    }
+    host_log_info("Read %i sequences from sequence files\n", (int)f.n);
+    host_set_intervals((const char *const *)f.names, f.lens, f.n);
+    paffy_stage st = {PAFFY_UPCONVERT, 0.0f, 0.0f};
+    return run_stream_cmd(&o, &st, 1, "upconvert");
+}
+
 /* impl/paf_tile.c: whole-file command; the batch is the file */
 int paffy_tile_main(int argc, char *argv[]) {
     cmd_opts o;

@@ -24,6 +24,8 @@ int paffy_tile_main(int argc, char *argv[]);
 int paffy_chain_main(int argc, char *argv[]);
 int paffy_view_main(int argc, char *argv[]);
 int paffy_to_bed_main(int argc, char *argv[]);
+int paffy_dechunk_main(int argc, char *argv[]);
+int paffy_upconvert_main(int argc, char *argv[]);
 
 /* The input of a command: `path` (NULL: stdin). Under the N-GPU launcher (host/paffy_launch.c) a worker reads only its byte range
  * of the file: PAFFY_RANGE="first:end". */
@@ -64,6 +66,9 @@ int host_split_file(FILE *in, const char *prefix, int by_query, int64_t min_leng
 
 /* Sequences handed to the context that host_stream creates (add_mismatches); pointers must stay valid. */
 void host_set_sequences(const char *const *names, const char *const *seqs, const int64_t *lens, int64_t n);
+/* Intervals handed to the context that host_stream creates (upconvert: FASTA headers, sequence lengths); pointers must stay valid.
+   A header that does not decode ends the process with abort(), as the reference's assert does. */
+void host_set_intervals(const char *const *headers, const int64_t *seq_lens, int64_t n);
 /* paffy view -a: keep the bases as loaded beside the upper-cased store (before host_stream), and print the rows under each stats line */
 void host_keep_raw_sequences(int on);
 void host_set_alignment_rows(int on);

@@ -6,7 +6,7 @@
  *
  * The reference's own parallelism is at this level: the user splits the input per contig and runs one `paffy` per split
  * (tests/paf_pipeline_test.sh:42-67, impl/paf_split_file.c:142-173). Here:
- *   stream commands (invert, trim, shatter, add_mismatches, filter): records are independent (impl/paf_invert.c:84-89), so worker r
+ *   stream commands (invert, trim, shatter, add_mismatches, filter, dechunk, upconvert): records are independent (impl/paf_invert.c:84-89), so worker r
  *     reads the r-th of N contiguous byte ranges of the input, cut at line ends (PAFFY_RANGE; no copy of the input), and writes a
  *     spool file; the spools are concatenated in rank order. A failing record ends the run as one process would: everything before it
  *     is written, the worker's exit status (or signal) becomes ours.
@@ -102,14 +102,15 @@ static void find_tmpdir(void) {
 }
 
 static int is_stream_cmd(const char *c) {
-    return !strcmp(c, "invert") || !strcmp(c, "trim") || !strcmp(c, "shatter") || !strcmp(c, "add_mismatches") || !strcmp(c, "filter");
+    return !strcmp(c, "invert") || !strcmp(c, "trim") || !strcmp(c, "shatter") || !strcmp(c, "add_mismatches") || !strcmp(c, "filter") ||
+           !strcmp(c, "dechunk") || !strcmp(c, "upconvert");
 }
 
 /*
  * The command line of a sharded command, parsed the way the worker will parse it: getopt_long with the subcommand's own option string
  * and long options (/root/reference/impl/paf_invert.c:41-76, paf_trim.c:45-100, paf_add_mismatches.c:40-85, paf_filter.c:50-115,
- * paf_tile.c:100-150) -- clustered short flags (`trim -fi in.paf`), abbreviated long options (`--input x`), an option's value that
- * looks like an option (`-l -i`) all mean here what they mean there. The worker's command line is rebuilt from the parse: every
+ * paf_tile.c:100-150, paf_dechunk.c:55-66, paf_upconvert.c:84-91) -- clustered short flags (`trim -fi in.paf`), abbreviated long
+ * options (`--input x`), an option's value that looks like an option (`-l -i`) all mean here what they mean there. The worker's command line is rebuilt from the parse: every
  * option but -i / -o as the worker would have seen it, then the positional arguments, then our own -i / -o. Anything getopt_long
  * rejects, and -h, leaves the command to a single worker (which prints what the reference prints).
  */
@@ -135,6 +136,12 @@ static const struct option k_filter[] = {{"logLevel", required_argument, 0, 'l'}
                                          {"minIdentity", required_argument, 0, 'u'}, {"minIdentityWithGaps", required_argument, 0, 'v'},
                                          {"maxTileLevel", required_argument, 0, 'w'}, {"invert", no_argument, 0, 'x'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
 
+static const struct option k_dechunk[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
+                                          {"query", no_argument, 0, 'q'}, {"target", no_argument, 0, 't'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+/* upconvert: --inFile (impl/paf_upconvert.c:84-88); its FASTA files are positional and every worker loads them */
+static const struct option k_upconvert[] = {{"logLevel", required_argument, 0, 'l'}, {"inFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
+                                            {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+
 static void parse_cmdline(int argc, char **argv, CmdLine *cl) {
     memset(cl, 0, sizeof(*cl));
     const char *cmd = argv[1];
@@ -143,6 +150,8 @@ static void parse_cmdline(int argc, char **argv, CmdLine *cl) {
     if (!strcmp(cmd, "trim")) { optstring = "l:i:o:ht:r:f"; lopts = k_trim; }
     else if (!strcmp(cmd, "add_mismatches")) { optstring = "l:i:o:ha"; lopts = k_add; }
     else if (!strcmp(cmd, "filter")) { optstring = "l:i:o:s:t:u:v:w:xh"; lopts = k_filter; }
+    else if (!strcmp(cmd, "dechunk")) { optstring = "l:i:o:hqt"; lopts = k_dechunk; }
+    else if (!strcmp(cmd, "upconvert")) { optstring = "l:o:hi:"; lopts = k_upconvert; }
     /* getopt_long permutes the array it is given: a copy of argv[1..] (argv[1], the subcommand, stands where the program name would) */
     char **v = (char **)calloc((size_t)argc + 1, sizeof(char *));
     for (int i = 1; i < argc; i++) v[i - 1] = argv[i];

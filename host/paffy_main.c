@@ -2,8 +2,7 @@
  * paffy_main.c -- `paffy <command> [options]` dispatcher of the MI355X build.
  * Contract of the reference dispatcher (paffy_main.c:46-84): no arguments -> usage, status 0;
  * unknown command -> message + usage, status 1; otherwise the command's own status. The hot-path
- * commands (shatter, invert, trim, add_mismatches, tile) run on the GPU; the others are outside
- * this build's scope and say so with status 1.
+ * commands run on the GPU; a command without a driver (none at present) would say so with status 1.
  */
 #define _GNU_SOURCE
 #include <fcntl.h>
@@ -22,7 +21,7 @@ static const struct {
 } COMMANDS[] = {
     {"add_mismatches", paffy_add_mismatches_main, "Replace Ms with =/Xs in the cigar (or -a: the reverse)"},
     {"chain", paffy_chain_main, "Chain alignments: every record gets the id and score of its chain"},
-    {"dechunk", NULL, "Map chunk coordinates back (not in this build)"},
+    {"dechunk", paffy_dechunk_main, "Map chunk coordinates back to the sequences"},
     {"dedupe", paffy_dedupe_main, "Drop duplicate alignments"},
     {"filter", paffy_filter_main, "Filter alignments on their stats"},
     {"invert", paffy_invert_main, "Switch query and target coordinates"},
@@ -30,7 +29,7 @@ static const struct {
     {"tile", paffy_tile_main, "Give alignments tile levels along the query"},
     {"to_bed", paffy_to_bed_main, "Coverage of the query sequences in BED format"},
     {"trim", paffy_trim_main, "Slice off lower identity tails"},
-    {"upconvert", NULL, "Convert coordinates to extracted subsequences (not in this build)"},
+    {"upconvert", paffy_upconvert_main, "Convert coordinates to extracted subsequences"},
     {"split_file", paffy_split_file_main, "Split a PAF file per contig"},
     {"view", paffy_view_main, "Alignment stats per record and overall, with -a the base-level alignments"},
 };

@@ -334,6 +334,18 @@ static int pipelined_stream(paffy_hip_ctx *ctx, const paffy_stage *stages, int n
     return rc;
 }
 
+/* paffy upconvert: the FASTA headers and sequence lengths of its intervals */
+static const char *const *g_iv_headers;
+static const int64_t *g_iv_lens;
+static int64_t g_iv_n = 0;
+static int g_iv_set = 0;
+void host_set_intervals(const char *const *headers, const int64_t *seq_lens, int64_t n) {
+    g_iv_headers = headers;
+    g_iv_lens = seq_lens;
+    g_iv_n = n;
+    g_iv_set = 1;
+}
+
 int host_stream(const paffy_stage *stages, int n_stages, FILE *in, FILE *out) {
     paffy_hip_ctx *ctx = NULL;
     if (paffy_hip_create(&ctx, host_device()) != 0) {
@@ -345,6 +357,18 @@ int host_stream(const paffy_stage *stages, int n_stages, FILE *in, FILE *out) {
     if (g_seq_n > 0 && paffy_hip_set_sequences(ctx, g_seq_n, g_seq_names, g_seq_data, g_seq_lens) != 0) {
         fprintf(stderr, "paffy: could not load the sequences onto the GPU: %s\n", paffy_hip_last_error(ctx));
         return 1;
+    }
+    if (g_iv_set) {
+        const int rc = paffy_hip_set_intervals(ctx, g_iv_headers, g_iv_lens, g_iv_n);
+        if (rc == PAFFY_E_HEADER) { /* the reference's assert in decode_fasta_header, before it reads a record */
+            fprintf(stderr, "%s\n", paffy_hip_last_error(ctx));
+            fflush(out);
+            abort();
+        }
+        if (rc != 0) {
+            fprintf(stderr, "paffy: could not load the intervals onto the GPU: %s\n", paffy_hip_last_error(ctx));
+            return 1;
+        }
     }
     if (!g_dedupe_mode && !g_stats_mode) {
         int rc = pipelined_stream(ctx, stages, n_stages, in, out);

@@ -41,7 +41,14 @@ enum {
                                     `paffy view -s`, impl/paf_view.c:163-168); the record passes on unchanged. See paffy_hip_plan_stats() */
     PAFFY_TRIM_ENDS = 9,         /* paf_trim_ends(paf, n), impl/paf.c:575-598: n aligned bases off each end; n = the 64 bits of (p0, p1),
                                     see paffy_stage_trim_ends(); then paf_check like the other trims */
-    PAFFY_CHECK = 11             /* paf_check alone (impl/paf.c:427-461): the record passes on unchanged or fails */
+    PAFFY_CHECK = 11,            /* paf_check alone (impl/paf.c:427-461): the record passes on unchanged or fails */
+    PAFFY_DECHUNK = 12,          /* impl/paf_dechunk.c:24-37,114-118: names "name|length|chunk start" decoded (decode_fasta_header, impl/paf.c:716-731),
+                                    the chunk start added to start and end, length = the decoded length; then paf_check. The first stage only,
+                                    any list that fuses today may follow it; p0 != 0: fix the query side, p1 != 0: the target side
+                                    (paffy_stage_dechunk()) */
+    PAFFY_UPCONVERT = 13         /* impl/paf_upconvert.c:26-66,148-153: each side that falls in an interval of paffy_hip_set_intervals is
+                                    renamed "name|length|start" and shifted into it; paf_check on the coordinates; the cigar text is not
+                                    parsed and is written verbatim (paf_read(.., 0)). A stage list of its own */
 };
 /* OR-ed into a transform's kind: without the paf_check that the command loops run after it (impl/paf_invert.c:84-89) -- what the
  * library functions of inc/paf.h do (paf_invert, paf_trim_ends ... check nothing, impl/paf.c:463-598) */
@@ -62,6 +69,15 @@ static inline paffy_stage paffy_stage_trim_ends(int64_t end_bases) {
     s.kind = PAFFY_TRIM_ENDS;
     s.p0 = u.f[0];
     s.p1 = u.f[1];
+    return s;
+}
+
+/* `paffy dechunk` (-q: fix_target = 0, -t: fix_query = 0) */
+static inline paffy_stage paffy_stage_dechunk(int fix_query, int fix_target) {
+    paffy_stage s;
+    s.kind = PAFFY_DECHUNK;
+    s.p0 = fix_query ? 1.0f : 0.0f;
+    s.p1 = fix_target ? 1.0f : 0.0f;
     return s;
 }
 
@@ -88,7 +104,9 @@ enum {
     PAFFY_ERR_MISSING_TARGET_SEQ = 18, /* impl/paf_add_mismatches.c:123-127 exit(1)     */
     PAFFY_ERR_TILE_ASSERT = 19,        /* impl/paf.c:685,698,708; impl/paf_tile.c:57,86,171 */
     PAFFY_ERR_SEQ_RANGE = 21,          /* paf_encode_mismatches would read outside a sequence */
-    PAFFY_ERR_CHAIN_ASSERT = 22        /* impl/chaining.c:275,278-281 asserts              */
+    PAFFY_ERR_CHAIN_ASSERT = 22,       /* impl/chaining.c:275,278-281 asserts              */
+    PAFFY_ERR_DECHUNK_HEADER = 23,     /* impl/paf.c:722,725 asserts: a name without "|length|start" (stage 0) */
+    PAFFY_ERR_UPCONVERT_ASSERT = 24    /* impl/paf_upconvert.c:33 assert: a side starts inside an interval and ends beyond it */
 };
 
 /* Call-level failures (negative return values). */
@@ -97,7 +115,8 @@ enum {
     PAFFY_E_ARG = -2,         /* bad argument (NULL, misaligned pointer, a batch of 2 GiB - 64 bytes or more) */
     PAFFY_E_UNSUPPORTED = -3, /* stage list this build cannot fuse (run the stages one by one)  */
     PAFFY_E_CAPACITY = -4,    /* output buffer smaller than the planned size                   */
-    PAFFY_E_STATE = -5        /* emit without a successful plan                                */
+    PAFFY_E_STATE = -5,       /* emit without a successful plan                                */
+    PAFFY_E_HEADER = -6       /* paffy_hip_set_intervals: a FASTA header without "|length|start" (the reference asserts) */
 };
 
 typedef struct {
@@ -351,6 +370,14 @@ int paffy_hip_parse_host(paffy_hip_ctx *ctx, const char *h_in, int64_t in_len, p
  * header used as key, seqs[i] / lens[i] the bases (host memory; copied to HBM here).
  */
 int paffy_hip_set_sequences(paffy_hip_ctx *ctx, int64_t n, const char *const *names, const char *const *seqs, const int64_t *lens);
+
+/*
+ * Intervals for PAFFY_UPCONVERT: what impl/paf_upconvert.c:26-32 makes of every FASTA record of the command's files -- headers[i] decoded
+ * as "name|length|start" (decode_fasta_header, impl/paf.c:716-731), end = start + seq_lens[i] (strlen of the sequence) -- sorted by
+ * (name, start) with the C library's qsort as stList_sort does (equal keys keep whatever order qsort gives them). A header that does not
+ * decode: PAFFY_E_HEADER and no intervals (the reference aborts before it writes anything). n = 0: no side is ever renamed.
+ */
+int paffy_hip_set_intervals(paffy_hip_ctx *ctx, const char *const *headers, const int64_t *seq_lens, int64_t n);
 
 /*
  * Thresholds of `paffy filter` as its main() holds them (impl/paf_filter.c:27-32; -s -t -w pass through atoi, -u -v

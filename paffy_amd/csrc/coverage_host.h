@@ -145,8 +145,10 @@ __global__ __launch_bounds__(PAFFY_NT) void k_line_size(const RecMeta *meta, con
 /* one WAVE per line (four lines per workgroup, no barrier): the header is built in the wave's LDS; the line leaves as 16-byte stores
    at 16-byte aligned output addresses, the cigar read with 16-byte loads at whatever alignment it has in the input */
 #define LINE_HDR_BYTES (3 * PAFFY_TMPL_MAX + 16)
+/* names2: the output names of upconvert's interval table -- RecMeta::pad0 bit 0 / bit 1: the query / target name is a slice of it */
 __global__ __launch_bounds__(PAFFY_NT) void k_line_emit(const uint8_t *const *batch_in, const RecMeta *meta, const uint32_t *order, const int64_t *level,
-                                                         const uint64_t *out_off, uint64_t first_line, uint64_t n_lines, uint64_t base_off, uint8_t *out) {
+                                                         const uint64_t *out_off, uint64_t first_line, uint64_t n_lines, uint64_t base_off, uint8_t *out,
+                                                         const uint8_t *names2) {
     __shared__ uint8_t hdr_all[PAFFY_NWAVE][LINE_HDR_BYTES];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t li = (uint64_t)blockIdx.x * PAFFY_NWAVE + wave;
@@ -162,7 +164,7 @@ __global__ __launch_bounds__(PAFFY_NT) void k_line_emit(const uint8_t *const *ba
     const bool direct = hl > 3 * PAFFY_TMPL_MAX; /* header longer than the LDS staging: built in place */
     {
         Piece w{direct ? o : hdr, 0, direct ? hl : 3 * PAFFY_TMPL_MAX, false};
-        build_header(w, s, in, false);
+        build_header2(w, s, (m.pad0 & 1u) ? names2 : in, (m.pad0 & 2u) ? names2 : in, false);
         if (m.has_cg) w.str("\tcg:Z:", 6);
     }
     __builtin_amdgcn_wave_barrier(); /* a wave's LDS operations execute in order */

@@ -987,6 +987,8 @@ __global__ __launch_bounds__(256) void k_flat_lane(FlatSizeParams F) {
             } else if (st.kind == PAFFY_STATS) {
                 if (flags & FLAT_F_NONPLAIN) { give_up = true; break; }
                 flat_stats(P, rec, v);
+            } else if (st.kind == PAFFY_CHECK) { /* what is left of `paffy dechunk` once k_dechunk has rewritten the header */
+                rc = flat_check(s, v);
             } else if (st.kind != PAFFY_PASS) {
                 give_up = true;
                 break;
@@ -1415,6 +1417,8 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
         } else if (st.kind == PAFFY_STATS) {
             if (flags & FLAT_F_NONPLAIN) return flat_leave(F, rec, FLAT_WHY_NONPLAIN);
             if (lane == 0) flat_stats(P, rec, v);
+        } else if (st.kind == PAFFY_CHECK) {
+            rc = flat_check(s, v);
         } else if (st.kind != PAFFY_PASS) {
             return flat_leave(F, rec, FLAT_WHY_STAGE);
         }

@@ -14,6 +14,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -498,6 +499,194 @@ __global__ __launch_bounds__(PAFFY_NT) void k_header(const uint8_t *in, const ui
 }
 
 /* ------------------------------------------------------------------ */
+/* dechunk (impl/paf_dechunk.c)                                         */
+/* ------------------------------------------------------------------ */
+
+/* sscanf(token, "%" PRIi64) of glibc x86-64 ("%li": strtol with base 0 on what the scanner took): white space, a sign, a 0x / 0X or 0
+   prefix, the digits of the base; a value outside int64 saturates. false: nothing converted (the reference's assert) */
+__device__ bool scan_li_dev(const uint8_t *in, uint32_t p, uint32_t e, int64_t &out) {
+    while (p < e && (in[p] == ' ' || (in[p] >= 9 && in[p] <= 13))) p++;
+    if (p == e) return false; /* sscanf's EOF */
+    bool neg = false;
+    if (in[p] == '+' || in[p] == '-') {
+        neg = in[p] == '-';
+        p++;
+    }
+    uint32_t base = 10;
+    bool any = false; /* a digit (the 0 of a prefix counts) */
+    if (p < e && in[p] == '0') {
+        any = true;
+        p++;
+        if (p < e && (in[p] | 0x20u) == 'x') {
+            base = 16;
+            p++;
+        } else {
+            base = 8;
+        }
+    }
+    uint64_t v = 0;
+    bool over = false;
+    for (; p < e; p++) {
+        const uint32_t ch = in[p], lc = ch | 0x20u;
+        uint32_t d;
+        if (ch - '0' < 10u) d = ch - '0';
+        else if (lc - 'a' < 6u) d = lc - 'a' + 10u;
+        else break;
+        if (d >= base) break;
+        any = true;
+        if (v > (~0ull - d) / base) over = true;
+        else v = v * base + d;
+    }
+    if (!any) return false;
+    if (neg) out = (over || v > (1ull << 63)) ? INT64_MIN : (int64_t)(0ull - v);
+    else out = (over || v > (uint64_t)INT64_MAX) ? INT64_MAX : (int64_t)v;
+    return true;
+}
+
+/* decode_fasta_header (impl/paf.c:716-731) of one name and the shift of impl/paf_dechunk.c:24-29: the last '|'-token is the chunk's start, the
+   one before it the sequence length, the rest (joined by '|' again: the text in front of the second-to-last '|') the new name -- a prefix
+   of the old one, so the record keeps addressing its name in the input text. The int64 sums wrap as the reference's do. */
+__device__ bool dechunk_side(const uint8_t *in, uint32_t off, uint32_t &len, int64_t &start, int64_t &end, int64_t &length) {
+    const uint32_t e = off + len;
+    uint32_t c1 = e, c2 = e; /* the last and the second-to-last '|' */
+    for (uint32_t i = e; i > off; i--)
+        if (in[i - 1] == '|') {
+            if (c1 == e) c1 = i - 1;
+            else {
+                c2 = i - 1;
+                break;
+            }
+        }
+    if (c1 == e) return false; /* one token: its start converts or not, the length then peeks an empty list */
+    int64_t cs, cl;
+    if (!scan_li_dev(in, c1 + 1, e, cs)) return false;
+    if (!scan_li_dev(in, c2 == e ? off : c2 + 1, c1, cl)) return false;
+    len = c2 == e ? 0u : c2 - off; /* two tokens: fastaEncodeHeader of an empty list */
+    start = (int64_t)((uint64_t)start + (uint64_t)cs);
+    end = (int64_t)((uint64_t)end + (uint64_t)cs);
+    length = cl;
+    return true;
+}
+
+/*
+ * One lane per record, between k_header and the sizing kernels: the fixed sides' names and coordinates of RecMeta rewritten in place,
+ * so that everything after (sizes, digit counts, the flat pass, the writers) sees the dechunked record. A name that does not decode is
+ * PAFFY_ERR_DECHUNK_HEADER -- unless the cigar, which the reference parses while reading (impl/paf_dechunk.c:114), fails first.
+ */
+__global__ __launch_bounds__(PAFFY_NT) void k_dechunk(const uint8_t *in, RecMeta *meta, uint32_t n_lines, uint32_t fix_query, uint32_t fix_target) {
+    const uint32_t r = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (r >= n_lines) return;
+    RecMeta &m = meta[r];
+    if (m.err) return;
+    bool ok = true;
+    if (fix_query) ok = dechunk_side(in, m.qname_off, m.qname_len, m.qs, m.qe, m.qlen);
+    if (ok && fix_target) ok = dechunk_side(in, m.tname_off, m.tname_len, m.ts, m.te, m.tlen);
+    if (ok) return;
+    int32_t err = PAFFY_ERR_DECHUNK_HEADER, aux = 0;
+    if (m.has_cg && m.cg_len > 0) { /* cigar_parse, impl/paf.c:70-110: the first byte that is neither a digit nor an op; '\0' after digits */
+        bool digit_last = false;
+        for (uint32_t i = m.cg_off; i < m.cg_off + m.cg_len; i++) {
+            const uint32_t ch = in[i];
+            digit_last = ch - '0' < 10u;
+            if (digit_last || ch == 'M' || ch == 'I' || ch == 'D' || ch == '=' || ch == 'X') continue;
+            err = PAFFY_ERR_CIGAR_CHAR;
+            aux = (int32_t)ch;
+            break;
+        }
+        if (err != PAFFY_ERR_CIGAR_CHAR && digit_last) err = PAFFY_ERR_CIGAR_CHAR;
+    }
+    m.err = err;
+    m.err_aux = aux;
+}
+
+/* ------------------------------------------------------------------ */
+/* upconvert (impl/paf_upconvert.c)                                     */
+/* ------------------------------------------------------------------ */
+
+/* One interval of paffy_hip_set_intervals, in cmp_intervals order (impl/paf.c:733-737): name and output name "name|length|start" are
+   slices of one blob. */
+struct UpInterval {
+    int64_t start, end, length;
+    uint32_t name_off, name_len, out_off, out_len;
+};
+
+/* strcmp of the record's name slice with an interval's name, bytes unsigned; only the sign is used */
+__device__ int up_strcmp(const uint8_t *a, uint32_t alen, const uint8_t *b, uint32_t blen) {
+    for (uint32_t i = 0;; i++) {
+        const uint32_t x = i < alen ? a[i] : 0u, y = i < blen ? b[i] : 0u;
+        if (x != y) return x < y ? -1 : 1;
+        if (x == 0) return 0;
+    }
+}
+
+/* stList_binarySearch(intervals, side, cmp_overlapping_intervals) (impl/paf_upconvert.c:26-44): glibc's bsearch probes, key first --
+   idx = (l + u) / 2, < 0: u = idx, > 0: l = idx + 1. The end of an interval is inclusive, so which of two adjacent intervals a start on
+   their common end meets first is this probe order's. Returns the interval, -1 for none, -2 for the comparator's assert. */
+__device__ int32_t up_search(const uint8_t *name, uint32_t name_len, int64_t start, int64_t end, const UpInterval *iv, uint32_t n_iv, const uint8_t *names) {
+    uint32_t l = 0, u = n_iv;
+    while (l < u) {
+        const uint32_t idx = (l + u) / 2u;
+        const UpInterval y = iv[idx];
+        int k = up_strcmp(name, name_len, names + y.name_off, y.name_len);
+        if (k == 0) {
+            if (start < y.start) k = -1;
+            else if (start <= y.end) return end <= y.end ? (int32_t)idx : -2;
+            else k = 1;
+        }
+        if (k < 0) u = idx;
+        else l = idx + 1u;
+    }
+    return -1;
+}
+
+/*
+ * One lane per record, after k_header: fix_interval of the query, then of the target (impl/paf_upconvert.c:46-66, 150-151), and paf_check
+ * on the coordinates (the cigar is not parsed: impl/paf_upconvert.c:148). A renamed side addresses its new name in the interval table's
+ * output names (RecMeta::pad0 bit 0 / bit 1, read by k_line_emit). The first failure in stream order goes to DevInfo::first_err_key;
+ * order / level are the line writer's (every record, in input order).
+ */
+__global__ __launch_bounds__(PAFFY_NT) void k_upconvert(const uint8_t *in, RecMeta *meta, uint32_t n_lines, const UpInterval *iv, uint32_t n_iv,
+                                                        const uint8_t *names, uint32_t check, uint32_t *order, int64_t *level, DevInfo *info) {
+    const uint32_t r = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (r >= n_lines) return;
+    RecMeta &m = meta[r];
+    order[r] = r;
+    level[r] = m.tile_level;
+    int32_t code = m.err, stage = -1;
+    if (!code) {
+        stage = 0;
+        const int32_t qi = up_search(in + m.qname_off, m.qname_len, m.qs, m.qe, iv, n_iv, names);
+        const int32_t ti = qi == -2 ? -1 : up_search(in + m.tname_off, m.tname_len, m.ts, m.te, iv, n_iv, names);
+        if (qi == -2 || ti == -2) code = PAFFY_ERR_UPCONVERT_ASSERT;
+        if (qi >= 0) {
+            const UpInterval y = iv[qi];
+            m.qname_off = y.out_off;
+            m.qname_len = y.out_len;
+            m.qs -= y.start;
+            m.qe -= y.start;
+            m.qlen = y.length;
+            m.pad0 |= 1u;
+        }
+        if (ti >= 0) {
+            const UpInterval y = iv[ti];
+            m.tname_off = y.out_off;
+            m.tname_len = y.out_len;
+            m.ts -= y.start;
+            m.te -= y.start;
+            m.tlen = y.length;
+            m.pad0 |= 2u;
+        }
+        if (!code && check) { /* paf_check without a cigar, impl/paf.c:427-439 */
+            if (m.qs < 0 || m.qs >= m.qlen) code = PAFFY_ERR_CHECK_QSTART;
+            else if (m.qs > m.qe || m.qe > m.qlen) code = PAFFY_ERR_CHECK_QEND;
+            else if (m.ts < 0 || m.ts >= m.tlen) code = PAFFY_ERR_CHECK_TSTART;
+            else if (m.ts > m.te || m.te > m.tlen) code = PAFFY_ERR_CHECK_TEND;
+        }
+    }
+    if (code) atomicMin(&info->first_err_key, ((unsigned long long)r << 16) | ((unsigned long long)((stage + 1) & 0xff) << 8) | (unsigned long long)code);
+}
+
+/* ------------------------------------------------------------------ */
 /* sequence lookup (add_mismatches)                                     */
 /* ------------------------------------------------------------------ */
 
@@ -913,6 +1102,10 @@ struct paffy_hip_ctx {
     const int64_t *line_level = nullptr;
     const uint64_t *line_off = nullptr;
     uint64_t line_n = 0;
+    const uint8_t *line_names2 = nullptr; /* upconvert: the interval table's output names (k_line_emit) */
+    /* upconvert (paffy_hip_set_intervals): the FASTA intervals sorted by (name, start), their names and output names in one blob */
+    DevBuf up_table, up_names;
+    uint32_t n_intervals = 0;
     DevInfo *h_info = nullptr; /* pinned */
     /* plan state */
     bool planned = false;
@@ -1091,7 +1284,7 @@ void paffy_hip_destroy(paffy_hip_ctx *c) {
     DevBuf *bufs[] = {&c->tile_counts, &c->sep_pos, &c->nl_idx, &c->meta, &c->out_len, &c->out_rows, &c->status, &c->err_aux,
                       &c->n_ops, &c->arena_off, &c->out_off, &c->w_list, &c->b_list, &c->b_list1, &c->arena, &c->info, &c->synth_sizes, &c->rec_plan, &c->ops_mirror, &c->seq_blob, &c->seq_table, &c->seq_names, &c->seq_name_off, &c->synth4_contigs, &c->synth4_q, &c->synth4_t, &c->seq_comp, &c->seq_raw, &c->pretty_off, &c->pretty_out, &c->pretty_err, &c->host_in, &c->host_out, &c->rec_stats, &c->flat_nd, &c->flat_rec, &c->flat_chunks, &c->flat_sums, &c->flat_done, &c->flat_items, &c->flat_pieces, &c->add_pieces, &c->add_scr_cnt, &c->add_scr_off, &c->add_new_cnt, &c->add_new_off, &c->add_text, &c->add_bad, &c->add_part, &c->add_scratch, &c->add_new_ops, &c->bed_keys, &c->bed_tab, &c->bed_starts, &c->bed_len, &c->bed_off, &c->bed_tiles,
                       &c->rec_qseq, &c->rec_tseq, &c->tile_keys, &c->tile_order, &c->tile_rank, &c->tile_coff, &c->tile_cbase,
-                      &c->tile_cov, &c->tile_level, &c->tile_len, &c->tile_items, &c->tile_slots, &c->tile_parts, &c->scan_part, &c->dedupe_keys, &c->emit_order, &c->order_cnt};
+                      &c->tile_cov, &c->tile_level, &c->tile_len, &c->tile_items, &c->tile_slots, &c->tile_parts, &c->scan_part, &c->dedupe_keys, &c->emit_order, &c->order_cnt, &c->up_table, &c->up_names};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     dedupe_free(c);
@@ -1211,6 +1404,7 @@ static int index_and_parse(paffy_hip_ctx *c, const uint8_t *in, uint32_t len, ui
     return 0;
 }
 
+static int upconvert_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bool check, paffy_plan_info *info);
 int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages, const void *d_in, int64_t in_len,
                    paffy_plan_info *info) {
     if (!c || !info || (n_stages > 0 && !stages) || n_stages < 0 || n_stages > PAFFY_MAX_STAGES) return PAFFY_E_ARG;
@@ -1222,6 +1416,21 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
         norm[i] = stages[i];
         if (stages[i].kind & PAFFY_NO_CHECK) nocheck_mask |= 1u << i;
         norm[i].kind = stages[i].kind & ~PAFFY_NO_CHECK;
+    }
+    /* `paffy dechunk` in front: k_dechunk rewrites the parsed names and coordinates, and what is left of the stage is its paf_check */
+    const bool dechunk = n_stages > 0 && norm[0].kind == PAFFY_DECHUNK;
+    const uint32_t fix_query = dechunk && norm[0].p0 != 0.0f, fix_target = dechunk && norm[0].p1 != 0.0f;
+    if (dechunk) {
+        norm[0].kind = (nocheck_mask & 1u) ? PAFFY_PASS : PAFFY_CHECK;
+        norm[0].p0 = norm[0].p1 = 0.0f;
+        nocheck_mask &= ~1u;
+    }
+    if (n_stages > 0 && norm[0].kind == PAFFY_UPCONVERT) { /* its read differs (no cigar parse): a plan of its own */
+        if (n_stages != 1) {
+            c->last_error = "upconvert is a stage list of its own";
+            return PAFFY_E_UNSUPPORTED;
+        }
+        return upconvert_plan(c, d_in, in_len, (nocheck_mask & 1u) == 0, info);
     }
     stages = norm;
     for (int32_t i = 0; i < n_stages; i++) {
@@ -1299,7 +1508,7 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
     }
     /* ... and a fixed trim (`paffy trim -f`) as the pipe's last stage: the wave kernel finds the two ops it stops at (flat_find_aligned) */
     const bool fixed_last = n_stages > 0 && stages[n_stages - 1].kind == PAFFY_TRIM_FIXED;
-    const uint32_t flat_kinds = PAFFY_MASK_LEAN | (1u << PAFFY_FILTER) | (has_shatter_stage ? 0u : 1u << PAFFY_STATS);
+    const uint32_t flat_kinds = PAFFY_MASK_LEAN | (1u << PAFFY_FILTER) | (has_shatter_stage ? 0u : 1u << PAFFY_STATS) | (dechunk ? 1u << PAFFY_CHECK : 0u);
     for (int32_t i = 0; i < n_stages; i++)
         lean_or_filter = lean_or_filter && (((flat_kinds >> stages[i].kind) & 1u) || (fixed_last && i == n_stages - 1));
     const bool flat = (lean_or_filter && nocheck_mask == 0 && !flat_off) || flat_add;
@@ -1307,6 +1516,9 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
         int rc = index_and_parse(c, in, len, &n_lines, lvl0_max, flat);
         if (rc) return rc;
     }
+    if ((fix_query || fix_target) && n_lines > 0)
+        LAUNCH(c, "k_dechunk", k_dechunk, dim3((n_lines + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, in, static_cast<RecMeta *>(c->meta.p), n_lines,
+               fix_query, fix_target);
     kp.lvl0_max = lvl0_max;
     kp.lvl0_long_bytes = (!add_not_last && !lvl0_long && !c->lvl0_long_off && lvl0_long_bytes > 2u * PAFFY_OPS_CAP) ? lvl0_long_bytes : 0u;
 
@@ -1636,6 +1848,7 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
         pl.error.code = (int32_t)(k & 0xff);
         pl.error.stage = (int32_t)((k >> 8) & 0xff) - 1;
         pl.error.record = (int64_t)(k >> 16);
+        if (pl.error.code == PAFFY_ERR_DECHUNK_HEADER) pl.error.stage = 0; /* k_dechunk's verdict travels with the parse's (RecMeta::err) */
         int32_t aux = 0;
         HIPCHK(c, hipMemcpy(&aux, static_cast<int32_t *>(c->err_aux.p) + pl.error.record, sizeof(aux), hipMemcpyDeviceToHost));
         pl.error.aux = aux;
@@ -1701,6 +1914,7 @@ static int lines_plan(paffy_hip_ctx *c, CovState &S, uint64_t n) {
     c->plan.n_rows = (int64_t)n;
     c->line_batches = static_cast<const uint8_t *const *>(S.batch_ptrs.p);
     c->line_meta = static_cast<const RecMeta *>(S.meta.p);
+    c->line_names2 = nullptr;
     c->line_order = static_cast<const uint32_t *>(S.order.p);
     c->line_level = static_cast<const int64_t *>(S.level.p);
     c->line_off = static_cast<const uint64_t *>(S.out_off.p);
@@ -2180,6 +2394,165 @@ int64_t paffy_hip_tile_keys(paffy_hip_ctx *c, int64_t cap_lines, void *d_keys) {
     return (int64_t)n;
 }
 
+/* `paffy upconvert` (impl/paf_upconvert.c:144-156): index, header parse, k_upconvert, then the line writer of tile / dedupe (header + the
+   cigar text as it was read) for every record in front of the first failing one */
+static int upconvert_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bool check, paffy_plan_info *info) {
+    c->planned = false;
+    c->plan_is_tile = true;
+    c->plan_is_bed = false;
+    c->flat_left = -1;
+    memset(info, 0, sizeof(*info));
+    memset(&c->plan, 0, sizeof(c->plan));
+    info->in_bytes = c->plan.in_bytes = in_len;
+    memset(&c->kp, 0, sizeof(c->kp));
+    c->tile_n = 0;
+    c->line_n = 0;
+    if (in_len == 0) {
+        c->planned = true;
+        return 0;
+    }
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    uint32_t n = 0;
+    {
+        int rc = index_and_parse(c, in, (uint32_t)in_len, &n);
+        if (rc) return rc;
+    }
+    c->plan.n_records = n;
+    if (n == 0) {
+        if (fetch_info(c)) return PAFFY_E_HIP;
+        *info = c->plan;
+        c->planned = true;
+        return 0;
+    }
+    if (ensure(c, c->tile_level, sizeof(int64_t) * (size_t)n) || ensure(c, c->tile_order, sizeof(uint32_t) * (size_t)n) ||
+        ensure(c, c->tile_len, sizeof(int64_t) * (size_t)(n + 2)))
+        return PAFFY_E_HIP;
+    RecMeta *meta = static_cast<RecMeta *>(c->meta.p);
+    LAUNCH(c, "k_upconvert", k_upconvert, dim3((n + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, in, meta, n, static_cast<const UpInterval *>(c->up_table.p),
+           c->n_intervals, static_cast<const uint8_t *>(c->up_names.p), check ? 1u : 0u, static_cast<uint32_t *>(c->tile_order.p),
+           static_cast<int64_t *>(c->tile_level.p), static_cast<DevInfo *>(c->info.p));
+    if (fetch_info(c)) return PAFFY_E_HIP;
+    uint32_t nk = n;
+    if (c->h_info->first_err_key != ~0ull) {
+        const unsigned long long k = c->h_info->first_err_key;
+        nk = (uint32_t)(k >> 16);
+        c->plan.error.code = (int32_t)(k & 0xff);
+        c->plan.error.stage = (int32_t)((k >> 8) & 0xff) - 1;
+        c->plan.error.record = nk;
+        if (c->plan.error.stage < 0) {
+            RecMeta m;
+            HIPCHK(c, hipMemcpy(&m, meta + nk, sizeof(m), hipMemcpyDeviceToHost));
+            c->plan.error.aux = m.err_aux;
+        }
+    }
+    int64_t total = 0;
+    if (nk > 0) {
+        int64_t *lens = static_cast<int64_t *>(c->tile_len.p);
+        LAUNCH(c, "k_line_size", k_line_size, dim3((nk + 1 + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, static_cast<const RecMeta *>(meta),
+               static_cast<const uint32_t *>(c->tile_order.p), static_cast<const int64_t *>(c->tile_level.p), (uint64_t)nk, reinterpret_cast<uint64_t *>(lens));
+        if (ensure(c, c->out_off, sizeof(int64_t) * ((size_t)nk + 1))) return PAFFY_E_HIP;
+        if (!c->dedupe) c->dedupe = new DedupeState();
+        DedupeState &D = *c->dedupe; /* its scratch for the scan */
+        size_t bytes = 0;
+        RPCHK(c, rocprim::exclusive_scan(nullptr, bytes, lens, static_cast<int64_t *>(c->out_off.p), (int64_t)0, (size_t)nk + 1, rocprim::plus<int64_t>(), c->stream));
+        if (ensure(c, D.tmp, bytes + 16)) return PAFFY_E_HIP;
+        RPCHK(c, rocprim::exclusive_scan(D.tmp.p, bytes, lens, static_cast<int64_t *>(c->out_off.p), (int64_t)0, (size_t)nk + 1, rocprim::plus<int64_t>(), c->stream));
+        HIPCHK(c, hipMemcpyAsync(&total, static_cast<int64_t *>(c->out_off.p) + nk, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (ensure(c, c->one_batch, sizeof(void *))) return PAFFY_E_HIP;
+        HIPCHK(c, hipMemcpyAsync(c->one_batch.p, &in, sizeof(void *), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (c->profile) prof_collect(c);
+    c->plan.out_bytes = total;
+    c->plan.n_rows = nk;
+    c->tile_n = total ? nk : 0;
+    c->line_batches = static_cast<const uint8_t *const *>(c->one_batch.p);
+    c->line_meta = meta;
+    c->line_names2 = static_cast<const uint8_t *>(c->up_names.p);
+    c->line_order = static_cast<const uint32_t *>(c->tile_order.p);
+    c->line_level = static_cast<const int64_t *>(c->tile_level.p);
+    c->line_off = static_cast<const uint64_t *>(c->out_off.p);
+    c->line_n = c->tile_n;
+    *info = c->plan;
+    c->planned = true;
+    return 0;
+}
+
+/* decode_fasta_header (impl/paf.c:716-731) of a FASTA header: false when the reference's asserts would fire */
+static bool up_decode(const char *h, std::string &name, int64_t &start, int64_t &length) {
+    const size_t n = strlen(h);
+    size_t c1 = n, c2 = n; /* the last and the second-to-last '|' */
+    for (size_t i = n; i > 0; i--)
+        if (h[i - 1] == '|') {
+            if (c1 == n) c1 = i - 1;
+            else {
+                c2 = i - 1;
+                break;
+            }
+        }
+    if (c1 == n) return false;
+    int64_t a = 0, b = 0;
+    const std::string ts(h + c1 + 1), tl(c2 == n ? std::string(h, c1) : std::string(h + c2 + 1, c1 - c2 - 1));
+    if (sscanf(ts.c_str(), "%" SCNi64, &a) != 1 || sscanf(tl.c_str(), "%" SCNi64, &b) != 1) return false;
+    name.assign(h, c2 == n ? 0 : c2);
+    start = a;
+    length = b;
+    return true;
+}
+
+struct UpHost {
+    std::string name;
+    int64_t start, end, length;
+};
+static int up_cmp_intervals(const void *i, const void *j) { /* cmp_intervals, impl/paf.c:733-737 */
+    const UpHost *x = *static_cast<const UpHost *const *>(i), *y = *static_cast<const UpHost *const *>(j);
+    const int k = strcmp(x->name.c_str(), y->name.c_str());
+    return k == 0 ? (x->start < y->start ? -1 : (x->start > y->start ? 1 : 0)) : k;
+}
+
+int paffy_hip_set_intervals(paffy_hip_ctx *c, const char *const *headers, const int64_t *seq_lens, int64_t n) {
+    if (!c || n < 0 || n >= (1ll << 31) || (n > 0 && (!headers || !seq_lens))) return PAFFY_E_ARG;
+    c->n_intervals = 0;
+    std::vector<UpHost> iv((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        if (!headers[i] || !up_decode(headers[i], iv[(size_t)i].name, iv[(size_t)i].start, iv[(size_t)i].length)) {
+            c->last_error = "upconvert: a FASTA header does not end in |length|start";
+            return PAFFY_E_HEADER;
+        }
+        iv[(size_t)i].end = (int64_t)((uint64_t)iv[(size_t)i].start + (uint64_t)seq_lens[i]); /* i->start + strlen(sequence) */
+    }
+    /* stList_sort: qsort of the list's pointer array */
+    std::vector<UpHost *> ptr((size_t)n);
+    for (int64_t i = 0; i < n; i++) ptr[(size_t)i] = &iv[(size_t)i];
+    if (n > 1) qsort(ptr.data(), (size_t)n, sizeof(UpHost *), up_cmp_intervals);
+    std::vector<UpInterval> tab((size_t)n);
+    std::string blob;
+    char num[64];
+    for (int64_t i = 0; i < n; i++) {
+        const UpHost &h = *ptr[(size_t)i];
+        UpInterval &t = tab[(size_t)i];
+        t.start = h.start;
+        t.end = h.end;
+        t.length = h.length;
+        t.name_off = (uint32_t)blob.size();
+        t.name_len = (uint32_t)h.name.size();
+        blob += h.name;
+        snprintf(num, sizeof(num), "|%lld|%lld", (long long)h.length, (long long)h.start); /* "%s|%" PRIi64 "|%" PRIi64, impl/paf_upconvert.c:55 */
+        t.out_off = (uint32_t)blob.size();
+        t.out_len = t.name_len + (uint32_t)strlen(num);
+        blob += h.name;
+        blob += num;
+        if (blob.size() >= 0xffffffffull) return PAFFY_E_ARG;
+    }
+    if (n > 0) {
+        if (ensure(c, c->up_table, sizeof(UpInterval) * (size_t)n) || ensure(c, c->up_names, blob.size() + 16)) return PAFFY_E_HIP;
+        HIPCHK(c, hipMemcpy(c->up_table.p, tab.data(), sizeof(UpInterval) * (size_t)n, hipMemcpyHostToDevice));
+        if (!blob.empty()) HIPCHK(c, hipMemcpy(c->up_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    }
+    c->n_intervals = (uint32_t)n;
+    return 0;
+}
+
 int paffy_hip_dedupe_reset(paffy_hip_ctx *c) {
     if (!c) return PAFFY_E_ARG;
     if (c->dedupe) c->dedupe->seen_n = 0;
@@ -2265,6 +2638,7 @@ int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, in
     c->tile_n = total ? nk : 0;
     c->line_batches = static_cast<const uint8_t *const *>(c->one_batch.p);
     c->line_meta = static_cast<const RecMeta *>(c->meta.p);
+    c->line_names2 = nullptr;
     c->line_order = static_cast<const uint32_t *>(c->tile_order.p);
     c->line_level = static_cast<const int64_t *>(c->tile_level.p);
     c->line_off = static_cast<const uint64_t *>(c->out_off.p);
@@ -2303,7 +2677,7 @@ int paffy_hip_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap) {
     }
     if (c->plan_is_tile) {
         if (c->line_n) LAUNCH(c, "k_tile_emit", k_line_emit, dim3((unsigned)((c->line_n + PAFFY_NWAVE - 1) / PAFFY_NWAVE)), dim3(PAFFY_NT), 0, c->line_batches, c->line_meta,
-                              c->line_order, c->line_level, c->line_off, (uint64_t)0, c->line_n, (uint64_t)0, static_cast<uint8_t *>(d_out));
+                              c->line_order, c->line_level, c->line_off, (uint64_t)0, c->line_n, (uint64_t)0, static_cast<uint8_t *>(d_out), c->line_names2);
         return 0;
     }
     KParams kp = c->kp;
@@ -2338,7 +2712,7 @@ int paffy_hip_emit_lines(paffy_hip_ctx *c, int64_t first, int64_t n, void *d_out
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((int64_t)(hi - lo) > out_cap) return PAFFY_E_CAPACITY;
     LAUNCH(c, "k_tile_emit", k_line_emit, dim3((unsigned)((n + PAFFY_NWAVE - 1) / PAFFY_NWAVE)), dim3(PAFFY_NT), 0, c->line_batches, c->line_meta, c->line_order, c->line_level,
-           c->line_off, (uint64_t)first, (uint64_t)n, lo, static_cast<uint8_t *>(d_out));
+           c->line_off, (uint64_t)first, (uint64_t)n, lo, static_cast<uint8_t *>(d_out), c->line_names2);
     *bytes = (int64_t)(hi - lo);
     return 0;
 }
@@ -3063,6 +3437,8 @@ const char *paffy_hip_error_string(int32_t code) {
         case PAFFY_ERR_TILE_ASSERT: return "tile: coverage assertion failed";
         case PAFFY_ERR_SEQ_RANGE: return "alignment reaches outside a sequence";
         case PAFFY_ERR_CHAIN_ASSERT: return "chain: trim fraction outside [0, 1] or a negative alignment length";
+        case PAFFY_ERR_DECHUNK_HEADER: return "dechunk: a name does not end in |length|start";
+        case PAFFY_ERR_UPCONVERT_ASSERT: return "upconvert: an alignment starts inside an interval and ends beyond it";
         default: return "unknown error";
     }
 }

@@ -2748,7 +2748,9 @@ __device__ __forceinline__ void header_put(uint8_t *p, uint32_t cap, uint32_t at
     for (uint32_t b = 0; b < 8; b++)
         if (b < n && at + b < cap) p[at + b] = (uint8_t)(w >> (8 * b));
 }
-__device__ __forceinline__ void build_header(Piece &w, const RecState &s, const uint8_t *in, bool newline) {
+/* qsrc / tsrc: the text the names are slices of -- the input for every writer but upconvert's, whose renamed sides are the interval
+   table's output names (k_line_emit) */
+__device__ __forceinline__ void build_header2(Piece &w, const RecState &s, const uint8_t *qsrc, const uint8_t *tsrc, bool newline) {
     const uint32_t lane = threadIdx.x & 63u;
     const HeaderItem it = header_item(s, newline, lane);
     DecText d;
@@ -2778,11 +2780,12 @@ __device__ __forceinline__ void build_header(Piece &w, const RecState &s, const 
     /* the names, by all lanes: the query name opens the line, the target name follows item 5's tab */
     const uint32_t t_at = w.n + (uint32_t)__shfl((int)(inc - len), 5) + 1u;
     for (uint32_t i = lane; i < s.qn_len; i += 64)
-        if (w.n + i < w.cap) w.p[w.n + i] = in[s.qn_off + i];
+        if (w.n + i < w.cap) w.p[w.n + i] = qsrc[s.qn_off + i];
     for (uint32_t i = lane; i < s.tn_len; i += 64)
-        if (t_at + i < w.cap) w.p[t_at + i] = in[s.tn_off + i];
+        if (t_at + i < w.cap) w.p[t_at + i] = tsrc[s.tn_off + i];
     w.n += total;
 }
+__device__ __forceinline__ void build_header(Piece &w, const RecState &s, const uint8_t *in, bool newline) { build_header2(w, s, in, in, newline); }
 /* the same items' lengths, one per lane: for the callers that are whole waves */
 __device__ __forceinline__ uint32_t header_len_wave(const RecState &s, bool newline) {
     const HeaderItem it = header_item(s, newline, threadIdx.x & 63u);

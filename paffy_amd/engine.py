@@ -13,6 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 _LIB = os.environ.get("PAFFY_HIP_LIB", os.path.join(HERE, "libpaffy_hip.so"))  # override for A/B experiments only
 
 INVERT, TRIM_IDENTITY, TRIM_FIXED, SHATTER, ADD_MISMATCHES, REMOVE_MISMATCHES, PASS, FILTER, TRIM_ENDS, STATS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+DECHUNK, UPCONVERT = 12, 13  # PAFFY_DECHUNK (first stage only), PAFFY_UPCONVERT (a stage list of its own)
 
 
 class BedOpts(C.Structure):
@@ -65,6 +66,11 @@ def stage_trim_ends(end_bases):
     st = Stage(TRIM_ENDS, 0.0, 0.0)
     C.memmove(C.addressof(st) + Stage.p0.offset, struct.pack("<ff", p0, p1), 8)  # no float round trip: NaN payloads must survive
     return st
+
+
+def stage_dechunk(query=True, target=True):
+    """`paffy dechunk` as a stage (the first of a pipe): query=False is `-t`, target=False is `-q`."""
+    return Stage(DECHUNK, 1.0 if query else 0.0, 1.0 if target else 0.0)
 
 
 def library_path():
@@ -132,6 +138,7 @@ def lib():
         L.paffy_hip_dedupe_reset.argtypes = [vp]
         L.paffy_hip_set_sequences.argtypes = [vp, i64, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(i64)]
         L.paffy_hip_set_filter.argtypes = [vp, C.POINTER(Filter)]
+        L.paffy_hip_set_intervals.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(i64), i64]
         L.paffy_hip_error_exit_status.argtypes = [i32]
         L.paffy_hip_error_string.restype = C.c_char_p
         L.paffy_hip_error_string.argtypes = [i32]
@@ -414,6 +421,17 @@ class Engine:
         ln = (C.c_int64 * max(1, n))(*[len(v) for v in vals])
         self._check(lib().paffy_hip_set_sequences(self._ctx, n, a, b, ln), "paffy_hip_set_sequences")
 
+    def set_intervals(self, headers, seq_lens):
+        """Intervals for UPCONVERT: the FASTA headers ("name|length|start") of extracted subsequences and the lengths of their sequences,
+        as `paffy upconvert a.fa b.fa` loads them. A header that does not decode raises (the reference aborts)."""
+        hs = [h if isinstance(h, bytes) else h.encode() for h in headers]
+        n = len(hs)
+        if len(seq_lens) != n:
+            raise ValueError("one sequence length per header")
+        a = (C.c_char_p * max(1, n))(*hs)
+        ln = (C.c_int64 * max(1, n))(*[int(x) for x in seq_lens])
+        self._check(lib().paffy_hip_set_intervals(self._ctx, a, ln, n), "paffy_hip_set_intervals")
+
     def sync(self):
         self._check(lib().paffy_hip_sync(self._ctx), "paffy_hip_sync")
 
@@ -593,6 +611,19 @@ def pipe(stages, data):
 def invert(data):
     """paffy invert (impl/paf_invert.c)."""
     return pipe([stage(INVERT)], data)
+
+
+def dechunk(data, query=True, target=True):
+    """paffy dechunk [-q] [-t] (impl/paf_dechunk.c): query=False is -t, target=False is -q."""
+    return pipe([stage_dechunk(query, target)], data)
+
+
+def upconvert(data, fasta=None):
+    """paffy upconvert [fasta...] (impl/paf_upconvert.c); fasta: {header: bases} of the extracted subsequences, in file order."""
+    e = _engine()
+    fasta = fasta or {}
+    e.set_intervals(list(fasta), [len(v) for v in fasta.values()])
+    return e.run([stage(UPCONVERT)], data)[0]
 
 
 def shatter(data):
