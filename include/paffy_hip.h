@@ -106,7 +106,11 @@ enum {
     PAFFY_ERR_SEQ_RANGE = 21,          /* paf_encode_mismatches would read outside a sequence */
     PAFFY_ERR_CHAIN_ASSERT = 22,       /* impl/chaining.c:275,278-281 asserts              */
     PAFFY_ERR_DECHUNK_HEADER = 23,     /* impl/paf.c:722,725 asserts: a name without "|length|start" (stage 0) */
-    PAFFY_ERR_UPCONVERT_ASSERT = 24    /* impl/paf_upconvert.c:33 assert: a side starts inside an interval and ends beyond it */
+    PAFFY_ERR_UPCONVERT_ASSERT = 24,   /* impl/paf_upconvert.c:33 assert: a side starts inside an interval and ends beyond it */
+    PAFFY_ERR_FAFFY_ASSERT = 25,       /* faffy asserts: chunk size <= overlap (impl/fasta_chunk.c:74), extract bounds (impl/fasta_extract.c:211)
+                                          or a BED line of fewer than 3 tokens, merge order / gap / header (impl/fasta_merge.c) */
+    PAFFY_ERR_FAFFY_BASE = 26,         /* chunk / extract: a base whose tolower() is not a, c, g, t or n (assert) */
+    PAFFY_ERR_FAFFY_MISSING_SEQ = 27   /* extract: a BED name without a sequence, "Missing sequence: %s" (st_errAbort, exit 1) */
 };
 
 /* Call-level failures (negative return values). */
@@ -378,6 +382,38 @@ int paffy_hip_set_sequences(paffy_hip_ctx *ctx, int64_t n, const char *const *na
  * decode: PAFFY_E_HEADER and no intervals (the reference aborts before it writes anything). n = 0: no side is ever renamed.
  */
 int paffy_hip_set_intervals(paffy_hip_ctx *ctx, const char *const *headers, const int64_t *seq_lens, int64_t n);
+
+/*
+ * `faffy chunk | extract | merge` (impl/fasta_{chunk,extract,merge}.c). The text of one or more FASTA files lies back to back in device
+ * memory (16-byte aligned, readable up to the next multiple of 16 past text_len; it must stay there until the last emit), file_starts[k]
+ * is the first byte of file k (file_starts[0] = 0, non-decreasing). paffy_hip_fasta_index reads it as host/paffy_cmds.c:fasta_read
+ * does, per file, into a compact buffer of all bases and a record table (64-bit offsets: a genome passes 4 GiB).
+ */
+typedef struct {
+    int64_t hdr_off, hdr_len; /* the header in the text (after '>', without the line end) */
+    int64_t seq_off, seq_len; /* the bases in the compact buffer */
+} paffy_fasta_record;
+int paffy_hip_fasta_index(paffy_hip_ctx *ctx, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records,
+                          int64_t *n_bases);
+/* records [first, first + cap) to recs (host); returns the number of records */
+int64_t paffy_hip_fasta_records(paffy_hip_ctx *ctx, int64_t first, int64_t cap, paffy_fasta_record *recs);
+/* bases [first, first + n) of the compact buffer to device memory */
+int paffy_hip_fasta_copy_bases(paffy_hip_ctx *ctx, int64_t first, int64_t n, void *d_dst);
+/*
+ * Plans over the index: info->out_bytes, info->n_rows (items), info->error (PAFFY_ERR_FAFFY_*: nothing is to be written; record = the
+ * record (chunk, merge), the BED line (extract: missing name, short line) or the sorted interval (extract bounds)).
+ * chunk: PAFFY_E_ARG where chunk_size > overlap but chunk_size <= 0 or chunk_size + overlap < 0 (the reference loops forever / takes
+ * negative lengths); the output files are byte ranges of the output, paffy_hip_faffy_chunk_files gives their ends.
+ * extract: bed is host text; duplicate FASTA names: the last record wins.
+ */
+int paffy_hip_faffy_chunk_plan(paffy_hip_ctx *ctx, int64_t chunk_size, int64_t overlap, paffy_plan_info *info);
+int64_t paffy_hip_faffy_chunk_files(paffy_hip_ctx *ctx, int64_t cap, int64_t *file_end);
+int paffy_hip_faffy_extract_plan(paffy_hip_ctx *ctx, const char *bed, int64_t bed_len, int64_t flank, int64_t min_size, int skip_missing,
+                                 paffy_plan_info *info);
+int paffy_hip_faffy_merge_plan(paffy_hip_ctx *ctx, paffy_plan_info *info);
+/* the planned bytes to d_out (16-byte aligned, out_cap >= out_bytes rounded up to 16); err->code = PAFFY_ERR_FAFFY_BASE, err->record =
+   the first item with a bad base (chunk, extract): the output is then not to be written */
+int paffy_hip_faffy_emit(paffy_hip_ctx *ctx, void *d_out, int64_t out_cap, paffy_error *err);
 
 /*
  * Thresholds of `paffy filter` as its main() holds them (impl/paf_filter.c:27-32; -s -t -w pass through atoi, -u -v

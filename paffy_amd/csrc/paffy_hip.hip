@@ -31,6 +31,7 @@
 #include "flat_add_kernel.h"
 #include "coverage_kernel.h"
 #include "bed_kernel.h"
+#include "fasta_kernel.h"
 
 #define SEP_TILE 65536u /* bytes per workgroup in the separator passes */
 #define WAVE_OPS_CAP 2048u   /* op store of the one-wave sizing kernel: 8 KiB, sixteen workgroups per CU */
@@ -1079,6 +1080,7 @@ struct paffy_hip_ctx {
     uint32_t tile_n = 0;
     const uint8_t *tile_in = nullptr;
     struct ChainState *chain = nullptr; /* `paffy chain` (chain_host.h) */
+    struct FastaState *fasta = nullptr; /* `faffy chunk | extract | merge`: FASTA index and item plan (fasta_host.h) */
     struct CovState *cov = nullptr; /* `paffy tile` / `paffy to_bed` over any number of batches (coverage_host.h) */
     /* the batch paffy_hip_query_names indexed last: paffy_hip_split_by_owner on the same batch reuses the index (one use) */
     const void *indexed_in = nullptr;
@@ -1263,6 +1265,7 @@ static void dedupe_free(paffy_hip_ctx *c); /* dedupe_host.h state */
 static void index_drop(paffy_hip_ctx *c, const void *d_in);
 static void index_drop_all(paffy_hip_ctx *c);
 static void chain_free(paffy_hip_ctx *c);
+static void fasta_free(paffy_hip_ctx *c);
 
 void paffy_hip_destroy(paffy_hip_ctx *c) {
     if (!c) return;
@@ -1273,6 +1276,7 @@ void paffy_hip_destroy(paffy_hip_ctx *c) {
     c->event_pool.clear();
     cov_free(c);
     chain_free(c);
+    fasta_free(c);
     while (!c->kept_index.empty()) index_drop(c, c->kept_index.back().in);
     for (paffy_hip_ctx::KeptIndex &k : c->index_pool) {
         if (k.meta.p) (void)hipFree(k.meta.p);
@@ -1865,6 +1869,7 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
 #include "dedupe_host.h"
 #include "chain_host.h"
 #include "pretty_kernel.h"
+#include "fasta_host.h"
 
 static CovState &cov_state(paffy_hip_ctx *c) {
     if (!c->cov) c->cov = new CovState();
@@ -3404,7 +3409,7 @@ int paffy_hip_error_exit_status(int32_t code) {
         case PAFFY_ERR_STRAND: case PAFFY_ERR_CIGAR_CHAR:
         case PAFFY_ERR_CHECK_QSTART: case PAFFY_ERR_CHECK_QEND: case PAFFY_ERR_CHECK_TSTART: case PAFFY_ERR_CHECK_TEND:
         case PAFFY_ERR_CHECK_CIGAR_Q: case PAFFY_ERR_CHECK_CIGAR_T:
-        case PAFFY_ERR_MISSING_QUERY_SEQ: case PAFFY_ERR_MISSING_TARGET_SEQ:
+        case PAFFY_ERR_MISSING_QUERY_SEQ: case PAFFY_ERR_MISSING_TARGET_SEQ: case PAFFY_ERR_FAFFY_MISSING_SEQ:
             return 1; /* st_errAbort / exit(1) */
         case PAFFY_ERR_FEW_FIELDS: case PAFFY_ERR_NULL_CIGAR: case PAFFY_ERR_SEQ_RANGE:
             return 139; /* the reference dereferences NULL / reads out of bounds */
@@ -3439,6 +3444,9 @@ const char *paffy_hip_error_string(int32_t code) {
         case PAFFY_ERR_CHAIN_ASSERT: return "chain: trim fraction outside [0, 1] or a negative alignment length";
         case PAFFY_ERR_DECHUNK_HEADER: return "dechunk: a name does not end in |length|start";
         case PAFFY_ERR_UPCONVERT_ASSERT: return "upconvert: an alignment starts inside an interval and ends beyond it";
+        case PAFFY_ERR_FAFFY_ASSERT: return "faffy: assertion failed (chunk size, interval bounds, or merge order)";
+        case PAFFY_ERR_FAFFY_BASE: return "faffy: a base other than a, c, g, t or n";
+        case PAFFY_ERR_FAFFY_MISSING_SEQ: return "Missing sequence";
         default: return "unknown error";
     }
 }

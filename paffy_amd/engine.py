@@ -40,6 +40,11 @@ class PlanInfo(C.Structure):
                 ("error", _Error)]
 
 
+class FastaRecord(C.Structure):
+    """paffy_fasta_record: the header in the text (after '>'), the bases in the compact buffer."""
+    _fields_ = [("hdr_off", C.c_int64), ("hdr_len", C.c_int64), ("seq_off", C.c_int64), ("seq_len", C.c_int64)]
+
+
 class ChainOpts(C.Structure):
     _fields_ = [("gap_open", C.c_int64), ("gap_extend", C.c_int64), ("max_gap_length", C.c_int64), ("trim_fraction", C.c_float)]
 
@@ -157,6 +162,16 @@ def lib():
         L.paffy_hip_synth4_setup.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, i64, i64, C.c_int]
         L.paffy_hip_synth4.argtypes = [vp, C.c_uint64, C.c_uint64, vp, i64, C.POINTER(i64)]
         L.paffy_hip_device_count.restype = C.c_int
+        L.paffy_hip_fasta_index.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64)]
+        L.paffy_hip_fasta_records.restype = i64
+        L.paffy_hip_fasta_records.argtypes = [vp, i64, i64, C.POINTER(FastaRecord)]
+        L.paffy_hip_fasta_copy_bases.argtypes = [vp, i64, i64, vp]
+        L.paffy_hip_faffy_chunk_plan.argtypes = [vp, i64, i64, C.POINTER(PlanInfo)]
+        L.paffy_hip_faffy_chunk_files.restype = i64
+        L.paffy_hip_faffy_chunk_files.argtypes = [vp, i64, C.POINTER(i64)]
+        L.paffy_hip_faffy_extract_plan.argtypes = [vp, C.c_char_p, i64, i64, i64, C.c_int, C.POINTER(PlanInfo)]
+        L.paffy_hip_faffy_merge_plan.argtypes = [vp, C.POINTER(PlanInfo)]
+        L.paffy_hip_faffy_emit.argtypes = [vp, vp, i64, C.POINTER(_Error)]
         _lib = L
     return _lib
 
@@ -578,6 +593,112 @@ class Engine:
             L.paffy_hip_stream_close(st)
             self.stream_seconds["close"] = time.perf_counter() - t_close
         return records, out_bytes
+
+    # ---- faffy chunk / extract / merge (FASTA index + item emit) ----
+    def fasta_index(self, d_text, text_len, file_starts=(0,)):
+        """Index FASTA text on the device (files back to back from file_starts); returns (records, bases). d_text must stay alive
+        until the last faffy_emit."""
+        n = len(file_starts)
+        st = (C.c_int64 * max(1, n))(*[int(x) for x in file_starts])
+        n_rec, n_bases = C.c_int64(), C.c_int64()
+        self._fasta_text = d_text
+        self._check(lib().paffy_hip_fasta_index(self._ctx, C.c_void_p(d_text.data_ptr()), text_len, st, n, C.byref(n_rec), C.byref(n_bases)),
+                    "paffy_hip_fasta_index")
+        return n_rec.value, n_bases.value
+
+    def fasta_table(self):
+        """The record table: a list of (hdr_off, hdr_len, seq_off, seq_len)."""
+        n = lib().paffy_hip_fasta_records(self._ctx, 0, 0, None)
+        if n < 0:
+            self._check(n, "paffy_hip_fasta_records")
+        arr = (FastaRecord * max(1, n))()
+        lib().paffy_hip_fasta_records(self._ctx, 0, n, arr)
+        return [(r.hdr_off, r.hdr_len, r.seq_off, r.seq_len) for r in arr[:n]]
+
+    def fasta_bases(self, first, n, d_dst):
+        """Copy bases [first, first + n) of the compact buffer into the device tensor d_dst."""
+        self._check(lib().paffy_hip_fasta_copy_bases(self._ctx, first, n, C.c_void_p(d_dst.data_ptr())), "paffy_hip_fasta_copy_bases")
+
+    def _files(self, files):
+        files = [f if isinstance(f, bytes) else f.encode() for f in files]
+        starts, at = [], 0
+        for f in files:
+            starts.append(at)
+            at += len(f)
+        data = b"".join(files)
+        d_text = self.to_device(data)
+        self.fasta_index(d_text, len(data), starts or [0])
+        return d_text
+
+    def fasta_records(self, files):
+        """FASTA files (bytes each) -> [(header, bases)] as the device index reads them."""
+        d_text = self._files(files)
+        data = b"".join(f if isinstance(f, bytes) else f.encode() for f in files)
+        table = self.fasta_table()
+        total = table[-1][2] + table[-1][3] if table else 0
+        buf = self.torch.zeros(max(1, total), dtype=self.torch.uint8, device=self.device)
+        if total:
+            self.fasta_bases(0, total, buf)
+        bases = bytes(buf[:total].cpu().numpy().tobytes())
+        del d_text
+        return [(data[h:h + hl], bases[s:s + sl]) for h, hl, s, sl in table]
+
+    def _faffy_fail(self, code, record):
+        L = lib()
+        info = PlanInfo()
+        info.error.code, info.error.record = code, record
+        raise PafError(f"record {record}: {L.paffy_hip_error_string(code).decode()}", info, L.paffy_hip_error_exit_status(code))
+
+    def _faffy_emit(self, info):
+        if info.error.code:
+            self._faffy_fail(info.error.code, info.error.record)
+        if not info.out_bytes:
+            return b""
+        d_out = self.alloc_out(info.out_bytes)
+        err = _Error()
+        self._check(lib().paffy_hip_faffy_emit(self._ctx, C.c_void_p(d_out.data_ptr()), d_out.numel(), C.byref(err)), "paffy_hip_faffy_emit")
+        if err.code:
+            self._faffy_fail(err.code, err.record)
+        return bytes(d_out[: info.out_bytes].cpu().numpy().tobytes())
+
+    def faffy_chunk(self, files, chunk_size=10000000, overlap=100000, d="./temp_fastas"):
+        """`faffy chunk -c -o -d` over FASTA files (bytes each): [(file name, bytes)], names as the CLI prints them."""
+        d_text = self._files(files)
+        info = PlanInfo()
+        rc = lib().paffy_hip_faffy_chunk_plan(self._ctx, chunk_size, overlap, C.byref(info))
+        if rc == -2:
+            raise ValueError(f"chunk size {chunk_size} with overlap {overlap} gives no chunks")
+        self._check(rc, "paffy_hip_faffy_chunk_plan")
+        out = self._faffy_emit(info)
+        n = lib().paffy_hip_faffy_chunk_files(self._ctx, 0, None)
+        ends = (C.c_int64 * max(1, n))()
+        lib().paffy_hip_faffy_chunk_files(self._ctx, n, ends)
+        res, at = [], 0
+        for k in range(n):
+            res.append((f"{d}/{k}.fa", out[at:ends[k]]))
+            at = ends[k]
+        del d_text
+        return res
+
+    def faffy_extract(self, files, bed, flank=10, min_size=100, skip_missing=False):
+        """`faffy extract -f -m [-n]` of BED text over FASTA files: bytes."""
+        d_text = self._files(files)
+        bed = bed if isinstance(bed, bytes) else bed.encode()
+        info = PlanInfo()
+        self._check(lib().paffy_hip_faffy_extract_plan(self._ctx, bed, len(bed), flank, min_size, 1 if skip_missing else 0, C.byref(info)),
+                    "paffy_hip_faffy_extract_plan")
+        out = self._faffy_emit(info)
+        del d_text
+        return out
+
+    def faffy_merge(self, files):
+        """`faffy merge` of chunk files (bytes each, in list order): bytes."""
+        d_text = self._files(files)
+        info = PlanInfo()
+        self._check(lib().paffy_hip_faffy_merge_plan(self._ctx, C.byref(info)), "paffy_hip_faffy_merge_plan")
+        out = self._faffy_emit(info)
+        del d_text
+        return out
 
     # ---- per-kernel HIP-event timing ----
     def profile(self, on=True, only=None):
