@@ -18,6 +18,7 @@
 
 #include "../include/paffy_hip.h"
 #include "faffy_host.h"
+#include "fasta_files.h"
 
 typedef struct {
     char *data;
@@ -44,14 +45,6 @@ static void buf_read(buf_t *b, FILE *fh) {
     }
 }
 
-static int buf_read_path(buf_t *b, const char *path) {
-    FILE *fh = fopen(path, "rb");
-    if (!fh) return -1;
-    buf_read(b, fh);
-    fclose(fh);
-    return 0;
-}
-
 static void fail_hip(const char *cmd, paffy_hip_ctx *ctx, int rc) {
     fprintf(stderr, "faffy %s: device call failed (%d): %s\n", cmd, rc, ctx ? paffy_hip_last_error(ctx) : "");
     exit(1);
@@ -75,15 +68,13 @@ typedef struct {
     int64_t out_bytes;
 } faffy_run;
 
-/* FASTA files -> device text -> index. files: host text of every file back to back, starts: first byte of each */
-static void run_index(const char *cmd, faffy_run *r, const buf_t *text, const int64_t *starts, int32_t n_files) {
+/* FASTA files -> device text -> index */
+static void run_index(const char *cmd, faffy_run *r, const fasta_text *text) {
     int rc = paffy_hip_create(&r->ctx, -1);
     if (rc) fail_hip(cmd, NULL, rc);
-    const int64_t cap = (text->len + 15) / 16 * 16 + 16;
-    if ((rc = paffy_hip_malloc(&r->d_text, cap)) != 0) fail_hip(cmd, r->ctx, rc);
-    if (text->len && (rc = paffy_hip_memcpy_h2d(r->d_text, text->data, text->len)) != 0) fail_hip(cmd, r->ctx, rc);
+    if ((rc = fasta_text_to_device(text, &r->d_text)) != 0) fail_hip(cmd, r->ctx, rc);
     int64_t n_rec = 0, n_bases = 0;
-    if ((rc = paffy_hip_fasta_index(r->ctx, r->d_text, text->len, starts, n_files, &n_rec, &n_bases)) != 0) fail_hip(cmd, r->ctx, rc);
+    if ((rc = paffy_hip_fasta_index(r->ctx, r->d_text, text->len, text->starts, text->n_files, &n_rec, &n_bases)) != 0) fail_hip(cmd, r->ctx, rc);
 }
 
 /* emit the planned items and bring them back; a bad base ends the process before anything is written */
@@ -113,11 +104,9 @@ static void run_close(faffy_run *r) {
 }
 
 /* positional FASTA files, back to back */
-static int read_fastas(const char *cmd, char **paths, int n, buf_t *text, int64_t **starts) {
-    *starts = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1));
+static int read_fastas(const char *cmd, char **paths, int n, fasta_text *text) {
     for (int i = 0; i < n; i++) {
-        (*starts)[i] = text->len;
-        if (buf_read_path(text, paths[i]) != 0) {
+        if (fasta_text_add(text, paths[i]) != 0) {
             fprintf(stderr, "faffy %s: cannot open %s\n", cmd, paths[i]);
             return -1;
         }
@@ -186,11 +175,10 @@ int faffy_chunk_main(int argc, char *argv[]) {
         fprintf(stderr, "faffy chunk: cannot create %s: %s\n", dir, strerror(errno));
         return 1;
     }
-    buf_t text = {0};
-    int64_t *starts = NULL;
-    if (read_fastas("chunk", argv + optind, argc - optind, &text, &starts) != 0) return 1;
+    fasta_text text = {0};
+    if (read_fastas("chunk", argv + optind, argc - optind, &text) != 0) return 1;
     faffy_run r = {0};
-    run_index("chunk", &r, &text, starts, argc - optind);
+    run_index("chunk", &r, &text);
     paffy_plan_info info;
     int rc = paffy_hip_faffy_chunk_plan(r.ctx, chunk, overlap, &info);
     if (rc) fail_hip("chunk", r.ctx, rc);
@@ -213,8 +201,7 @@ int faffy_chunk_main(int argc, char *argv[]) {
         at = ends[k];
     }
     free(ends);
-    free(starts);
-    free(text.data);
+    fasta_text_free(&text);
     run_close(&r);
     return 0;
 }
@@ -255,9 +242,8 @@ int faffy_extract_main(int argc, char *argv[]) {
             default: extract_usage(); return 1;
         }
     }
-    buf_t text = {0};
-    int64_t *starts = NULL;
-    if (read_fastas("extract", argv + optind, argc - optind, &text, &starts) != 0) return 1;
+    fasta_text text = {0};
+    if (read_fastas("extract", argv + optind, argc - optind, &text) != 0) return 1;
     /* the output is opened before the BED file is read (an error leaves it empty) */
     FILE *out = out_path ? fopen(out_path, "w") : stdout;
     if (!out) {
@@ -273,7 +259,7 @@ int faffy_extract_main(int argc, char *argv[]) {
     buf_read(&bed, in);
     if (bed_path) fclose(in);
     faffy_run r = {0};
-    run_index("extract", &r, &text, starts, argc - optind);
+    run_index("extract", &r, &text);
     paffy_plan_info info;
     int rc = paffy_hip_faffy_extract_plan(r.ctx, bed.data, bed.len, flank, min_size, skip, &info);
     if (rc) fail_hip("extract", r.ctx, rc);
@@ -297,8 +283,7 @@ int faffy_extract_main(int argc, char *argv[]) {
     }
     if (!out_path) fflush(stdout);
     free(bed.data);
-    free(starts);
-    free(text.data);
+    fasta_text_free(&text);
     run_close(&r);
     return 0;
 }
@@ -344,19 +329,15 @@ int faffy_merge_main(int argc, char *argv[]) {
     buf_reserve(&list, 1);
     list.data[list.len] = '\0';
     /* every white-space separated token of the list is a chunk file, in order */
-    buf_t text = {0};
-    int64_t n_files = 0, cap_files = 16;
-    int64_t *starts = (int64_t *)malloc(sizeof(int64_t) * (size_t)cap_files);
+    fasta_text text = {0};
     for (char *save = NULL, *tok = strtok_r(list.data, " \t\n\r\v\f", &save); tok; tok = strtok_r(NULL, " \t\n\r\v\f", &save)) {
-        if (n_files == cap_files) starts = (int64_t *)realloc(starts, sizeof(int64_t) * (size_t)(cap_files *= 2));
-        starts[n_files++] = text.len;
-        if (buf_read_path(&text, tok) != 0) {
+        if (fasta_text_add(&text, tok) != 0) {
             fprintf(stderr, "faffy merge: cannot open %s\n", tok);
             return 1;
         }
     }
     faffy_run r = {0};
-    run_index("merge", &r, &text, starts, (int32_t)n_files);
+    run_index("merge", &r, &text);
     paffy_plan_info info;
     int rc = paffy_hip_faffy_merge_plan(r.ctx, &info);
     if (rc) fail_hip("merge", r.ctx, rc);
@@ -368,8 +349,7 @@ int faffy_merge_main(int argc, char *argv[]) {
     }
     if (!out_path) fflush(stdout);
     free(list.data);
-    free(starts);
-    free(text.data);
+    fasta_text_free(&text);
     run_close(&r);
     return 0;
 }

@@ -241,54 +241,16 @@ int paffy_split_file_main(int argc, char *argv[]) {
     return rc;
 }
 
-/* FASTA -> (header, sequence) pairs. Key = the whole header line after '>', sequence = all
- * non-whitespace characters up to the next header (the fastaReadToFunction /
- * fastaRead_readToMapFunction behaviour assumed in SURVEY Appendix C; parity unpinned). */
-typedef struct {
-    char **names, **seqs;
-    int64_t *lens;
-    int64_t n, cap;
-} fasta_set;
-
-static void fasta_push(fasta_set *f, char *name, char *seq, int64_t len) {
-    if (f->n == f->cap) {
-        f->cap = f->cap ? f->cap * 2 : 64;
-        f->names = (char **)realloc(f->names, sizeof(char *) * (size_t)f->cap);
-        f->seqs = (char **)realloc(f->seqs, sizeof(char *) * (size_t)f->cap);
-        f->lens = (int64_t *)realloc(f->lens, sizeof(int64_t) * (size_t)f->cap);
-    }
-    f->names[f->n] = name;
-    f->seqs[f->n] = seq;
-    f->lens[f->n] = len;
-    f->n++;
-}
-
-static int fasta_read(const char *path, fasta_set *f) {
-    FILE *fh = fopen(path, "r");
-    if (!fh) return -1;
-    char *line = NULL, *name = NULL, *seq = NULL;
-    size_t lcap = 0;
-    int64_t slen = 0, scap = 0;
-    ssize_t got;
-    while ((got = getline(&line, &lcap, fh)) >= 0) {
-        while (got > 0 && (line[got - 1] == '\n' || line[got - 1] == '\r')) line[--got] = '\0';
-        if (line[0] == '>') {
-            if (name) fasta_push(f, name, seq, slen);
-            name = strdup(line + 1);
-            seq = NULL;
-            slen = scap = 0;
-        } else if (name) {
-            if (slen + got + 1 > scap) {
-                scap = (slen + got + 1) * 2;
-                seq = (char *)realloc(seq, (size_t)scap);
-            }
-            for (ssize_t i = 0; i < got; i++)
-                if (line[i] != ' ' && line[i] != '\t') seq[slen++] = line[i];
+/* The positional FASTA files as raw text for the device index (fasta_files.c), each announced at -l INFO as the reference does; 1 after
+   "paffy <cmd>: cannot open <file>" when one cannot be opened (before the GPU is touched). */
+static int read_fasta_args(const char *cmd, char **paths, int n, fasta_text *t) {
+    for (int i = 0; i < n; i++) {
+        host_log_info("Parsing sequence file : %s\n", paths[i]);
+        if (fasta_text_add(t, paths[i]) != 0) {
+            fprintf(stderr, "paffy %s: cannot open %s\n", cmd, paths[i]);
+            return 1;
         }
     }
-    if (name) fasta_push(f, name, seq ? seq : strdup(""), slen);
-    free(line);
-    fclose(fh);
     return 0;
 }
 
@@ -322,18 +284,13 @@ int paffy_add_mismatches_main(int argc, char *argv[]) {
     }
     host_set_log_level(o.log_level);
     paffy_stage st = {remove ? PAFFY_REMOVE_MISMATCHES : PAFFY_ADD_MISMATCHES, 0.05f, 1.0f};
+    fasta_text f;
+    memset(&f, 0, sizeof(f));
     if (!remove) {
-        fasta_set f;
-        memset(&f, 0, sizeof(f));
-        for (int i = optind; i < argc; i++) {
-            host_log_info("Parsing sequence file : %s\n", argv[i]);
-            if (fasta_read(argv[i], &f) != 0) {
-                fprintf(stderr, "paffy add_mismatches: cannot open %s\n", argv[i]);
-                return 1;
-            }
-        }
-        host_log_info("Read %i sequences from sequence files\n", (int)f.n);
-        host_set_sequences((const char *const *)f.names, (const char *const *)f.seqs, f.lens, f.n);
+        if (read_fasta_args("add_mismatches", argv + optind, argc - optind, &f)) return 1;
+        host_set_sequences(&f, 1);
+        if (host_load_fasta()) return 1;
+        fasta_text_free(&f); /* the sequences are on the device now */
     }
     return run_stream_cmd(&o, &st, 1, "add_mismatches");
 }
@@ -395,17 +352,12 @@ int paffy_upconvert_main(int argc, char *argv[]) {
         }
     }
     host_set_log_level(o.log_level);
-    fasta_set f;
+    fasta_text f;
     memset(&f, 0, sizeof(f));
-    for (int i = optind; i < argc; i++) {
-        host_log_info("Parsing sequence file : %s\n", argv[i]);
-        if (fasta_read(argv[i], &f) != 0) {
-            fprintf(stderr, "paffy upconvert: cannot open %s\n", argv[i]);
-            return 1;
-        }
-    }
-    host_log_info("Read %i sequences from sequence files\n", (int)f.n);
-    host_set_intervals((const char *const *)f.names, f.lens, f.n);
+    if (read_fasta_args("upconvert", argv + optind, argc - optind, &f)) return 1;
+    host_set_intervals(&f);
+    if (host_load_fasta()) return 1;
+    fasta_text_free(&f);
     paffy_stage st = {PAFFY_UPCONVERT, 0.0f, 0.0f};
     return run_stream_cmd(&o, &st, 1, "upconvert");
 }
@@ -522,17 +474,13 @@ int paffy_view_main(int argc, char *argv[]) {
         exit(1);
     }
     host_set_log_level(o.log_level);
-    fasta_set f;
+    fasta_text f;
     memset(&f, 0, sizeof(f));
-    for (int i = optind; i < argc; i++) {
-        host_log_info("Parsing sequence file : %s\n", argv[i]);
-        if (fasta_read(argv[i], &f) != 0) {
-            fprintf(stderr, "paffy view: cannot open %s\n", argv[i]);
-            return 1;
-        }
-    }
+    if (read_fasta_args("view", argv + optind, argc - optind, &f)) return 1;
     host_keep_raw_sequences(include_alignment); /* the rows show the bases in the case of the files */
-    host_set_sequences((const char *const *)f.names, (const char *const *)f.seqs, f.lens, f.n);
+    host_set_sequences(&f, 0);
+    if (host_load_fasta()) return 1;
+    fasta_text_free(&f);
     host_set_alignment_rows(include_alignment && per_alignment); /* impl/paf_view.c:158-160: paf_pretty_print runs unless -t */
     const paffy_stage st[2] = {{PAFFY_ADD_MISMATCHES, 0.05f, 1.0f}, {PAFFY_STATS, 0.0f, 0.0f}};
     host_set_stats(1);
@@ -629,30 +577,23 @@ int paffy_to_bed_main(int argc, char *argv[]) {
         if (have == 0) fgetc(mem);
         rc = host_to_bed(mem, out, &b);
         fclose(mem);
-        fasta_set f;
+        fasta_text f;
         memset(&f, 0, sizeof(f));
-        if (rc == 0 && fasta_read(query_fasta, &f) == 0) {
-            for (int64_t k = 0; k < f.n; k++) {
-                const size_t nl = strlen(f.names[k]);
-                int seen = 0;
-                for (const char *p = buf, *end = buf + have; p < end && !seen;) { /* a sequence is known if a line names it as query (or, with -n, as target) */
-                    const char *le = memchr(p, '\n', (size_t)(end - p));
-                    if (!le) le = end;
-                    const char *t1 = memchr(p, '\t', (size_t)(le - p));
-                    if (t1 && (size_t)(t1 - p) == nl && memcmp(p, f.names[k], nl) == 0) seen = 1;
-                    if (!seen && b.include_inverted && t1) {
-                        const char *q = t1;
-                        for (int col = 1; col < 5 && q; col++) q = memchr(q + 1, '\t', (size_t)(le - q - 1));
-                        if (q) {
-                            const char *t6 = memchr(q + 1, '\t', (size_t)(le - q - 1));
-                            if (t6 && (size_t)(t6 - q - 1) == nl && memcmp(q + 1, f.names[k], nl) == 0) seen = 1;
-                        }
-                    }
-                    p = le + 1;
+        if (rc == 0 && fasta_text_add(&f, query_fasta) == 0) { /* a file that cannot be opened adds nothing */
+            /* a sequence is known if a line names it as query (or, with -n, as target): one lookup per line on the device */
+            paffy_fasta_record *recs = NULL;
+            uint8_t *seen = NULL;
+            int64_t n = 0;
+            rc = host_fasta_seen(&f, buf, (int64_t)have, b.include_inverted, &recs, &seen, &n);
+            for (int64_t k = 0; k < n && rc == 0; k++)
+                if (!seen[k]) { /* the name is the header up to a NUL byte */
+                    const char *h = f.data + recs[k].hdr_off;
+                    fprintf(out, "%.*s 0 %" PRIi64 "\t0\n", (int)strnlen(h, (size_t)recs[k].hdr_len), h, recs[k].seq_len);
                 }
-                if (!seen) fprintf(out, "%s 0 %" PRIi64 "\t0\n", f.names[k], f.lens[k]);
-            }
+            free(recs);
+            free(seen);
         }
+        fasta_text_free(&f);
         free(buf);
     } else {
         rc = host_to_bed(in, out, &b);

@@ -12,6 +12,7 @@
 #include <stdio.h>
 
 #include "../include/paffy_hip.h"
+#include "fasta_files.h"
 
 int paffy_shatter_main(int argc, char *argv[]);
 int paffy_invert_main(int argc, char *argv[]);
@@ -64,11 +65,18 @@ int host_chain(FILE *in, FILE *out, const paffy_chain_opts *opts);
 /* paffy split_file: normalised lines (cigar text verbatim) routed to "<prefix><contig>.paf" / "<prefix>small_<k>.paf" */
 int host_split_file(FILE *in, const char *prefix, int by_query, int64_t min_length);
 
-/* Sequences handed to the context that host_stream creates (add_mismatches); pointers must stay valid. */
-void host_set_sequences(const char *const *names, const char *const *seqs, const int64_t *lens, int64_t n);
-/* Intervals handed to the context that host_stream creates (upconvert: FASTA headers, sequence lengths); pointers must stay valid.
-   A header that does not decode ends the process with abort(), as the reference's assert does. */
-void host_set_intervals(const char *const *headers, const int64_t *seq_lens, int64_t n);
+/* FASTA files whose sequences host_load_fasta loads (add_mismatches, view: paffy_hip_set_sequences_fasta); t must stay valid until then.
+   log_count: log "Read %i sequences from sequence files" once they are loaded. */
+void host_set_sequences(const fasta_text *t, int log_count);
+/* FASTA files whose intervals host_load_fasta loads (upconvert: paffy_hip_set_intervals_fasta; logs the count); t must stay valid until
+   then. A header that does not decode ends the process with abort() in the next host_stream, as the reference's assert does. */
+void host_set_intervals(const fasta_text *t);
+/* creates the context of the next host_stream and loads the FASTA files set above into it (after host_keep_raw_sequences); 0, or 1 after
+   a message */
+int host_load_fasta(void);
+/* to_bed -q: the records of the FASTA files (header offsets into t->data, sequence lengths) and, per record, whether a line of the PAF
+   text names it (paffy_hip_fasta_seen); *recs and *seen are malloc'ed. 0, or 1 after a message. */
+int host_fasta_seen(const fasta_text *t, const char *paf, int64_t paf_len, int with_target, paffy_fasta_record **recs, uint8_t **seen, int64_t *n);
 /* paffy view -a: keep the bases as loaded beside the upper-cased store (before host_stream), and print the rows under each stats line */
 void host_keep_raw_sequences(int on);
 void host_set_alignment_rows(int on);

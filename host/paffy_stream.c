@@ -60,15 +60,12 @@ FILE *host_open_input(const char *path) {
 }
 
 static int g_log_level = 0;
-static const char *const *g_seq_names, *const *g_seq_data;
-static const int64_t *g_seq_lens;
-static int64_t g_seq_n = 0;
+static const fasta_text *g_seq_text = NULL;
+static int g_seq_log = 0;
 
-void host_set_sequences(const char *const *names, const char *const *seqs, const int64_t *lens, int64_t n) {
-    g_seq_names = names;
-    g_seq_data = seqs;
-    g_seq_lens = lens;
-    g_seq_n = n;
+void host_set_sequences(const fasta_text *t, int log_count) {
+    g_seq_text = t;
+    g_seq_log = log_count;
 }
 
 static int g_keep_raw = 0;
@@ -334,42 +331,98 @@ static int pipelined_stream(paffy_hip_ctx *ctx, const paffy_stage *stages, int n
     return rc;
 }
 
-/* paffy upconvert: the FASTA headers and sequence lengths of its intervals */
-static const char *const *g_iv_headers;
-static const int64_t *g_iv_lens;
-static int64_t g_iv_n = 0;
-static int g_iv_set = 0;
-void host_set_intervals(const char *const *headers, const int64_t *seq_lens, int64_t n) {
-    g_iv_headers = headers;
-    g_iv_lens = seq_lens;
-    g_iv_n = n;
-    g_iv_set = 1;
+/* paffy upconvert: the FASTA files of its intervals */
+static const fasta_text *g_iv_text = NULL;
+void host_set_intervals(const fasta_text *t) { g_iv_text = t; }
+
+/* the FASTA text to the device, one of the paffy_hip_set_*_fasta loaders, the text freed; the loader's code (or the copy's) */
+static int load_fasta(paffy_hip_ctx *ctx, const fasta_text *t, int intervals, int64_t *n_records) {
+    void *d_text = NULL;
+    int rc = fasta_text_to_device(t, &d_text);
+    if (rc) return rc;
+    rc = intervals ? paffy_hip_set_intervals_fasta(ctx, d_text, t->len, t->starts, t->n_files, n_records)
+                   : paffy_hip_set_sequences_fasta(ctx, d_text, t->len, t->starts, t->n_files, n_records);
+    paffy_hip_free(d_text);
+    return rc;
 }
 
-int host_stream(const paffy_stage *stages, int n_stages, FILE *in, FILE *out) {
+int host_fasta_seen(const fasta_text *t, const char *paf, int64_t paf_len, int with_target, paffy_fasta_record **recs, uint8_t **seen, int64_t *n) {
     paffy_hip_ctx *ctx = NULL;
+    *recs = NULL;
+    *seen = NULL;
+    *n = 0;
     if (paffy_hip_create(&ctx, host_device()) != 0) {
         fprintf(stderr, "paffy: no usable GPU (this build has no CPU path)\n");
         return 1;
     }
-    paffy_hip_set_filter(ctx, &g_filter);
-    if (g_keep_raw) paffy_hip_keep_raw_sequences(ctx, 1);
-    if (g_seq_n > 0 && paffy_hip_set_sequences(ctx, g_seq_n, g_seq_names, g_seq_data, g_seq_lens) != 0) {
-        fprintf(stderr, "paffy: could not load the sequences onto the GPU: %s\n", paffy_hip_last_error(ctx));
-        return 1;
-    }
-    if (g_iv_set) {
-        const int rc = paffy_hip_set_intervals(ctx, g_iv_headers, g_iv_lens, g_iv_n);
-        if (rc == PAFFY_E_HEADER) { /* the reference's assert in decode_fasta_header, before it reads a record */
-            fprintf(stderr, "%s\n", paffy_hip_last_error(ctx));
-            fflush(out);
-            abort();
+    void *d_text = NULL, *d_paf = NULL;
+    int rc = fasta_text_to_device(t, &d_text);
+    if (!rc) rc = paffy_hip_fasta_index_headers(ctx, d_text, t->len, t->starts, t->n_files, n);
+    if (d_text) paffy_hip_free(d_text); /* the index keeps the table and the headers on the host */
+    if (!rc && *n > 0) {
+        *recs = (paffy_fasta_record *)malloc(sizeof(paffy_fasta_record) * (size_t)*n);
+        *seen = (uint8_t *)malloc((size_t)*n);
+        if (!*recs || !*seen) {
+            fprintf(stderr, "paffy: out of memory\n");
+            exit(1);
         }
-        if (rc != 0) {
-            fprintf(stderr, "paffy: could not load the intervals onto the GPU: %s\n", paffy_hip_last_error(ctx));
+        paffy_hip_fasta_records(ctx, 0, *n, *recs);
+        rc = paffy_hip_malloc(&d_paf, (paf_len + 15) / 16 * 16 + 16);
+        if (!rc && paf_len) rc = paffy_hip_memcpy_h2d(d_paf, paf, paf_len);
+        if (!rc) rc = paffy_hip_fasta_seen(ctx, d_paf, paf_len, with_target, *seen);
+        if (d_paf) paffy_hip_free(d_paf);
+    }
+    if (rc) fprintf(stderr, "paffy: GPU call failed (%d): %s\n", rc, paffy_hip_last_error(ctx));
+    paffy_hip_destroy(ctx);
+    return rc ? 1 : 0;
+}
+
+/* the context host_load_fasta prepared for the next host_stream (NULL: host_stream creates its own) */
+static paffy_hip_ctx *g_ctx = NULL;
+static int g_bad_header = 0;
+
+static paffy_hip_ctx *open_ctx(void) {
+    paffy_hip_ctx *ctx = NULL;
+    if (paffy_hip_create(&ctx, host_device()) != 0) {
+        fprintf(stderr, "paffy: no usable GPU (this build has no CPU path)\n");
+        return NULL;
+    }
+    return ctx;
+}
+
+int host_load_fasta(void) {
+    if (!(g_ctx = open_ctx())) return 1;
+    if (g_keep_raw) paffy_hip_keep_raw_sequences(g_ctx, 1);
+    int64_t n_fasta = 0;
+    if (g_seq_text) {
+        if (load_fasta(g_ctx, g_seq_text, 0, &n_fasta) != 0) {
+            fprintf(stderr, "paffy: could not load the sequences onto the GPU: %s\n", paffy_hip_last_error(g_ctx));
+            return 1;
+        }
+        if (g_seq_log) host_log_info("Read %i sequences from sequence files\n", (int)n_fasta);
+    }
+    if (g_iv_text) {
+        const int rc = load_fasta(g_ctx, g_iv_text, 1, &n_fasta);
+        if (rc == 0 || rc == PAFFY_E_HEADER) host_log_info("Read %i sequences from sequence files\n", (int)n_fasta); /* read before the header check */
+        g_bad_header = rc == PAFFY_E_HEADER; /* host_stream ends the process where the reference's assert does */
+        if (rc != 0 && rc != PAFFY_E_HEADER) {
+            fprintf(stderr, "paffy: could not load the intervals onto the GPU: %s\n", paffy_hip_last_error(g_ctx));
             return 1;
         }
     }
+    return 0;
+}
+
+int host_stream(const paffy_stage *stages, int n_stages, FILE *in, FILE *out) {
+    paffy_hip_ctx *ctx = g_ctx;
+    g_ctx = NULL;
+    if (!ctx && !(ctx = open_ctx())) return 1;
+    if (g_bad_header) { /* the reference's assert in decode_fasta_header, before it reads a record */
+        fprintf(stderr, "%s\n", paffy_hip_last_error(ctx));
+        fflush(out);
+        abort();
+    }
+    paffy_hip_set_filter(ctx, &g_filter);
     if (!g_dedupe_mode && !g_stats_mode) {
         int rc = pipelined_stream(ctx, stages, n_stages, in, out);
         paffy_hip_destroy(ctx);

@@ -400,6 +400,23 @@ int64_t paffy_hip_fasta_records(paffy_hip_ctx *ctx, int64_t first, int64_t cap, 
 /* bases [first, first + n) of the compact buffer to device memory */
 int paffy_hip_fasta_copy_bases(paffy_hip_ctx *ctx, int64_t first, int64_t n, void *d_dst);
 /*
+ * FASTA files as the paffy commands load them, from text in device memory with the contract of paffy_hip_fasta_index. The
+ * text is indexed into a state of the call's own (an index of paffy_hip_fasta_index stays as it is) and may be freed when the call
+ * returns; n_records (may be NULL) gets the number of FASTA records.
+ * set_sequences_fasta: the store paffy_hip_set_sequences builds from the same records (names = the headers up to a NUL byte, in input
+ *   order), with the raw copy under paffy_hip_keep_raw_sequences; the bases never leave the device.
+ * set_intervals_fasta: paffy_hip_set_intervals over the records' headers and sequence lengths (PAFFY_E_HEADER as there).
+ */
+int paffy_hip_set_sequences_fasta(paffy_hip_ctx *ctx, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records);
+int paffy_hip_set_intervals_fasta(paffy_hip_ctx *ctx, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records);
+/* paffy_hip_fasta_index without the compact base buffer (record table and headers only; the faffy plans and copy_bases then refuse) */
+int paffy_hip_fasta_index_headers(paffy_hip_ctx *ctx, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files,
+                                  int64_t *n_records);
+/* to_bed -q: seen[r] (host, one byte per record of the context's index) = 1 when a line of the PAF text d_paf (16-byte aligned, readable
+   to the next multiple of 16) names record r's header (up to a NUL byte) as its query -- the bytes before its first tab -- or, with
+   with_target, as its target -- between its fifth and sixth tab --, else 0. One device lookup per line in the sorted distinct names. */
+int paffy_hip_fasta_seen(paffy_hip_ctx *ctx, const void *d_paf, int64_t paf_len, int with_target, uint8_t *seen);
+/*
  * Plans over the index: info->out_bytes, info->n_rows (items), info->error (PAFFY_ERR_FAFFY_*: nothing is to be written; record = the
  * record (chunk, merge), the BED line (extract: missing name, short line) or the sorted interval (extract bounds)).
  * chunk: PAFFY_E_ARG where chunk_size > overlap but chunk_size <= 0 or chunk_size + overlap < 0 (the reference loops forever / takes

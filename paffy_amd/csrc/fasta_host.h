@@ -10,9 +10,11 @@
 
 struct FastaState {
     DevBuf starts, tiles, totals, recs, bases, hdr_off, hdr_blob, items, bad;
+    DevBuf seen_names, seen_off, seen; /* paffy_hip_fasta_seen (seqload_host.h): the distinct names and a flag per name */
     const uint8_t *text = nullptr; /* the caller's text: emit reads the header names from it */
     int64_t text_len = 0, n_rec = 0, n_bases = 0;
     bool indexed = false, planned = false;
+    bool with_bases = false; /* false: paffy_hip_fasta_index_headers, no compact base buffer */
     std::vector<FaRec> h_recs;
     std::vector<char> h_hdr;       /* all headers back to back */
     std::vector<int64_t> h_hdr_at; /* record r's header is h_hdr[h_hdr_at[r] .. h_hdr_at[r + 1]) */
@@ -21,12 +23,18 @@ struct FastaState {
     int64_t out_bytes = 0;
 };
 
+static void fasta_release(FastaState &F) {
+    DevBuf *bufs[] = {&F.starts, &F.tiles, &F.totals, &F.recs, &F.bases, &F.hdr_off, &F.hdr_blob, &F.items, &F.bad, &F.seen_names, &F.seen_off, &F.seen};
+    for (DevBuf *b : bufs) {
+        if (b->p) (void)hipFree(b->p);
+        b->p = nullptr;
+        b->cap = 0;
+    }
+}
+
 static void fasta_free(paffy_hip_ctx *c) {
     if (!c->fasta) return;
-    FastaState &F = *c->fasta;
-    DevBuf *bufs[] = {&F.starts, &F.tiles, &F.totals, &F.recs, &F.bases, &F.hdr_off, &F.hdr_blob, &F.items, &F.bad};
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
+    fasta_release(*c->fasta);
     delete c->fasta;
     c->fasta = nullptr;
 }
@@ -64,7 +72,7 @@ static void fa_push(FastaState &F, int64_t r, int32_t kind, int32_t name_len, in
 }
 
 static int fa_plan_begin(paffy_hip_ctx *c, paffy_plan_info *info) {
-    if (!c || !info || !c->fasta || !c->fasta->indexed) return PAFFY_E_STATE;
+    if (!c || !info || !c->fasta || !c->fasta->indexed || !c->fasta->with_bases) return PAFFY_E_STATE;
     FastaState &F = *c->fasta;
     memset(info, 0, sizeof(*info));
     F.planned = false;
@@ -94,10 +102,9 @@ static int fa_plan_end(paffy_hip_ctx *c, paffy_plan_info *info) {
     return 0;
 }
 
-extern "C" {
-
-int paffy_hip_fasta_index(paffy_hip_ctx *c, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records,
-                          int64_t *n_bases) {
+/* The index of the text into F (the context's state, or one of a loader's own). with_bases = false: the record table and the headers
+   only; the compact base buffer is neither allocated nor written (upconvert and to_bed -q need the lengths alone). */
+static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, bool with_bases) {
     if (!c || text_len < 0 || (text_len > 0 && !d_text) || (reinterpret_cast<uintptr_t>(d_text) & 15u)) return PAFFY_E_ARG;
     if (n_files < 0 || (n_files > 0 && !file_starts)) return PAFFY_E_ARG;
     std::vector<int64_t> starts(file_starts, file_starts + n_files);
@@ -105,8 +112,8 @@ int paffy_hip_fasta_index(paffy_hip_ctx *c, const void *d_text, int64_t text_len
     if (starts[0] != 0) return PAFFY_E_ARG;
     for (size_t k = 1; k < starts.size(); k++)
         if (starts[k] < starts[k - 1] || starts[k] > text_len) return PAFFY_E_ARG;
-    FastaState &F = fasta_state(c);
     F.indexed = F.planned = false;
+    F.with_bases = with_bases;
     F.text = static_cast<const uint8_t *>(d_text);
     F.text_len = text_len;
     F.n_rec = F.n_bases = 0;
@@ -130,9 +137,9 @@ int paffy_hip_fasta_index(paffy_hip_ctx *c, const void *d_text, int64_t text_len
         F.n_rec = tot[0];
         F.n_bases = tot[1];
         if (ensure(c, F.recs, sizeof(FaRec) * (size_t)(F.n_rec + 1))) return PAFFY_E_HIP;
-        if (ensure(c, F.bases, (size_t)F.n_bases + 64)) return PAFFY_E_HIP; /* k_fa_emit reads up to 32 bytes past the last base */
+        if (with_bases && ensure(c, F.bases, (size_t)F.n_bases + 64)) return PAFFY_E_HIP; /* k_fa_emit reads up to 32 bytes past the last base */
         LAUNCH(c, "k_fa_write", k_fa_write, dim3(n_tiles), dim3(FA_NT), 0, F.text, text_len, d_starts, nf, static_cast<const FaTile *>(F.tiles.p),
-               static_cast<uint8_t *>(F.bases.p), static_cast<FaRec *>(F.recs.p));
+               with_bases ? static_cast<uint8_t *>(F.bases.p) : nullptr, static_cast<FaRec *>(F.recs.p));
         if (F.n_rec) {
             LAUNCH(c, "k_fa_records", k_fa_records, dim3((unsigned)((F.n_rec + FA_NT - 1) / FA_NT)), dim3(FA_NT), 0, F.text, text_len, d_starts, nf,
                    static_cast<FaRec *>(F.recs.p), F.n_rec, F.n_bases);
@@ -156,6 +163,17 @@ int paffy_hip_fasta_index(paffy_hip_ctx *c, const void *d_text, int64_t text_len
         if (c->profile) prof_collect(c);
     }
     F.indexed = true;
+    return 0;
+}
+
+extern "C" {
+
+int paffy_hip_fasta_index(paffy_hip_ctx *c, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records,
+                          int64_t *n_bases) {
+    if (!c) return PAFFY_E_ARG;
+    FastaState &F = fasta_state(c);
+    const int rc = fa_index(c, F, d_text, text_len, file_starts, n_files, true);
+    if (rc) return rc;
     if (n_records) *n_records = F.n_rec;
     if (n_bases) *n_bases = F.n_bases;
     return 0;
@@ -175,7 +193,8 @@ int64_t paffy_hip_fasta_records(paffy_hip_ctx *c, int64_t first, int64_t cap, pa
 }
 
 int paffy_hip_fasta_copy_bases(paffy_hip_ctx *c, int64_t first, int64_t n, void *d_dst) {
-    if (!c || !c->fasta || !c->fasta->indexed || first < 0 || n < 0 || first + n > c->fasta->n_bases || (n > 0 && !d_dst)) return PAFFY_E_ARG;
+    if (!c || !c->fasta || !c->fasta->indexed || !c->fasta->with_bases || first < 0 || n < 0 || first + n > c->fasta->n_bases || (n > 0 && !d_dst))
+        return PAFFY_E_ARG;
     if (n) HIPCHK(c, hipMemcpyAsync(d_dst, static_cast<const uint8_t *>(c->fasta->bases.p) + first, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;

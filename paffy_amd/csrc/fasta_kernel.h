@@ -327,7 +327,8 @@ __global__ __launch_bounds__(FA_NT) void k_fa_scan(FaTile *tiles, uint32_t n_til
     }
 }
 
-/* bases of a tile to the compact buffer (staged in LDS, stored with 16-byte stores where no other tile writes), record starts */
+/* bases of a tile to the compact buffer (staged in LDS, stored with 16-byte stores where no other tile writes), record starts; bases =
+   nullptr: record starts only */
 __global__ __launch_bounds__(FA_NT) void k_fa_write(const uint8_t *in, int64_t len, const int64_t *starts, int32_t n_files, const FaTile *tiles,
                                                     uint8_t *bases, FaRec *recs) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[FA_TILE];
@@ -346,6 +347,7 @@ __global__ __launch_bounds__(FA_NT) void k_fa_write(const uint8_t *in, int64_t l
     int64_t n_h2 = 0, x_a = 0, x_dep = 0, x_loc = 0;
     fa_span<true>(in, len, starts, n_files, g0, w, n_h2, x_a, x_dep, x_loc, stage, (uint32_t)s1, recs, t.rec_base + s0, t.seq_base + s1);
     __syncthreads();
+    if (!bases) return; /* record starts only (every thread of the workgroup leaves here) */
     /* the tile's bases are [seq_base, seq_base + n): 16-byte stores inside, bytes at the two ends (shared with the neighbours) */
     const int64_t d0 = t.seq_base, d1 = d0 + n_loc;
     const int64_t a0 = (d0 + 15) & ~(int64_t)15, a1 = d1 & ~(int64_t)15;

@@ -3326,8 +3326,10 @@ int paffy_hip_parse_host(paffy_hip_ctx *c, const char *h_in, int64_t in_len, paf
 }
 
 /* Lays the sequence store out for n named sequences (sorted by name for the lookup kernel) and uploads the name tables;
- * blob_off[i] = where sequence i starts in seq_blob. The bases are written by the caller. */
-static int seq_store_layout(paffy_hip_ctx *c, int64_t n, const char *const *names, const int64_t *lens, std::vector<uint64_t> &blob_off) {
+ * blob_off[i] = where sequence i starts in seq_blob. The bases are written by the caller. fixed_off: sequence i starts at fixed_off[i]
+ * of a seq_blob the caller provides (nothing is allocated for it); nullptr: back to back in name order in a seq_blob allocated here. */
+static int seq_store_layout(paffy_hip_ctx *c, int64_t n, const char *const *names, const int64_t *lens, std::vector<uint64_t> &blob_off,
+                            const int64_t *fixed_off = nullptr) {
     c->n_seqs = 0;
     std::vector<int64_t> order((size_t)n);
     for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
@@ -3348,13 +3350,18 @@ static int seq_store_layout(paffy_hip_ctx *c, int64_t n, const char *const *name
         int64_t i = order[(size_t)k];
         name_off[(size_t)k] = (uint32_t)blob.size();
         blob.append(names[i], nlen[(size_t)i]);
-        table[(size_t)k].off = total;
+        const uint64_t at = fixed_off ? (uint64_t)fixed_off[i] : total;
+        table[(size_t)k].off = at;
         table[(size_t)k].len = lens[i];
-        blob_off[(size_t)i] = total;
+        blob_off[(size_t)i] = at;
         total += (uint64_t)lens[i];
     }
     name_off[(size_t)n] = (uint32_t)blob.size();
-    if (ensure(c, c->seq_blob, total + 64)) return PAFFY_E_HIP;
+    if (blob.size() >= 0xffffffffull) { /* name_off is 32-bit */
+        c->last_error = "sequence store: the names pass 4 GiB";
+        return PAFFY_E_ARG;
+    }
+    if (!fixed_off && ensure(c, c->seq_blob, total + 64)) return PAFFY_E_HIP;
     if (ensure(c, c->seq_table, sizeof(SeqEntry) * (size_t)n)) return PAFFY_E_HIP;
     if (ensure(c, c->seq_names, blob.size() + 16)) return PAFFY_E_HIP;
     if (ensure(c, c->seq_name_off, sizeof(uint32_t) * ((size_t)n + 1))) return PAFFY_E_HIP;
@@ -3610,3 +3617,6 @@ int paffy_hip_synth4(paffy_hip_ctx *c, uint64_t r0, uint64_t n, void *d_out, int
 }
 
 } /* extern "C" */
+
+#include "seqload_kernel.h"
+#include "seqload_host.h"

@@ -1,0 +1,151 @@
+/*
+ * seqload_host.h -- FASTA files in HBM to the sequence store (add_mismatches, view), the upconvert intervals and the to_bed -q name query
+ * (include/paffy_hip.h). The text is indexed by fa_index (fasta_host.h) into a state of the loader's own, so a faffy index
+ * of the context is left alone, and that state is freed before the call returns. Included at the end of paffy_hip.hip.
+ */
+#pragma once
+
+/* record r's header as host/paffy_cmds.c's former fasta_read keyed it: a C string, so up to its first NUL byte */
+static std::string fa_key(const FastaState &F, int64_t r) {
+    const char *h = F.h_hdr.data() + F.h_hdr_at[r];
+    return std::string(h, strnlen(h, (size_t)(F.h_hdr_at[r + 1] - F.h_hdr_at[r])));
+}
+
+/* seq_blob holds the bases (input order) from n_bases on: upper case, complement and the raw copy in one pass */
+static int seq_store_fill(paffy_hip_ctx *c, int64_t n_bases) {
+    uint64_t n16 = ((uint64_t)n_bases + 64 + 15) / 16; /* the bases and the 64 bytes past them that seq_store_layout keeps too */
+    if (n16 > c->seq_blob.cap / 16) n16 = c->seq_blob.cap / 16;
+    if (ensure(c, c->seq_comp, n16 * 16)) return PAFFY_E_HIP;
+    if (c->keep_raw && ensure(c, c->seq_raw, n16 * 16)) return PAFFY_E_HIP;
+    if (n16) {
+        const uint64_t blocks = (n16 + PAFFY_NT - 1) / PAFFY_NT;
+        LAUNCH(c, "k_seq_store", k_seq_store, dim3((unsigned)(blocks < SL_GRID_MAX ? blocks : SL_GRID_MAX)), dim3(PAFFY_NT), 0,
+               static_cast<uint8_t *>(c->seq_blob.p), static_cast<uint8_t *>(c->seq_comp.p), c->keep_raw ? static_cast<uint8_t *>(c->seq_raw.p) : nullptr,
+               n16);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->profile) prof_collect(c);
+    }
+    return 0;
+}
+
+static int seq_store_from_index(paffy_hip_ctx *c, FastaState &F) {
+    const int64_t n = F.n_rec;
+    if (n >= (1ll << 31)) {
+        c->last_error = "sequence store: more than 2^31 - 1 records";
+        return PAFFY_E_ARG;
+    }
+    std::vector<std::string> names((size_t)n);
+    std::vector<const char *> ptr((size_t)n);
+    std::vector<int64_t> lens((size_t)n), offs((size_t)n);
+    for (int64_t r = 0; r < n; r++) {
+        names[(size_t)r] = fa_key(F, r);
+        ptr[(size_t)r] = names[(size_t)r].c_str();
+        lens[(size_t)r] = F.h_recs[(size_t)r].seq_len;
+        offs[(size_t)r] = F.h_recs[(size_t)r].seq_off;
+    }
+    std::vector<uint64_t> blob_off;
+    int rc = seq_store_layout(c, n, ptr.data(), lens.data(), blob_off, offs.data());
+    if (rc) return rc;
+    std::swap(c->seq_blob, F.bases); /* the compact bases are the store; the old store goes with F */
+    return seq_store_fill(c, F.n_bases);
+}
+
+extern "C" {
+
+int paffy_hip_set_sequences_fasta(paffy_hip_ctx *c, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records) {
+    if (!c) return PAFFY_E_ARG;
+    c->n_seqs = 0;
+    FastaState F;
+    int rc = fa_index(c, F, d_text, text_len, file_starts, n_files, true);
+    if (!rc && F.n_rec > 0) rc = seq_store_from_index(c, F);
+    fasta_release(F);
+    if (rc) return rc;
+    c->n_seqs = (int32_t)F.n_rec;
+    if (n_records) *n_records = F.n_rec;
+    return 0;
+}
+
+int paffy_hip_set_intervals_fasta(paffy_hip_ctx *c, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records) {
+    if (!c) return PAFFY_E_ARG;
+    c->n_intervals = 0;
+    FastaState F;
+    int rc = fa_index(c, F, d_text, text_len, file_starts, n_files, false);
+    fasta_release(F); /* the host copy of the table and the headers is all that is needed */
+    if (rc) return rc;
+    const int64_t n = F.n_rec;
+    std::vector<std::string> hdr((size_t)n);
+    std::vector<const char *> ptr((size_t)n);
+    std::vector<int64_t> lens((size_t)n);
+    for (int64_t r = 0; r < n; r++) {
+        hdr[(size_t)r] = fa_key(F, r);
+        ptr[(size_t)r] = hdr[(size_t)r].c_str();
+        lens[(size_t)r] = F.h_recs[(size_t)r].seq_len;
+    }
+    if (n_records) *n_records = n;
+    return paffy_hip_set_intervals(c, ptr.data(), lens.data(), n);
+}
+
+int paffy_hip_fasta_index_headers(paffy_hip_ctx *c, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records) {
+    if (!c) return PAFFY_E_ARG;
+    FastaState &F = fasta_state(c);
+    const int rc = fa_index(c, F, d_text, text_len, file_starts, n_files, false);
+    if (rc) return rc;
+    if (n_records) *n_records = F.n_rec;
+    return 0;
+}
+
+int paffy_hip_fasta_seen(paffy_hip_ctx *c, const void *d_paf, int64_t paf_len, int with_target, uint8_t *seen) {
+    if (!c) return PAFFY_E_ARG;
+    if (!c->fasta || !c->fasta->indexed) return PAFFY_E_STATE;
+    if (paf_len < 0 || (paf_len > 0 && !d_paf) || (reinterpret_cast<uintptr_t>(d_paf) & 15u)) return PAFFY_E_ARG;
+    FastaState &F = *c->fasta;
+    const int64_t n = F.n_rec;
+    if (n == 0) return 0;
+    if (!seen) return PAFFY_E_ARG;
+    /* the distinct names, sorted as find_seq expects (bytes, then the shorter first); uid[r] = record r's name */
+    std::vector<std::string> key((size_t)n);
+    std::vector<int64_t> order((size_t)n), uid((size_t)n);
+    for (int64_t r = 0; r < n; r++) {
+        key[(size_t)r] = fa_key(F, r);
+        order[(size_t)r] = r;
+    }
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        const std::string &x = key[(size_t)a], &y = key[(size_t)b];
+        const int d = memcmp(x.data(), y.data(), x.size() < y.size() ? x.size() : y.size());
+        return d ? d < 0 : x.size() < y.size();
+    });
+    std::string blob;
+    std::vector<uint32_t> name_off;
+    for (int64_t k = 0; k < n; k++) {
+        const int64_t r = order[(size_t)k];
+        if (k == 0 || key[(size_t)r] != key[(size_t)order[(size_t)k - 1]]) {
+            name_off.push_back((uint32_t)blob.size());
+            blob += key[(size_t)r];
+            if (blob.size() >= 0xffffffffull) {
+                c->last_error = "fasta_seen: the names pass 4 GiB";
+                return PAFFY_E_ARG;
+            }
+        }
+        uid[(size_t)r] = (int64_t)name_off.size() - 1;
+    }
+    const int32_t n_names = (int32_t)name_off.size();
+    name_off.push_back((uint32_t)blob.size());
+    std::vector<uint8_t> flag((size_t)n_names, 0);
+    if (paf_len > 0) {
+        if (ensure(c, F.seen_names, blob.size() + 16) || ensure(c, F.seen_off, sizeof(uint32_t) * name_off.size()) || ensure(c, F.seen, (size_t)n_names))
+            return PAFFY_E_HIP;
+        if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(F.seen_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(F.seen_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(F.seen.p, 0, (size_t)n_names, c->stream));
+        const int64_t blocks = (paf_len + FA_TILE - 1) / FA_TILE;
+        LAUNCH(c, "k_fa_seen", k_fa_seen, dim3((unsigned)blocks), dim3(FA_NT), 0, static_cast<const uint8_t *>(d_paf), paf_len, with_target ? 1 : 0,
+               static_cast<const uint8_t *>(F.seen_names.p), static_cast<const uint32_t *>(F.seen_off.p), n_names, static_cast<uint8_t *>(F.seen.p));
+        HIPCHK(c, hipMemcpyAsync(flag.data(), F.seen.p, (size_t)n_names, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->profile) prof_collect(c);
+    }
+    for (int64_t r = 0; r < n; r++) seen[r] = flag[(size_t)uid[(size_t)r]];
+    return 0;
+}
+
+} /* extern "C" */

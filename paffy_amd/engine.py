@@ -172,6 +172,11 @@ def lib():
         L.paffy_hip_faffy_extract_plan.argtypes = [vp, C.c_char_p, i64, i64, i64, C.c_int, C.POINTER(PlanInfo)]
         L.paffy_hip_faffy_merge_plan.argtypes = [vp, C.POINTER(PlanInfo)]
         L.paffy_hip_faffy_emit.argtypes = [vp, vp, i64, C.POINTER(_Error)]
+        L.paffy_hip_set_sequences_fasta.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64)]
+        L.paffy_hip_set_intervals_fasta.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64)]
+        L.paffy_hip_fasta_index_headers.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64)]
+        L.paffy_hip_fasta_seen.argtypes = [vp, vp, i64, C.c_int, C.POINTER(C.c_uint8)]
+        L.paffy_hip_keep_raw_sequences.argtypes = [vp, C.c_int]
         _lib = L
     return _lib
 
@@ -630,6 +635,67 @@ class Engine:
         self.fasta_index(d_text, len(data), starts or [0])
         return d_text
 
+    @staticmethod
+    def _fasta_text(files):
+        """FASTA files -> (text back to back, file starts); a str is a path, bytes are a file's contents."""
+        parts = []
+        for f in files:
+            if isinstance(f, bytes):
+                parts.append(f)
+            else:
+                with open(f, "rb") as fh:
+                    parts.append(fh.read())
+        starts, at = [], 0
+        for p in parts:
+            starts.append(at)
+            at += len(p)
+        return b"".join(parts), starts or [0]
+
+    def _load_fasta(self, fn, files, what):
+        data, starts = self._fasta_text(files)
+        d_text = self.to_device(data)
+        st = (C.c_int64 * len(starts))(*starts)
+        n_rec = C.c_int64()
+        rc = fn(self._ctx, C.c_void_p(d_text.data_ptr()), len(data), st, len(starts), C.byref(n_rec))
+        self.torch.cuda.synchronize(self.device)
+        del d_text  # the loaders keep nothing of the text
+        self._check(rc, what)
+        return n_rec.value
+
+    def keep_raw_sequences(self, on=True):
+        """Keep the bases as loaded beside the upper-cased store (what `paffy view -a` prints); set before loading them."""
+        self._check(lib().paffy_hip_keep_raw_sequences(self._ctx, 1 if on else 0), "paffy_hip_keep_raw_sequences")
+
+    def set_sequences_fasta(self, files):
+        """Sequences for add_mismatches from FASTA files (paths, or bytes each) read on the device, as `paffy add_mismatches a.fa b.fa`
+        loads them; returns the number of records."""
+        return self._load_fasta(lib().paffy_hip_set_sequences_fasta, files, "paffy_hip_set_sequences_fasta")
+
+    def set_intervals_fasta(self, files):
+        """Intervals for UPCONVERT from FASTA files (paths, or bytes each) read on the device, as `paffy upconvert a.fa b.fa` loads them;
+        returns the number of records. A header that does not decode raises (the reference aborts)."""
+        return self._load_fasta(lib().paffy_hip_set_intervals_fasta, files, "paffy_hip_set_intervals_fasta")
+
+    def fasta_seen(self, files, paf, with_target=False):
+        """`paffy to_bed -q`'s query: [(name, sequence length, named)] per FASTA record, named = a line of the PAF text names it as its
+        query (or, with with_target, as its target)."""
+        data, starts = self._fasta_text(files)
+        d_text = self.to_device(data)
+        st = (C.c_int64 * len(starts))(*starts)
+        n = C.c_int64()
+        rc = lib().paffy_hip_fasta_index_headers(self._ctx, C.c_void_p(d_text.data_ptr()), len(data), st, len(starts), C.byref(n))
+        del d_text
+        self._check(rc, "paffy_hip_fasta_index_headers")
+        table = self.fasta_table()
+        d_paf = self.to_device(paf)
+        seen = (C.c_uint8 * max(1, n.value))()
+        self._check(lib().paffy_hip_fasta_seen(self._ctx, C.c_void_p(d_paf.data_ptr()), len(paf), 1 if with_target else 0, seen), "paffy_hip_fasta_seen")
+        out = []
+        for k, (h, hl, _, sl) in enumerate(table):
+            name = data[h:h + hl].split(b"\0", 1)[0]
+            out.append((name, sl, bool(seen[k])))
+        return out
+
     def fasta_records(self, files):
         """FASTA files (bytes each) -> [(header, bases)] as the device index reads them."""
         d_text = self._files(files)
@@ -739,11 +805,15 @@ def dechunk(data, query=True, target=True):
     return pipe([stage_dechunk(query, target)], data)
 
 
-def upconvert(data, fasta=None):
-    """paffy upconvert [fasta...] (impl/paf_upconvert.c); fasta: {header: bases} of the extracted subsequences, in file order."""
+def upconvert(data, fasta=None, fasta_files=None):
+    """paffy upconvert [fasta...] (impl/paf_upconvert.c); fasta: {header: bases} of the extracted subsequences, in file order, or
+    fasta_files: the FASTA files themselves (paths, or bytes each), read on the device."""
     e = _engine()
-    fasta = fasta or {}
-    e.set_intervals(list(fasta), [len(v) for v in fasta.values()])
+    if fasta_files is not None:
+        e.set_intervals_fasta(fasta_files)
+    else:
+        fasta = fasta or {}
+        e.set_intervals(list(fasta), [len(v) for v in fasta.values()])
     return e.run([stage(UPCONVERT)], data)[0]
 
 

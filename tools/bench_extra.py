@@ -31,12 +31,15 @@ def main():
     ap.add_argument("--mean-ops", type=int, default=2048)
     ap.add_argument("--contigs", type=int, default=24, help="contigs of the synthetic stream (chain: fewer contigs = larger groups)")
     ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "filter", "add", "dedupe", "bed", "stats", "chain",
-                                                    "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge"])
+                                                    "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload"])
     ap.add_argument("--genome-gb", type=float, default=3.1, help="faffy_*: bases of the synthetic genome (24 contigs)")
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
+    ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome")
     a = ap.parse_args()
     if a.cmd.startswith("faffy_"):
         return faffy_bench(a)
+    if a.cmd == "seqload":
+        return seqload_bench(a)
     import torch
 
     import paffy_amd
@@ -217,6 +220,80 @@ def faffy_bench(a):
                       "seconds_index_plan_emit": round(min(res[1:]), 4), "kernel_ms": kernel_ms, "kernel_ms_total": round(total_ms, 3),
                       "GBps_text_in_out_over_kernel_time": round(moved / (total_ms / 1e3) / 1e9, 1),
                       "fraction_of_8TBps": round(moved / (total_ms / 1e3) / 8e12, 3)}))
+    eng.close()
+
+
+def seqload_bench(a):
+    """The sequence store of add_mismatches / view from FASTA text: paffy_hip_set_sequences_fasta on text resident in HBM (index + store
+    kernels, names sorted on the host) against paffy_hip_set_sequences on the same records held as host strings (one copy per record +
+    k_seq_canon; the host parse of the former CLI path is not included). The text is freed by neither call."""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    import paffy_amd
+    from paffy_amd import engine as E
+
+    L = E.lib()
+    eng = paffy_amd.Engine()
+    dev = eng.device
+    if a.scaffolds:
+        rng = np.random.default_rng(11)
+        lens = rng.integers(1, 2001, a.scaffolds)
+        seq = np.frombuffer(b"ACGTacgtN", dtype=np.uint8)[rng.integers(0, 9, int(lens.sum()))].tobytes()
+        parts, at = [], 0
+        for i, n in enumerate(lens.tolist()):
+            parts.append(b">scaffold_%d\n%s\n" % (i, seq[at:at + n]))
+            at += n
+        host = b"".join(parts)
+        text = eng.to_device(host)
+        nbytes = len(host)
+    else:
+        text, nbytes, _ = synth_genome(torch, dev, a.genome_gb)
+    torch.cuda.synchronize()
+    st = (C.c_int64 * 1)(0)
+    n_rec = C.c_int64()
+    new = []
+    for rep in range(3):
+        if rep == 1:
+            eng.profile(True)
+        t0 = time.perf_counter()
+        assert L.paffy_hip_set_sequences_fasta(eng._ctx, C.c_void_p(text.data_ptr()), nbytes, st, 1, C.byref(n_rec)) == 0
+        eng.sync()
+        new.append(time.perf_counter() - t0)
+    prof = {k: (v[0], v[1]) for k, v in eng.profile_read().items()}
+    eng.profile(False)
+    kernel_ms = {k: round(ms / max(1, cnt), 3) for k, (ms, cnt) in prof.items()}
+    # the records as host strings (what the former host parse produced), then the host-string call
+    recs = eng.fasta_records([bytes(text[:nbytes].cpu().numpy().tobytes())]) if a.scaffolds else None
+    if recs is None:
+        eng.fasta_index(text, nbytes, [0])
+        table = eng.fasta_table()
+        total = table[-1][2] + table[-1][3]
+        buf = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+        eng.fasta_bases(0, total, buf)
+        bases = buf[:total].cpu().numpy().tobytes()
+        recs = [(b"chr%d" % k, bases[s:s + n]) for k, (_, _, s, n) in enumerate(table)]
+        del buf
+    del text
+    torch.cuda.empty_cache()
+    names = (C.c_char_p * len(recs))(*[h for h, _ in recs])
+    seqs = (C.c_char_p * len(recs))(*[s for _, s in recs])
+    lns = (C.c_int64 * len(recs))(*[len(s) for _, s in recs])
+    old = []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        assert L.paffy_hip_set_sequences(eng._ctx, len(recs), names, seqs, lns) == 0
+        eng.sync()
+        old.append(time.perf_counter() - t0)
+    n_bases = sum(len(s) for _, s in recs)
+    store_ms = kernel_ms.get("k_seq_store", 0.0)
+    moved = 3 * n_bases  # k_seq_store: the bases read once, written upper-cased and complemented (no raw copy here)
+    print(json.dumps({"cmd": "seqload", "text_bytes": nbytes, "records": n_rec.value, "bases": n_bases,
+                      "seconds_set_sequences_fasta": round(min(new[1:]), 4), "seconds_set_sequences_host_strings": round(min(old[1:]), 4),
+                      "kernel_ms": kernel_ms, "k_seq_store_GBps": round(moved / (store_ms / 1e3) / 1e9, 1) if store_ms else None,
+                      "k_seq_store_fraction_of_8TBps": round(moved / (store_ms / 1e3) / 8e12, 3) if store_ms else None}))
     eng.close()
 
 
