@@ -1051,6 +1051,14 @@ struct ProfEntry {
     int64_t launches = 0;
 };
 
+/* what the current plan is, and so what paffy_hip_emit writes and which getters answer */
+enum PlanKind {
+    PLAN_NONE,
+    PLAN_RECORDS, /* paffy_hip_plan: the stage list's output through the record writers */
+    PLAN_LINES,   /* tile, chain, dedupe, upconvert: a line table (header + the cigar text as it was read) */
+    PLAN_BED      /* paffy to_bed: the run lines */
+};
+
 struct paffy_hip_ctx {
     hipStream_t stream = nullptr;
     hipStream_t side = nullptr; /* sizing launches of the long-cigar records run here, beside the main launch */
@@ -1065,8 +1073,6 @@ struct paffy_hip_ctx {
     DevBuf dedupe_keys;
     struct DedupeState *dedupe = nullptr; /* dedupe_host.h: keys of the records written so far (sorted, on the device) and scratch */
     DevBuf scan_part, emit_order, order_cnt, tile_keys, tile_order, tile_rank, tile_coff, tile_cbase, tile_cov, tile_level, tile_len, tile_items, tile_slots, tile_parts;
-    bool plan_is_tile = false;
-    bool plan_is_bed = false; /* paffy to_bed: emit writes the run lines */
     bool keep_raw = false;    /* paffy_hip_keep_raw_sequences: seq_raw holds the bases as loaded (paf_pretty_print shows their case) */
     bool plan_seq_lookup = false; /* rec_qseq / rec_tseq belong to the current plan */
     DevBuf seq_raw, pretty_off, pretty_out, pretty_err, host_in, host_out;
@@ -1077,7 +1083,6 @@ struct paffy_hip_ctx {
     DevBuf bed_keys, bed_tab, bed_starts, bed_len, bed_off, bed_tiles;
     struct BedParams *bed_params = nullptr; /* host copy */
     uint64_t bed_runs = 0;
-    uint32_t tile_n = 0;
     const uint8_t *tile_in = nullptr;
     struct ChainState *chain = nullptr; /* `paffy chain` (chain_host.h) */
     struct FastaState *fasta = nullptr; /* `faffy chunk | extract | merge`: FASTA index and item plan (fasta_host.h) */
@@ -1109,8 +1114,9 @@ struct paffy_hip_ctx {
     DevBuf up_table, up_names;
     uint32_t n_intervals = 0;
     DevInfo *h_info = nullptr; /* pinned */
-    /* plan state */
+    /* plan state (plan_begin clears it) */
     bool planned = false;
+    PlanKind plan_kind = PLAN_NONE;
     KParams kp;
     paffy_plan_info plan;
     /* profiling */
@@ -1207,21 +1213,52 @@ static bool prof_wants(const paffy_hip_ctx *c, const char *name) { return c->pro
         HIPCHK(ctx, hipGetLastError());                                                     \
     } while (0)
 
+/* the dynamic LDS of one stage-mask instantiation of the sizing kernels (more than the default 64 KiB) */
+template <uint32_t MASK>
+static void size_lds_attributes() {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds<MASK>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds_long<MASK>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG));
+}
+
+/* One sizing pass of the record kernels: levels 1 and 2 (long cigars, queued by k_header) on the side stream, level 0 on the main one
+   -- one wave per record for the cigars of at most kp.wave_max_bytes (0: none), four waves for the rest -- then the join. */
+template <uint32_t MASK>
+static int size_records(paffy_hip_ctx *c, const KParams &kp, uint32_t n_lines) {
+    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    KParams k1 = kp;
+    k1.ops_cap = PAFFY_OPS_CAP_MID;
+    k1.next_cap = PAFFY_OPS_CAP_BIG;
+    k1.level = 1;
+    hipLaunchKernelGGL(k_size_lds_long<MASK>, dim3(768), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_MID), c->side, k1);
+    k1.ops_cap = PAFFY_OPS_CAP_BIG;
+    k1.next_cap = 0;
+    k1.level = 2;
+    hipLaunchKernelGGL(k_size_lds_long<MASK>, dim3(256), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG), c->side, k1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_join, c->side));
+    if (kp.wave_max_bytes) { /* short cigars: one wave per record, sixteen records in flight per CU */
+        KParams kw = kp;
+        kw.ops_cap = WAVE_OPS_CAP;
+        const size_t wlds = (size_t)WAVE_OPS_CAP * 4 + PAFFY_HALO + 64 * 16 + 64 * 8 + 64;
+        LAUNCH(c, "k_size_wave", g64::k_size_lds<MASK>, dim3(n_lines), dim3(64), wlds, kw);
+    }
+    LAUNCH(c, "k_size_lds", k_size_lds<MASK>, dim3(n_lines), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES, kp);
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0)); /* join */
+    return 0;
+}
+static int size_records_for(paffy_hip_ctx *c, uint32_t mask, const KParams &kp, uint32_t n_lines) {
+    switch (mask) {
+    case PAFFY_MASK_LEAN: return size_records<PAFFY_MASK_LEAN>(c, kp, n_lines);
+    case PAFFY_MASK_ADD: return size_records<PAFFY_MASK_ADD>(c, kp, n_lines);
+    case PAFFY_MASK_SEL: return size_records<PAFFY_MASK_SEL>(c, kp, n_lines);
+    case PAFFY_MASK_PLAIN: return size_records<PAFFY_MASK_PLAIN>(c, kp, n_lines);
+    default: return size_records<PAFFY_MASK_ALL>(c, kp, n_lines);
+    }
+}
+
 extern "C" {
 
-/* Experiments only: extra dynamic LDS per workgroup of the row writer (0), the one-wave sizing launch (1) and the four-wave sizing launch (2)
-   of the lean pipes, from PAFFY_DBG_LDS_PAD="emit,size64,size256" (bytes) -- lowers a kernel's occupancy so that two contexts' kernels can be
-   resident on a CU at the same time (bench.py --pipeline 2). */
-static size_t dbg_lds_pad(int which) {
-    static long pad[3] = {-1, 0, 0};
-    if (pad[0] < 0) {
-        pad[0] = 0;
-        const char *e = getenv("PAFFY_DBG_LDS_PAD");
-        if (e) sscanf(e, "%ld,%ld,%ld", &pad[0], &pad[1], &pad[2]);
-        for (int k = 0; k < 3; k++) pad[k] = pad[k] < 0 ? 0 : pad[k] & ~15l;
-    }
-    return (size_t)pad[which];
-}
 int paffy_hip_create(paffy_hip_ctx **out, int device) {
     if (!out) return PAFFY_E_ARG;
     if (device >= 0 && hipSetDevice(device) != hipSuccess) return PAFFY_E_HIP;
@@ -1240,16 +1277,11 @@ int paffy_hip_create(paffy_hip_ctx **out, int device) {
     /* the record kernels use more than the default 64 KiB of LDS */
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cov_walk<true>), hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(CovWalkLds));
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cov_walk<false>), hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(CovWalkLds));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds<PAFFY_MASK_ALL>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds<PAFFY_MASK_LEAN>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES + dbg_lds_pad(2));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds<PAFFY_MASK_ADD>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds<PAFFY_MASK_PLAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds<PAFFY_MASK_SEL>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds_long<PAFFY_MASK_PLAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds_long<PAFFY_MASK_SEL>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds_long<PAFFY_MASK_ADD>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds_long<PAFFY_MASK_ALL>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_size_lds_long<PAFFY_MASK_LEAN>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG));
+    size_lds_attributes<PAFFY_MASK_LEAN>();
+    size_lds_attributes<PAFFY_MASK_ADD>();
+    size_lds_attributes<PAFFY_MASK_SEL>();
+    size_lds_attributes<PAFFY_MASK_PLAIN>();
+    size_lds_attributes<PAFFY_MASK_ALL>();
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_emit_lds<true>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_EMIT_LDS_BYTES);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_emit_lds<false>), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_EMIT_LDS_BYTES);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_arena_size), hipFuncAttributeMaxDynamicSharedMemorySize, PAFFY_SIZE_LDS_BYTES);
@@ -1315,6 +1347,22 @@ static int fetch_info(paffy_hip_ctx *c) {
     return 0;
 }
 
+/* Every planner starts here: nothing that describes the plan before survives (what emit writes, what the getters report). */
+static void plan_begin(paffy_hip_ctx *c, PlanKind kind, int64_t in_bytes, paffy_plan_info *info) {
+    c->planned = false;
+    c->plan_kind = kind;
+    memset(info, 0, sizeof(*info));
+    info->in_bytes = in_bytes;
+    memset(&c->plan, 0, sizeof(c->plan));
+    c->plan.in_bytes = in_bytes;
+    memset(&c->kp, 0, sizeof(c->kp));
+    c->flat_left = -1;
+    memset(c->flat_reasons, 0, sizeof(c->flat_reasons));
+    c->line_n = 0;
+    c->bed_runs = 0;
+    c->plan_seq_lookup = false;
+}
+
 /* Separator index + header parse shared by plan and tile_plan. */
 static void index_drop(paffy_hip_ctx *c, const void *d_in);
 static int index_and_parse(paffy_hip_ctx *c, const uint8_t *in, uint32_t len, uint32_t *n_lines_out, uint32_t lvl0_max = PAFFY_OPS_CAP, bool flat = false) {
@@ -1337,7 +1385,7 @@ static int index_and_parse(paffy_hip_ctx *c, const uint8_t *in, uint32_t len, ui
         if (ensure(c, c->flat_nd, sizeof(uint16_t) * (((size_t)len >> FLAT_TILE_SHIFT) + 2))) return PAFFY_E_HIP;
         nd = static_cast<uint16_t *>(c->flat_nd.p);
     }
-    if (c->sep_guess_per_mib > 0 && !getenv("PAFFY_TWO_PASS_INDEX")) {
+    if (c->sep_guess_per_mib > 0) {
         const double mib = (double)len / (1 << 20) + 1.0;
         const size_t want_seps = (size_t)(c->sep_guess_per_mib * mib * 1.25) + 4096, want_lines = (size_t)(c->line_guess_per_mib * mib * 1.25) + 4096;
         if (ensure(c, c->sep_pos, sizeof(uint32_t) * (want_seps + 1)) || ensure(c, c->nl_idx, sizeof(uint32_t) * (want_lines + 1)) ||
@@ -1370,19 +1418,14 @@ static int index_and_parse(paffy_hip_ctx *c, const uint8_t *in, uint32_t len, ui
         c->line_guess_per_mib = (double)n_lines / mib + 1.0;
     }
 
-    if (ensure(c, c->meta, sizeof(RecMeta) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->b_list, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->out_len, sizeof(int64_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->out_rows, sizeof(int64_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->out_off, sizeof(int64_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->status, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->err_aux, sizeof(int32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->n_ops, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->arena_off, sizeof(uint64_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->w_list, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->b_list, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->b_list1, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-    if (ensure(c, c->rec_plan, sizeof(RecPlan) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
+    const struct {
+        DevBuf *buf;
+        size_t entry;
+    } per_record[] = {{&c->meta, sizeof(RecMeta)},     {&c->b_list, sizeof(uint32_t)},    {&c->out_len, sizeof(int64_t)}, {&c->out_rows, sizeof(int64_t)},
+                      {&c->out_off, sizeof(int64_t)},  {&c->status, sizeof(uint32_t)},    {&c->err_aux, sizeof(int32_t)}, {&c->n_ops, sizeof(uint32_t)},
+                      {&c->arena_off, sizeof(uint64_t)}, {&c->w_list, sizeof(uint32_t)}, {&c->b_list1, sizeof(uint32_t)}, {&c->rec_plan, sizeof(RecPlan)}};
+    for (const auto &r : per_record)
+        if (ensure(c, *r.buf, r.entry * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
     if (ensure(c, c->ops_mirror, sizeof(uint32_t) * ((size_t)len / 2 + 64))) return PAFFY_E_HIP;
     if (c->arena.cap == 0 && ensure(c, c->arena, (size_t)8 << 20)) return PAFFY_E_HIP;
 
@@ -1409,130 +1452,104 @@ static int index_and_parse(paffy_hip_ctx *c, const uint8_t *in, uint32_t len, ui
 }
 
 static int upconvert_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bool check, paffy_plan_info *info);
-int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages, const void *d_in, int64_t in_len,
-                   paffy_plan_info *info) {
-    if (!c || !info || (n_stages > 0 && !stages) || n_stages < 0 || n_stages > PAFFY_MAX_STAGES) return PAFFY_E_ARG;
-    if (in_len < 0 || in_len >= (1ll << 31) - 64 || (in_len > 0 && !d_in) || (reinterpret_cast<uintptr_t>(d_in) & 15)) return PAFFY_E_ARG;
-    bool need_seqs = false;
-    paffy_stage norm[PAFFY_MAX_STAGES]; /* kinds without the PAFFY_NO_CHECK flag */
-    uint32_t nocheck_mask = 0;
+
+/* what a stage list asks of paffy_hip_plan, worked out once */
+enum FlatMode {
+    FLAT_MODE_NONE, /* the record kernels size every record */
+    FLAT_MODE_PASS, /* the flat pass (flat_kernel.h); what it leaves goes to the record kernels */
+    FLAT_MODE_ADD   /* `paffy add_mismatches` alone: the flat parse and the encoder on its pieces (flat_add_kernel.h) */
+};
+struct StageClass {
+    paffy_stage stages[PAFFY_MAX_STAGES]; /* kinds without the PAFFY_NO_CHECK flag; a leading dechunk is its paf_check */
+    int32_t n_stages;
+    uint32_t nocheck_mask, fix_query, fix_target;
+    bool upconvert; /* `paffy upconvert`: a plan of its own */
+    bool need_seqs, add_not_last, has_stats, has_shatter, fixed_last;
+    FlatMode flat;
+    uint32_t size_mask; /* the instantiation of the sizing kernels: PAFFY_MASK_LEAN / ADD / SEL / PLAIN / ALL */
+};
+
+static int classify_stages(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages, StageClass &s) {
+    s = StageClass{};
+    s.n_stages = n_stages;
+    paffy_stage *norm = s.stages;
     for (int32_t i = 0; i < n_stages; i++) {
         norm[i] = stages[i];
-        if (stages[i].kind & PAFFY_NO_CHECK) nocheck_mask |= 1u << i;
+        if (stages[i].kind & PAFFY_NO_CHECK) s.nocheck_mask |= 1u << i;
         norm[i].kind = stages[i].kind & ~PAFFY_NO_CHECK;
     }
     /* `paffy dechunk` in front: k_dechunk rewrites the parsed names and coordinates, and what is left of the stage is its paf_check */
     const bool dechunk = n_stages > 0 && norm[0].kind == PAFFY_DECHUNK;
-    const uint32_t fix_query = dechunk && norm[0].p0 != 0.0f, fix_target = dechunk && norm[0].p1 != 0.0f;
+    s.fix_query = dechunk && norm[0].p0 != 0.0f;
+    s.fix_target = dechunk && norm[0].p1 != 0.0f;
     if (dechunk) {
-        norm[0].kind = (nocheck_mask & 1u) ? PAFFY_PASS : PAFFY_CHECK;
+        norm[0].kind = (s.nocheck_mask & 1u) ? PAFFY_PASS : PAFFY_CHECK;
         norm[0].p0 = norm[0].p1 = 0.0f;
-        nocheck_mask &= ~1u;
+        s.nocheck_mask &= ~1u;
     }
     if (n_stages > 0 && norm[0].kind == PAFFY_UPCONVERT) { /* its read differs (no cigar parse): a plan of its own */
         if (n_stages != 1) {
             c->last_error = "upconvert is a stage list of its own";
             return PAFFY_E_UNSUPPORTED;
         }
-        return upconvert_plan(c, d_in, in_len, (nocheck_mask & 1u) == 0, info);
+        s.upconvert = true;
+        return 0;
     }
-    stages = norm;
+    uint32_t kinds = 0;
     for (int32_t i = 0; i < n_stages; i++) {
-        int k = stages[i].kind;
+        int k = norm[i].kind;
         bool ok = k == PAFFY_CHECK || k == PAFFY_INVERT || k == PAFFY_TRIM_IDENTITY || k == PAFFY_TRIM_FIXED || k == PAFFY_TRIM_ENDS || k == PAFFY_PASS || k == PAFFY_FILTER || k == PAFFY_STATS ||
                   k == PAFFY_REMOVE_MISMATCHES || (k == PAFFY_ADD_MISMATCHES && c->n_seqs > 0) ||
                   (k == PAFFY_SHATTER && i == n_stages - 1);
-        if (k == PAFFY_ADD_MISMATCHES) need_seqs = true;
         if (!ok) {
             c->last_error = "stage list not fusable in this build";
             return PAFFY_E_UNSUPPORTED;
         }
+        kinds |= 1u << k;
+        /* add_mismatches makes more ops of a cigar (about 1.8 x at 2 % substitutions, 1.45 per two cigar bytes): when a stage follows
+           it, its records start one store level up at 5/8 of the usual length, so that the rebuilt array usually fits the level the
+           record was parsed at */
+        if (k == PAFFY_ADD_MISMATCHES && i + 1 < n_stages) s.add_not_last = true;
     }
-    bool lean = true; /* only stage kinds the lean sizing kernel knows */
-    for (int32_t i = 0; i < n_stages; i++) lean = lean && ((PAFFY_MASK_LEAN >> stages[i].kind) & 1u);
-    bool lean_add = !lean; /* the lean kinds and add_mismatches: its own instantiation (the encoder wants the registers) */
-    for (int32_t i = 0; i < n_stages; i++) lean_add = lean_add && ((PAFFY_MASK_ADD >> stages[i].kind) & 1u);
-    bool sel = !lean && !lean_add; /* the lean kinds with filter / trim -f / stats / check */
-    for (int32_t i = 0; i < n_stages; i++) sel = sel && ((PAFFY_MASK_SEL >> stages[i].kind) & 1u);
-    bool plain = !lean; /* no stage of the kinds that came with the encoder: the instantiation without them */
-    for (int32_t i = 0; i < n_stages; i++) plain = plain && ((PAFFY_MASK_PLAIN >> stages[i].kind) & 1u);
-    c->planned = false;
-    c->plan_is_tile = false;
-    c->plan_is_bed = false;
-    c->flat_left = -1;
-    memset(info, 0, sizeof(*info));
-    info->in_bytes = in_len;
-    memset(&c->plan, 0, sizeof(c->plan));
-    c->plan.in_bytes = in_len;
-    KParams &kp = c->kp;
-    memset(&kp, 0, sizeof(kp));
-    if (in_len == 0) {
-        c->planned = true;
-        kp.n_rec = 0;
-        return 0;
-    }
-    const uint8_t *in = static_cast<const uint8_t *>(d_in);
-    const uint32_t len = (uint32_t)in_len;
-    uint32_t n_lines = 0;
-    /* add_mismatches makes more ops of a cigar (about 1.8 x at 2 % substitutions, 1.45 per two cigar bytes): when a stage follows it, its
-       records start one store level up at 5/8 of the usual length, so that the rebuilt array usually fits the level the record was parsed at */
-    const bool add_not_last = need_seqs && [&] {
-        for (int32_t i = 0; i + 1 < n_stages; i++)
-            if (stages[i].kind == PAFFY_ADD_MISMATCHES) return true;
-        return false;
-    }();
-    /* Cigars of more than 2 x lvl0_max bytes start at the second store level (k_header queues them), whose 64 KB of ops leave a CU two
-       workgroups: on cfg3 / cfg4 the 7 % of the records there cost as much kernel time as all the others. Two bytes per op is the bound
-       that can never overflow the first level's 8 192-op store, but a cigar of the usual density (2.5-3 bytes per op) fits it up to about
-       LVL0_LONG_BYTES. So a context starts with the safe bound and lets the second level count the records that would have overflowed the
-       longer one (DevInfo::lvl0_probe_dense); a batch without any switches the following batches to the longer first level (cfg4 12.23 ->
-       11.72 ms per step, cfg3 -1.2 to -1.6 %), and the first record that does overflow there (it goes to the arena class: slow, correct)
-       switches the context back for good. PAFFY_LVL0_BYTES overrides the length (0: never). */
-    static const uint32_t lvl0_long_bytes = getenv("PAFFY_LVL0_BYTES") ? (uint32_t)atol(getenv("PAFFY_LVL0_BYTES")) : LVL0_LONG_BYTES;
-    const bool lvl0_long = !add_not_last && c->lvl0_long_ok && lvl0_long_bytes > 2u * PAFFY_OPS_CAP;
-    const uint32_t lvl0_max = add_not_last ? PAFFY_OPS_CAP * 5 / 8 : (lvl0_long ? lvl0_long_bytes / 2u : PAFFY_OPS_CAP);
-    /* records with at most this many cigar bytes (about WAVE_OPS_CAP ops at three bytes per op) are sized one wave per record; denser
-       cigars of that length overflow the wave's store and are redone by the four-wave build. add_mismatches rebuilds the op array: when
-       a stage follows it the new array must fit the store, so only pipes that end with it take the one-wave build. */
-    static const uint32_t wave_env = getenv("PAFFY_WAVE_BYTES") ? (uint32_t)atoi(getenv("PAFFY_WAVE_BYTES")) : WAVE_MAX_BYTES;
-    static const uint32_t wave_cap_env = getenv("PAFFY_WAVE_OPS") ? (uint32_t)atoi(getenv("PAFFY_WAVE_OPS")) : WAVE_OPS_CAP;
-    const uint32_t wave_bytes = (need_seqs && add_not_last) ? 0u : wave_env;
+    s.need_seqs = (kinds >> PAFFY_ADD_MISMATCHES) & 1u;
+    s.has_stats = (kinds >> PAFFY_STATS) & 1u;
+    s.has_shatter = (kinds >> PAFFY_SHATTER) & 1u;
     /* the lean pipes are sized by the flat pass (flat_kernel.h): the text parsed in chunks whatever record they belong to, one wave per
-       record on the chunks' summaries; what it leaves (FLAT_F_IRREG and friends) goes through the record kernels below as before */
+       record on the chunks' summaries; what it leaves (FLAT_F_IRREG and friends) goes through the record kernels as before. It also
+       knows `paffy filter` (a predicate on the sums it keeps anyway), the stats stage of `paffy view -s` (paf_stats_calc,
+       impl/paf.c:236-260: sums the pieces' summaries hold, with the I ops counted where a shatter pipe counts the digits of its rows --
+       so not both in one pipe), and a fixed trim (`paffy trim -f`) as the pipe's last stage: the wave kernel finds the two ops it stops
+       at (flat_find_aligned) */
+    s.fixed_last = n_stages > 0 && norm[n_stages - 1].kind == PAFFY_TRIM_FIXED;
+    const uint32_t flat_kinds = PAFFY_MASK_LEAN | (1u << PAFFY_FILTER) | (s.has_shatter ? 0u : 1u << PAFFY_STATS) | (dechunk ? 1u << PAFFY_CHECK : 0u);
+    bool lean_or_filter = n_stages > 0;
+    for (int32_t i = 0; i < n_stages; i++)
+        lean_or_filter = lean_or_filter && (((flat_kinds >> norm[i].kind) & 1u) || (s.fixed_last && i == n_stages - 1));
     static const bool flat_off = getenv("PAFFY_NO_FLAT") != nullptr;
     /* `paffy add_mismatches` alone (BASELINE cfg4): the same parse, the encoder on the pieces (flat_add_kernel.h) */
-    const bool flat_add = n_stages == 1 && stages[0].kind == PAFFY_ADD_MISMATCHES && nocheck_mask == 0 && !flat_off && c->n_seqs > 0;
-    bool lean_or_filter = n_stages > 0; /* the flat pass also knows `paffy filter` (a predicate on the sums it keeps anyway) */
-    /* ... and the stats stage of `paffy view -s` (paf_stats_calc, impl/paf.c:236-260: sums the pieces' summaries hold, with the I ops counted
-       where a shatter pipe counts the digits of its rows -- so not both in one pipe) */
-    bool has_stats = false, has_shatter_stage = false;
-    for (int32_t i = 0; i < n_stages; i++) {
-        has_stats = has_stats || stages[i].kind == PAFFY_STATS;
-        has_shatter_stage = has_shatter_stage || stages[i].kind == PAFFY_SHATTER;
-    }
-    /* ... and a fixed trim (`paffy trim -f`) as the pipe's last stage: the wave kernel finds the two ops it stops at (flat_find_aligned) */
-    const bool fixed_last = n_stages > 0 && stages[n_stages - 1].kind == PAFFY_TRIM_FIXED;
-    const uint32_t flat_kinds = PAFFY_MASK_LEAN | (1u << PAFFY_FILTER) | (has_shatter_stage ? 0u : 1u << PAFFY_STATS) | (dechunk ? 1u << PAFFY_CHECK : 0u);
-    for (int32_t i = 0; i < n_stages; i++)
-        lean_or_filter = lean_or_filter && (((flat_kinds >> stages[i].kind) & 1u) || (fixed_last && i == n_stages - 1));
-    const bool flat = (lean_or_filter && nocheck_mask == 0 && !flat_off) || flat_add;
-    {
-        int rc = index_and_parse(c, in, len, &n_lines, lvl0_max, flat);
-        if (rc) return rc;
-    }
-    if ((fix_query || fix_target) && n_lines > 0)
-        LAUNCH(c, "k_dechunk", k_dechunk, dim3((n_lines + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, in, static_cast<RecMeta *>(c->meta.p), n_lines,
-               fix_query, fix_target);
-    kp.lvl0_max = lvl0_max;
-    kp.lvl0_long_bytes = (!add_not_last && !lvl0_long && !c->lvl0_long_off && lvl0_long_bytes > 2u * PAFFY_OPS_CAP) ? lvl0_long_bytes : 0u;
+    if (n_stages == 1 && norm[0].kind == PAFFY_ADD_MISMATCHES && s.nocheck_mask == 0 && !flat_off && c->n_seqs > 0) s.flat = FLAT_MODE_ADD;
+    else if (lean_or_filter && s.nocheck_mask == 0 && !flat_off) s.flat = FLAT_MODE_PASS;
+    /* the first instantiation that knows every stage kind: the lean kinds; them and add_mismatches (the encoder wants the registers); them
+       with filter / trim -f / stats / check; no stage of the kinds that came with the encoder; all */
+    s.size_mask = PAFFY_MASK_ALL;
+    for (uint32_t m : {PAFFY_MASK_LEAN, PAFFY_MASK_ADD, PAFFY_MASK_SEL, PAFFY_MASK_PLAIN})
+        if ((kinds & ~m) == 0) {
+            s.size_mask = m;
+            break;
+        }
+    return 0;
+}
 
+/* the record kernels' parameters for the batch at in (c->kp), with the sequence lookup of add_mismatches and the stats stage's sums */
+static int record_params(paffy_hip_ctx *c, const StageClass &s, const uint8_t *in, uint32_t len, uint32_t n_lines) {
+    KParams &kp = c->kp;
     kp.in = in;
     kp.in_len = len;
     kp.n_rec = n_lines;
     kp.meta = static_cast<const RecMeta *>(c->meta.p);
-    for (int32_t i = 0; i < n_stages; i++) kp.stages[i] = stages[i];
-    kp.n_stages = n_stages;
-    kp.nocheck_mask = nocheck_mask;
+    for (int32_t i = 0; i < s.n_stages; i++) kp.stages[i] = s.stages[i];
+    kp.n_stages = s.n_stages;
+    kp.nocheck_mask = s.nocheck_mask;
     kp.out_len = static_cast<int64_t *>(c->out_len.p);
     kp.out_rows = static_cast<int64_t *>(c->out_rows.p);
     kp.status = static_cast<uint32_t *>(c->status.p);
@@ -1541,8 +1558,8 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
     kp.arena_off = static_cast<uint64_t *>(c->arena_off.p);
     kp.rec_plan = c->rec_plan.p;
     kp.ops_mirror = static_cast<uint32_t *>(c->ops_mirror.p);
-    c->plan_seq_lookup = need_seqs && n_lines > 0;
-    if (need_seqs && n_lines > 0) {
+    c->plan_seq_lookup = s.need_seqs && n_lines > 0;
+    if (s.need_seqs && n_lines > 0) {
         if (ensure(c, c->rec_qseq, sizeof(int32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
         if (ensure(c, c->rec_tseq, sizeof(int32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
         LAUNCH(c, "k_seq_lookup", k_seq_lookup, dim3((n_lines + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, in,
@@ -1561,281 +1578,248 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
     kp.b_list[1] = static_cast<uint32_t *>(c->b_list1.p);
     kp.info = static_cast<DevInfo *>(c->info.p);
     kp.filter = c->filter;
-    for (int32_t i = 0; i < n_stages; i++)
-        if (stages[i].kind == PAFFY_STATS && n_lines > 0) {
+    for (int32_t i = 0; i < s.n_stages; i++)
+        if (s.stages[i].kind == PAFFY_STATS && n_lines > 0) {
             if (ensure(c, c->rec_stats, sizeof(int64_t) * 6 * (size_t)n_lines)) return PAFFY_E_HIP;
             kp.rec_stats = static_cast<int64_t *>(c->rec_stats.p);
             HIPCHK(c, hipMemsetAsync(c->rec_stats.p, 0, sizeof(int64_t) * 6 * (size_t)n_lines, c->stream)); /* records that stop before the stage */
         }
+    return 0;
+}
 
-    auto post_scans = [&]() -> int {
-        /* the scan rides along: one host synchronisation per plan in the usual case (the arena was big enough) */
-        {
-            const uint32_t n_blocks = (n_lines + SCAN_BLOCK - 1) / SCAN_BLOCK;
-            if (ensure(c, c->scan_part, sizeof(int64_t) * 2 * (size_t)n_blocks)) return PAFFY_E_HIP;
-            LAUNCH(c, "k_scan_part", k_scan_part, dim3(n_blocks), dim3(PAFFY_NT), 0, kp.out_len, kp.out_rows, n_lines,
-                   static_cast<int64_t *>(c->out_off.p), static_cast<int64_t *>(c->scan_part.p), kp.info);
-            LAUNCH(c, "k_scan_fix", k_scan_fix, dim3(n_blocks), dim3(PAFFY_NT), 0, n_lines, n_blocks, static_cast<int64_t *>(c->out_off.p),
-                   static_cast<const int64_t *>(c->scan_part.p), kp.info);
-        }
-        {
-            if (ensure(c, c->emit_order, sizeof(uint32_t) * (size_t)n_lines)) return PAFFY_E_HIP;
-            if (ensure(c, c->order_cnt, sizeof(uint32_t) * 2 * ORDER_CLASSES)) return PAFFY_E_HIP;
-            uint32_t *cnt = static_cast<uint32_t *>(c->order_cnt.p);
-            HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint32_t) * 2 * ORDER_CLASSES, c->stream));
-            const uint32_t g = (n_lines + PAFFY_NT - 1) / PAFFY_NT;
-            LAUNCH(c, "k_order_count", k_order_count, dim3(g), dim3(PAFFY_NT), 0, kp.out_len, n_lines, 14u, cnt);
-            LAUNCH(c, "k_order_scatter", k_order_scatter, dim3(g), dim3(PAFFY_NT), 0, kp.out_len, n_lines, 14u, cnt, cnt + ORDER_CLASSES,
-                   static_cast<uint32_t *>(c->emit_order.p));
-            kp.emit_order = static_cast<const uint32_t *>(c->emit_order.p);
-        }
-        return 0;
-    };
-    uint32_t flat_g_count = 0;
-    bool need_legacy = true;
-    if (flat_add && n_lines > 0) {
-        FlatParams fp;
-        fp.in = in;
-        fp.in_len = len;
-        fp.meta = kp.meta;
-        fp.chunk_rec = static_cast<const uint32_t *>(c->flat_chunks.p);
-        fp.n_chunk_slots = c->flat_chunk_slots;
-        fp.nd = static_cast<const uint16_t *>(c->flat_nd.p);
-        fp.sums = static_cast<PieceSum *>(c->flat_sums.p);
-        fp.ops_mirror = kp.ops_mirror;
-        fp.info = kp.info;
-        fp.items_mode = 1;
-        LAUNCH(c, "k_flat_parse", k_flat_parse<1u>, dim3(2048), dim3(64 * FLAT_PARSE_WAVES), 0, fp);
-        const uint32_t n_slots = c->flat_piece_slots, n_sblocks = (n_slots + SCAN32_BLOCK - 1) / SCAN32_BLOCK;
-        if (ensure(c, c->add_pieces, sizeof(AddPiece) * (size_t)n_slots) || ensure(c, c->add_scr_cnt, sizeof(uint32_t) * (size_t)n_slots) ||
-            ensure(c, c->add_scr_off, sizeof(uint64_t) * (size_t)n_slots) || ensure(c, c->add_new_cnt, sizeof(uint32_t) * (size_t)n_slots) ||
-            ensure(c, c->add_new_off, sizeof(uint64_t) * (size_t)n_slots) || ensure(c, c->add_text, sizeof(uint32_t) * (size_t)n_slots) ||
-            ensure(c, c->add_bad, sizeof(uint32_t) * (size_t)(n_lines + 1)) || ensure(c, c->add_part, sizeof(uint64_t) * (size_t)(n_sblocks + 1)))
-            return PAFFY_E_HIP;
-        /* item words + passed-through ops, and the new 4-byte ops: about 2.4 and 2.9 bytes per byte of text for 2 %-divergent sequences; a
-           batch that needs more is encoded again with what it asked for (the totals come back with the plan's one synchronisation) */
-        size_t scr_words = std::max<size_t>(c->add_scratch.cap / 4, (size_t)len + ((size_t)1 << 20)), new_words = std::max<size_t>(c->add_new_ops.cap / 4, (size_t)len + ((size_t)1 << 20));
-        for (int attempt = 0;; attempt++) {
-            if (ensure(c, c->add_scratch, 4 * scr_words) || ensure(c, c->add_new_ops, 4 * new_words)) return PAFFY_E_HIP;
-            AddParams ap;
+/* the offsets of the lines and the emit order (long lines first): the scan rides along, one host synchronisation per plan in the usual case */
+static int post_scans(paffy_hip_ctx *c, uint32_t n_lines) {
+    KParams &kp = c->kp;
+    const uint32_t n_blocks = (n_lines + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    if (ensure(c, c->scan_part, sizeof(int64_t) * 2 * (size_t)n_blocks)) return PAFFY_E_HIP;
+    LAUNCH(c, "k_scan_part", k_scan_part, dim3(n_blocks), dim3(PAFFY_NT), 0, kp.out_len, kp.out_rows, n_lines,
+           static_cast<int64_t *>(c->out_off.p), static_cast<int64_t *>(c->scan_part.p), kp.info);
+    LAUNCH(c, "k_scan_fix", k_scan_fix, dim3(n_blocks), dim3(PAFFY_NT), 0, n_lines, n_blocks, static_cast<int64_t *>(c->out_off.p),
+           static_cast<const int64_t *>(c->scan_part.p), kp.info);
+    if (ensure(c, c->emit_order, sizeof(uint32_t) * (size_t)n_lines)) return PAFFY_E_HIP;
+    if (ensure(c, c->order_cnt, sizeof(uint32_t) * 2 * ORDER_CLASSES)) return PAFFY_E_HIP;
+    uint32_t *cnt = static_cast<uint32_t *>(c->order_cnt.p);
+    HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint32_t) * 2 * ORDER_CLASSES, c->stream));
+    const uint32_t g = (n_lines + PAFFY_NT - 1) / PAFFY_NT;
+    LAUNCH(c, "k_order_count", k_order_count, dim3(g), dim3(PAFFY_NT), 0, kp.out_len, n_lines, 14u, cnt);
+    LAUNCH(c, "k_order_scatter", k_order_scatter, dim3(g), dim3(PAFFY_NT), 0, kp.out_len, n_lines, 14u, cnt, cnt + ORDER_CLASSES,
+           static_cast<uint32_t *>(c->emit_order.p));
+    kp.emit_order = static_cast<const uint32_t *>(c->emit_order.p);
+    return 0;
+}
+
+static FlatParams flat_params(const paffy_hip_ctx *c, uint32_t items_mode) {
+    const KParams &kp = c->kp;
+    FlatParams fp;
+    fp.in = kp.in;
+    fp.in_len = kp.in_len;
+    fp.meta = kp.meta;
+    fp.chunk_rec = static_cast<const uint32_t *>(c->flat_chunks.p);
+    fp.n_chunk_slots = c->flat_chunk_slots;
+    fp.nd = static_cast<const uint16_t *>(c->flat_nd.p);
+    fp.sums = static_cast<PieceSum *>(c->flat_sums.p);
+    fp.ops_mirror = kp.ops_mirror;
+    fp.info = kp.info;
+    fp.items_mode = items_mode;
+    return fp;
+}
+
+/* `paffy add_mismatches` alone: the flat parse, then the encoder on its pieces, repeated with more scratch while a batch asks for more.
+   *need_records: the encoder left records to the record kernels. */
+static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records) {
+    KParams &kp = c->kp;
+    const uint32_t len = kp.in_len;
+    const FlatParams fp = flat_params(c, 1u);
+    LAUNCH(c, "k_flat_parse", k_flat_parse<1u>, dim3(2048), dim3(64 * FLAT_PARSE_WAVES), 0, fp);
+    const uint32_t n_slots = c->flat_piece_slots, n_sblocks = (n_slots + SCAN32_BLOCK - 1) / SCAN32_BLOCK;
+    if (ensure(c, c->add_pieces, sizeof(AddPiece) * (size_t)n_slots) || ensure(c, c->add_scr_cnt, sizeof(uint32_t) * (size_t)n_slots) ||
+        ensure(c, c->add_scr_off, sizeof(uint64_t) * (size_t)n_slots) || ensure(c, c->add_new_cnt, sizeof(uint32_t) * (size_t)n_slots) ||
+        ensure(c, c->add_new_off, sizeof(uint64_t) * (size_t)n_slots) || ensure(c, c->add_text, sizeof(uint32_t) * (size_t)n_slots) ||
+        ensure(c, c->add_bad, sizeof(uint32_t) * (size_t)(n_lines + 1)) || ensure(c, c->add_part, sizeof(uint64_t) * (size_t)(n_sblocks + 1)))
+        return PAFFY_E_HIP;
+    /* item words + passed-through ops, and the new 4-byte ops: about 2.4 and 2.9 bytes per byte of text for 2 %-divergent sequences; a
+       batch that needs more is encoded again with what it asked for (the totals come back with the plan's one synchronisation) */
+    size_t scr_words = std::max<size_t>(c->add_scratch.cap / 4, (size_t)len + ((size_t)1 << 20)), new_words = std::max<size_t>(c->add_new_ops.cap / 4, (size_t)len + ((size_t)1 << 20));
+    for (int attempt = 0;; attempt++) {
+        if (ensure(c, c->add_scratch, 4 * scr_words) || ensure(c, c->add_new_ops, 4 * new_words)) return PAFFY_E_HIP;
+        AddParams ap;
+        ap.P = kp;
+        ap.sums = fp.sums;
+        ap.pieces = static_cast<AddPiece *>(c->add_pieces.p);
+        ap.n_piece_slots = n_slots;
+        ap.scr_cnt = static_cast<uint32_t *>(c->add_scr_cnt.p);
+        ap.scr_off = static_cast<const uint64_t *>(c->add_scr_off.p);
+        ap.scratch = static_cast<uint32_t *>(c->add_scratch.p);
+        ap.scr_cap = c->add_scratch.cap / 4;
+        ap.new_cnt = static_cast<uint32_t *>(c->add_new_cnt.p);
+        ap.new_off = static_cast<const uint64_t *>(c->add_new_off.p);
+        ap.new_ops = static_cast<uint32_t *>(c->add_new_ops.p);
+        ap.new_cap = c->add_new_ops.cap / 4;
+        ap.text_cnt = static_cast<uint32_t *>(c->add_text.p);
+        ap.rec_bad = static_cast<uint32_t *>(c->add_bad.p);
+        ap.flat_done = static_cast<uint8_t *>(c->flat_done.p);
+        { /* segments of the lines that become more than PAFFY_ROWS_MAX_OPS ops */
+            const size_t items_cap = new_words / (PAFFY_ROWS_MAX_OPS / 4u) + ((size_t)len >> 14) + 64;
+            if (ensure(c, c->flat_items, sizeof(EmitItem) * items_cap)) return PAFFY_E_HIP;
+            kp.items = static_cast<EmitItem *>(c->flat_items.p);
+            kp.items_cap = (uint32_t)items_cap;
             ap.P = kp;
-            ap.sums = fp.sums;
-            ap.pieces = static_cast<AddPiece *>(c->add_pieces.p);
-            ap.n_piece_slots = n_slots;
-            ap.scr_cnt = static_cast<uint32_t *>(c->add_scr_cnt.p);
-            ap.scr_off = static_cast<const uint64_t *>(c->add_scr_off.p);
-            ap.scratch = static_cast<uint32_t *>(c->add_scratch.p);
-            ap.scr_cap = c->add_scratch.cap / 4;
-            ap.new_cnt = static_cast<uint32_t *>(c->add_new_cnt.p);
-            ap.new_off = static_cast<const uint64_t *>(c->add_new_off.p);
-            ap.new_ops = static_cast<uint32_t *>(c->add_new_ops.p);
-            ap.new_cap = c->add_new_ops.cap / 4;
-            ap.text_cnt = static_cast<uint32_t *>(c->add_text.p);
-            ap.rec_bad = static_cast<uint32_t *>(c->add_bad.p);
-            ap.flat_done = static_cast<uint8_t *>(c->flat_done.p);
-            { /* segments of the lines that become more than PAFFY_ROWS_MAX_OPS ops */
-                const size_t items_cap = new_words / (PAFFY_ROWS_MAX_OPS / 4u) + ((size_t)len >> 14) + 64;
-                if (ensure(c, c->flat_items, sizeof(EmitItem) * items_cap)) return PAFFY_E_HIP;
-                kp.items = static_cast<EmitItem *>(c->flat_items.p);
-                kp.items_cap = (uint32_t)items_cap;
-                ap.P = kp;
-            }
-            HIPCHK(c, hipMemsetAsync(c->add_pieces.p, 0xff, sizeof(AddPiece) * (size_t)n_slots, c->stream)); /* rec = FLAT_NO_CHUNK */
-            HIPCHK(c, hipMemsetAsync(c->add_scr_cnt.p, 0, sizeof(uint32_t) * (size_t)n_slots, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->add_new_cnt.p, 0, sizeof(uint32_t) * (size_t)n_slots, c->stream));
-            LAUNCH(c, "k_add_prep", k_add_prep, dim3((n_lines + 255) / 256), dim3(256), 0, ap);
-            LAUNCH(c, "k_scan32_part", k_scan32_part, dim3(n_sblocks), dim3(256), 0, ap.scr_cnt, n_slots, static_cast<uint64_t *>(c->add_scr_off.p), static_cast<uint64_t *>(c->add_part.p));
-            LAUNCH(c, "k_scan32_fix", k_scan32_fix, dim3(n_sblocks), dim3(256), 0, n_slots, n_sblocks, static_cast<uint64_t *>(c->add_scr_off.p), static_cast<const uint64_t *>(c->add_part.p),
-                   reinterpret_cast<uint64_t *>(&static_cast<DevInfo *>(c->info.p)->add_scr_total));
-            LAUNCH(c, "k_add_count", k_add_count, dim3(2048), dim3(64 * ADD_WAVES), 0, ap);
-            LAUNCH(c, "k_scan32_part", k_scan32_part, dim3(n_sblocks), dim3(256), 0, ap.new_cnt, n_slots, static_cast<uint64_t *>(c->add_new_off.p), static_cast<uint64_t *>(c->add_part.p));
-            LAUNCH(c, "k_scan32_fix", k_scan32_fix, dim3(n_sblocks), dim3(256), 0, n_slots, n_sblocks, static_cast<uint64_t *>(c->add_new_off.p), static_cast<const uint64_t *>(c->add_part.p),
-                   reinterpret_cast<uint64_t *>(&static_cast<DevInfo *>(c->info.p)->add_new_total));
-            LAUNCH(c, "k_add_fill", k_add_fill, dim3(2048), dim3(64 * ADD_WAVES), 0, ap);
-            LAUNCH(c, "k_add_final", k_add_final, dim3((n_lines + 255) / 256), dim3(256), 0, ap);
-            kp.new_ops = ap.new_ops;
-            if (post_scans()) return PAFFY_E_HIP;
-            if (fetch_info(c)) return PAFFY_E_HIP;
-            kp.n_items = c->h_info->n_items;
-            if (c->h_info->add_scr_total <= ap.scr_cap && c->h_info->add_new_total <= ap.new_cap) break;
-            if (attempt == 2) {
-                c->last_error = "add_mismatches: the scratch demand kept growing";
-                return PAFFY_E_HIP;
-            }
-            scr_words = std::max<size_t>(scr_words, (size_t)c->h_info->add_scr_total + ((size_t)c->h_info->add_scr_total >> 3) + 1024);
-            new_words = std::max<size_t>(new_words, (size_t)c->h_info->add_new_total + ((size_t)c->h_info->add_new_total >> 3) + 1024);
-            DevInfo z = *c->h_info; /* once more: nothing of the first try counts */
-            z.flat_legacy = 0;
-            z.n_items = 0;
-            z.out_bytes = z.out_rows = 0;
-            HIPCHK(c, hipMemcpyAsync(c->info.p, &z, sizeof(z), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        need_legacy = c->h_info->flat_legacy > 0;
-        c->flat_left = c->h_info->flat_legacy;
-        for (int k = 0; k < 16; k++) c->flat_reasons[k] = 0;
-        kp.flat_done = static_cast<const uint8_t *>(c->flat_done.p);
-    } else if (flat && n_lines > 0) {
-        FlatParams fp;
-        fp.in = in;
-        fp.in_len = len;
-        fp.meta = kp.meta;
-        fp.chunk_rec = static_cast<const uint32_t *>(c->flat_chunks.p);
-        fp.n_chunk_slots = c->flat_chunk_slots;
-        fp.nd = static_cast<const uint16_t *>(c->flat_nd.p);
-        fp.sums = static_cast<PieceSum *>(c->flat_sums.p);
-        fp.ops_mirror = kp.ops_mirror;
-        fp.info = kp.info;
-        fp.items_mode = has_stats ? 2u : 0u;
-        /* persistent waves over the chunks: eight workgroups of four waves per CU */
-        if (has_stats) LAUNCH(c, "k_flat_parse", k_flat_parse<2u>, dim3(2048), dim3(64 * FLAT_PARSE_WAVES), 0, fp);
-        else LAUNCH(c, "k_flat_parse", k_flat_parse<0u>, dim3(2048), dim3(64 * FLAT_PARSE_WAVES), 0, fp);
-        /* segments of the shatter records too long for one wave of the row writer: a record of more than PAFFY_ROWS_MAX_OPS ops has
-           2 x that many cigar bytes at least, a segment holds half that many ops */
-        const size_t items_cap = ((size_t)len >> 15) + ((size_t)len >> 16) + 16;
-        if (ensure(c, c->flat_items, sizeof(EmitItem) * items_cap)) return PAFFY_E_HIP;
-        kp.items = static_cast<EmitItem *>(c->flat_items.p);
-        kp.items_cap = (uint32_t)items_cap;
-        /* the constant pieces of a shatter record's rows, 144 bytes per record (lane_row_pieces, flat_kernel.h) */
-        static const bool no_pieces = getenv("PAFFY_NO_ROW_PIECES") != nullptr;
-        const bool has_shatter = [&] {
-            for (int32_t i = 0; i < n_stages; i++)
-                if (stages[i].kind == PAFFY_SHATTER) return true;
-            return false;
-        }();
-        if (has_shatter && !no_pieces) {
-            if (ensure(c, c->flat_pieces, FLAT_ROW_PIECES_BYTES * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-            kp.row_pieces = static_cast<uint8_t *>(c->flat_pieces.p);
-        }
-        FlatSizeParams fs;
-        fs.P = kp;
-        fs.sums = fp.sums;
-        fs.flat_done = static_cast<uint8_t *>(c->flat_done.p);
-        if (ensure(c, c->flat_rec, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
-        fs.defer = static_cast<uint32_t *>(c->flat_rec.p);
-        /* one lane per record for the records that need little, one wave per record for the rest (a list whose length only the device knows) */
-        if (fixed_last) { /* one wave per record for all of them */
-            LAUNCH(c, "k_flat_size", k_flat_size<true>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
-        } else {
-            LAUNCH(c, "k_flat_lane", k_flat_lane, dim3((n_lines + 255) / 256), dim3(256), 0, fs);
-            LAUNCH(c, "k_flat_size", k_flat_size<false>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
-        }
-        if (post_scans()) return PAFFY_E_HIP;
+        HIPCHK(c, hipMemsetAsync(c->add_pieces.p, 0xff, sizeof(AddPiece) * (size_t)n_slots, c->stream)); /* rec = FLAT_NO_CHUNK */
+        HIPCHK(c, hipMemsetAsync(c->add_scr_cnt.p, 0, sizeof(uint32_t) * (size_t)n_slots, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->add_new_cnt.p, 0, sizeof(uint32_t) * (size_t)n_slots, c->stream));
+        LAUNCH(c, "k_add_prep", k_add_prep, dim3((n_lines + 255) / 256), dim3(256), 0, ap);
+        LAUNCH(c, "k_scan32_part", k_scan32_part, dim3(n_sblocks), dim3(256), 0, ap.scr_cnt, n_slots, static_cast<uint64_t *>(c->add_scr_off.p), static_cast<uint64_t *>(c->add_part.p));
+        LAUNCH(c, "k_scan32_fix", k_scan32_fix, dim3(n_sblocks), dim3(256), 0, n_slots, n_sblocks, static_cast<uint64_t *>(c->add_scr_off.p), static_cast<const uint64_t *>(c->add_part.p),
+               reinterpret_cast<uint64_t *>(&static_cast<DevInfo *>(c->info.p)->add_scr_total));
+        LAUNCH(c, "k_add_count", k_add_count, dim3(2048), dim3(64 * ADD_WAVES), 0, ap);
+        LAUNCH(c, "k_scan32_part", k_scan32_part, dim3(n_sblocks), dim3(256), 0, ap.new_cnt, n_slots, static_cast<uint64_t *>(c->add_new_off.p), static_cast<uint64_t *>(c->add_part.p));
+        LAUNCH(c, "k_scan32_fix", k_scan32_fix, dim3(n_sblocks), dim3(256), 0, n_slots, n_sblocks, static_cast<uint64_t *>(c->add_new_off.p), static_cast<const uint64_t *>(c->add_part.p),
+               reinterpret_cast<uint64_t *>(&static_cast<DevInfo *>(c->info.p)->add_new_total));
+        LAUNCH(c, "k_add_fill", k_add_fill, dim3(2048), dim3(64 * ADD_WAVES), 0, ap);
+        LAUNCH(c, "k_add_final", k_add_final, dim3((n_lines + 255) / 256), dim3(256), 0, ap);
+        kp.new_ops = ap.new_ops;
+        if (post_scans(c, n_lines)) return PAFFY_E_HIP;
         if (fetch_info(c)) return PAFFY_E_HIP;
-        flat_g_count = c->h_info->g_count;
         kp.n_items = c->h_info->n_items;
-        need_legacy = c->h_info->flat_legacy > 0;
-        c->flat_left = c->h_info->flat_legacy;
-        for (int k = 0; k < 16; k++) c->flat_reasons[k] = c->h_info->flat_reason[k];
-        kp.flat_done = static_cast<const uint8_t *>(c->flat_done.p);
-        if (kp.rec_stats && !need_legacy) { /* the batch's sums (the record kernels' launch chain does this when it runs) */
+        if (c->h_info->add_scr_total <= ap.scr_cap && c->h_info->add_new_total <= ap.new_cap) break;
+        if (attempt == 2) {
+            c->last_error = "add_mismatches: the scratch demand kept growing";
+            return PAFFY_E_HIP;
+        }
+        scr_words = std::max<size_t>(scr_words, (size_t)c->h_info->add_scr_total + ((size_t)c->h_info->add_scr_total >> 3) + 1024);
+        new_words = std::max<size_t>(new_words, (size_t)c->h_info->add_new_total + ((size_t)c->h_info->add_new_total >> 3) + 1024);
+        DevInfo z = *c->h_info; /* once more: nothing of the first try counts */
+        z.flat_legacy = 0;
+        z.n_items = 0;
+        z.out_bytes = z.out_rows = 0;
+        HIPCHK(c, hipMemcpyAsync(c->info.p, &z, sizeof(z), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    *need_records = c->h_info->flat_legacy > 0;
+    c->flat_left = c->h_info->flat_legacy;
+    kp.flat_done = static_cast<const uint8_t *>(c->flat_done.p);
+    return 0;
+}
+
+/* the flat pass: *need_records as above; *g_count = the records it left to the four-wave writers */
+static int plan_flat(paffy_hip_ctx *c, const StageClass &s, uint32_t n_lines, bool *need_records, uint32_t *g_count) {
+    KParams &kp = c->kp;
+    const uint32_t len = kp.in_len;
+    const FlatParams fp = flat_params(c, s.has_stats ? 2u : 0u);
+    /* persistent waves over the chunks: eight workgroups of four waves per CU */
+    if (s.has_stats) LAUNCH(c, "k_flat_parse", k_flat_parse<2u>, dim3(2048), dim3(64 * FLAT_PARSE_WAVES), 0, fp);
+    else LAUNCH(c, "k_flat_parse", k_flat_parse<0u>, dim3(2048), dim3(64 * FLAT_PARSE_WAVES), 0, fp);
+    /* segments of the shatter records too long for one wave of the row writer: a record of more than PAFFY_ROWS_MAX_OPS ops has
+       2 x that many cigar bytes at least, a segment holds half that many ops */
+    const size_t items_cap = ((size_t)len >> 15) + ((size_t)len >> 16) + 16;
+    if (ensure(c, c->flat_items, sizeof(EmitItem) * items_cap)) return PAFFY_E_HIP;
+    kp.items = static_cast<EmitItem *>(c->flat_items.p);
+    kp.items_cap = (uint32_t)items_cap;
+    if (s.has_shatter) { /* the constant pieces of a shatter record's rows, 144 bytes per record (lane_row_pieces, flat_kernel.h) */
+        if (ensure(c, c->flat_pieces, FLAT_ROW_PIECES_BYTES * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
+        kp.row_pieces = static_cast<uint8_t *>(c->flat_pieces.p);
+    }
+    FlatSizeParams fs;
+    fs.P = kp;
+    fs.sums = fp.sums;
+    fs.flat_done = static_cast<uint8_t *>(c->flat_done.p);
+    if (ensure(c, c->flat_rec, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
+    fs.defer = static_cast<uint32_t *>(c->flat_rec.p);
+    /* one lane per record for the records that need little, one wave per record for the rest (a list whose length only the device knows) */
+    if (s.fixed_last) { /* one wave per record for all of them */
+        LAUNCH(c, "k_flat_size", k_flat_size<true>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
+    } else {
+        LAUNCH(c, "k_flat_lane", k_flat_lane, dim3((n_lines + 255) / 256), dim3(256), 0, fs);
+        LAUNCH(c, "k_flat_size", k_flat_size<false>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
+    }
+    if (post_scans(c, n_lines)) return PAFFY_E_HIP;
+    if (fetch_info(c)) return PAFFY_E_HIP;
+    *g_count = c->h_info->g_count;
+    kp.n_items = c->h_info->n_items;
+    *need_records = c->h_info->flat_legacy > 0;
+    c->flat_left = c->h_info->flat_legacy;
+    for (int k = 0; k < 16; k++) c->flat_reasons[k] = c->h_info->flat_reason[k];
+    kp.flat_done = static_cast<const uint8_t *>(c->flat_done.p);
+    if (kp.rec_stats && !*need_records) { /* the batch's sums (the record kernels' launch chain does this when it runs) */
+        LAUNCH(c, "k_stats_reduce", k_stats_reduce, dim3(std::min<uint32_t>(512u, (n_lines + PAFFY_NT - 1) / PAFFY_NT)), dim3(PAFFY_NT), 0, kp.rec_stats, n_lines,
+               static_cast<DevInfo *>(c->info.p)->stats);
+        if (fetch_info(c)) return PAFFY_E_HIP;
+    }
+    return 0;
+}
+
+/* the record kernels, sizing again with a larger arena while a batch asks for more; lvl0_long: the batch started at the longer first
+   store level; flat_g_count: the records the flat pass left to the four-wave writers */
+static int plan_records(paffy_hip_ctx *c, const StageClass &s, uint32_t n_lines, bool lvl0_long, uint32_t flat_g_count) {
+    KParams &kp = c->kp;
+    if (s.flat == FLAT_MODE_NONE) { /* launch order of the sizing workgroups: long cigars first (out_len is scratch until the sizing pass fills it) */
+        if (ensure(c, c->emit_order, sizeof(uint32_t) * (size_t)n_lines)) return PAFFY_E_HIP;
+        if (ensure(c, c->order_cnt, sizeof(uint32_t) * 2 * ORDER_CLASSES)) return PAFFY_E_HIP;
+        uint32_t *cnt = static_cast<uint32_t *>(c->order_cnt.p);
+        HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint32_t) * 2 * ORDER_CLASSES, c->stream));
+        const uint32_t g = (n_lines + PAFFY_NT - 1) / PAFFY_NT;
+        LAUNCH(c, "k_cigar_bytes", k_cigar_bytes, dim3(g), dim3(PAFFY_NT), 0, kp.meta, n_lines, kp.out_len);
+        LAUNCH(c, "k_order_count", k_order_count, dim3(g), dim3(PAFFY_NT), 0, kp.out_len, n_lines, 9u, cnt);
+        LAUNCH(c, "k_order_scatter", k_order_scatter, dim3(g), dim3(PAFFY_NT), 0, kp.out_len, n_lines, 9u, cnt, cnt + ORDER_CLASSES,
+               static_cast<uint32_t *>(c->emit_order.p));
+        kp.size_order = static_cast<const uint32_t *>(c->emit_order.p); /* any permutation serves a repeated sizing pass too */
+    }
+    /* add_mismatches keeps one word per 16 columns and the new 4-byte ops of every record in the arena: about eight times
+       the text for 2 %-divergent sequences; start there instead of finding out through repeated passes */
+    if (s.need_seqs && ensure(c, c->arena, (size_t)kp.in_len * 8 + ((size_t)8 << 20))) return PAFFY_E_HIP;
+    const int max_attempts = 6;
+    for (int attempt = 0; attempt < max_attempts; attempt++) {
+        kp.arena = static_cast<uint64_t *>(c->arena.p);
+        kp.arena_cap = c->arena.cap / 8;
+        kp.ops_cap = PAFFY_OPS_CAP;
+        kp.next_cap = 0;
+        kp.level = 0;
+        /* records with at most WAVE_MAX_BYTES cigar bytes (about WAVE_OPS_CAP ops at three bytes per op) are sized one wave per record;
+           denser cigars of that length overflow the wave's store and are redone by the four-wave build. add_mismatches rebuilds the op
+           array: when a stage follows it the new array must fit the store, so only pipes that end with it take the one-wave build. */
+        kp.wave_max_bytes = s.add_not_last ? 0u : WAVE_MAX_BYTES;
+        {
+            int rc = size_records_for(c, s.size_mask, kp, n_lines);
+            if (rc) return rc;
+        }
+        LAUNCH(c, "k_arena_size", k_arena_size, dim3(2048), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES, kp);
+        if (kp.rec_stats)
             LAUNCH(c, "k_stats_reduce", k_stats_reduce, dim3(std::min<uint32_t>(512u, (n_lines + PAFFY_NT - 1) / PAFFY_NT)), dim3(PAFFY_NT), 0, kp.rec_stats, n_lines,
                    static_cast<DevInfo *>(c->info.p)->stats);
-            if (fetch_info(c)) return PAFFY_E_HIP;
+        if (post_scans(c, n_lines)) return PAFFY_E_HIP;
+        if (fetch_info(c)) return PAFFY_E_HIP;
+        if (c->h_info->arena_used <= kp.arena_cap) {
+            if (lvl0_long && c->h_info->lvl0_over > 0) { /* denser cigars than the longer first level takes: back to the safe bound, for good */
+                c->lvl0_long_ok = false;
+                c->lvl0_long_off = true;
+            } else if (kp.lvl0_long_bytes) { /* the safe bound was in force and the second level kept count */
+                c->lvl0_long_ok = c->h_info->lvl0_probe_dense == 0;
+            }
+            return 0;
         }
+        /* arena too small: grow to the demand seen so far and redo the sizing pass */
+        /* a record that found no room stopped asking, so the demand seen is a lower bound: at least double what there was */
+        size_t need = (size_t)c->h_info->arena_used * 8 * 2;
+        if (need < c->arena.cap * 2) need = c->arena.cap * 2;
+        if (ensure(c, c->arena, need)) return PAFFY_E_HIP;
+        DevInfo z = *c->h_info;
+        z.arena_used = 0;
+        z.w_count = 0;
+        z.g_count = flat_g_count; /* the records the flat pass left to the four-wave writers stay counted */
+        z.b_count[1] = 0; /* b_count[0] was filled by k_header and stays */
+        for (int k = 0; k < 6; k++) z.stats[k] = 0;
+        z.first_err_key = ~0ull;
+        z.out_bytes = z.out_rows = 0;
+        HIPCHK(c, hipMemcpyAsync(c->info.p, &z, sizeof(z), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    if (n_lines > 0 && need_legacy) {
-        if (!flat) { /* launch order of the sizing workgroups: long cigars first (out_len is scratch until the sizing pass fills it) */
-            if (ensure(c, c->emit_order, sizeof(uint32_t) * (size_t)n_lines)) return PAFFY_E_HIP;
-            if (ensure(c, c->order_cnt, sizeof(uint32_t) * 2 * ORDER_CLASSES)) return PAFFY_E_HIP;
-            uint32_t *cnt = static_cast<uint32_t *>(c->order_cnt.p);
-            HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(uint32_t) * 2 * ORDER_CLASSES, c->stream));
-            const uint32_t g = (n_lines + PAFFY_NT - 1) / PAFFY_NT;
-            LAUNCH(c, "k_cigar_bytes", k_cigar_bytes, dim3(g), dim3(PAFFY_NT), 0, kp.meta, n_lines, kp.out_len);
-            LAUNCH(c, "k_order_count", k_order_count, dim3(g), dim3(PAFFY_NT), 0, kp.out_len, n_lines, 9u, cnt);
-            LAUNCH(c, "k_order_scatter", k_order_scatter, dim3(g), dim3(PAFFY_NT), 0, kp.out_len, n_lines, 9u, cnt, cnt + ORDER_CLASSES,
-                   static_cast<uint32_t *>(c->emit_order.p));
-            kp.size_order = static_cast<const uint32_t *>(c->emit_order.p); /* any permutation serves a repeated sizing pass too */
-        }
-        /* add_mismatches keeps one word per 16 columns and the new 4-byte ops of every record in the arena: about eight times
-           the text for 2 %-divergent sequences; start there instead of finding out through repeated passes */
-        if (need_seqs && ensure(c, c->arena, (size_t)len * 8 + ((size_t)8 << 20))) return PAFFY_E_HIP;
-        const int max_attempts = 6;
-        for (int attempt = 0; attempt < max_attempts; attempt++) {
-            kp.arena = static_cast<uint64_t *>(c->arena.p);
-            kp.arena_cap = c->arena.cap / 8;
-            /* fork: levels 1 and 2 (long cigars, queued by k_header) on the side stream, level 0 on the main one */
-            HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-            {
-                KParams k1 = kp;
-                k1.ops_cap = PAFFY_OPS_CAP_MID;
-                k1.next_cap = PAFFY_OPS_CAP_BIG;
-                k1.level = 1;
-                if (lean) hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_LEAN>, dim3(768), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_MID), c->side, k1);
-                else if (lean_add) hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_ADD>, dim3(768), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_MID), c->side, k1);
-                else if (sel) hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_SEL>, dim3(768), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_MID), c->side, k1);
-                else if (plain) hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_PLAIN>, dim3(768), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_MID), c->side, k1);
-                else hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_ALL>, dim3(768), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_MID), c->side, k1);
-                k1.ops_cap = PAFFY_OPS_CAP_BIG;
-                k1.next_cap = 0;
-                k1.level = 2;
-                if (lean) hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_LEAN>, dim3(256), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG), c->side, k1);
-                else if (lean_add) hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_ADD>, dim3(256), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG), c->side, k1);
-                else if (sel) hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_SEL>, dim3(256), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG), c->side, k1);
-                else if (plain) hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_PLAIN>, dim3(256), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG), c->side, k1);
-                else hipLaunchKernelGGL(k_size_lds_long<PAFFY_MASK_ALL>, dim3(256), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES_FOR(PAFFY_OPS_CAP_BIG), c->side, k1);
-                HIPCHK(c, hipGetLastError());
-                HIPCHK(c, hipEventRecord(c->ev_join, c->side));
-            }
-            kp.ops_cap = PAFFY_OPS_CAP;
-            kp.next_cap = 0;
-            kp.level = 0;
-            kp.wave_max_bytes = wave_bytes;
-            if (wave_bytes) { /* short cigars: one wave per record, sixteen records in flight per CU */
-                KParams kw = kp;
-                kw.ops_cap = wave_cap_env;
-                const size_t wlds = (size_t)wave_cap_env * 4 + PAFFY_HALO + 64 * 16 + 64 * 8 + 64;
-                if (lean) LAUNCH(c, "k_size_wave", g64::k_size_lds<PAFFY_MASK_LEAN>, dim3(n_lines), dim3(64), wlds + dbg_lds_pad(1), kw);
-                else if (lean_add) LAUNCH(c, "k_size_wave", g64::k_size_lds<PAFFY_MASK_ADD>, dim3(n_lines), dim3(64), wlds, kw);
-                else if (sel) LAUNCH(c, "k_size_wave", g64::k_size_lds<PAFFY_MASK_SEL>, dim3(n_lines), dim3(64), wlds, kw);
-                else if (plain) LAUNCH(c, "k_size_wave", g64::k_size_lds<PAFFY_MASK_PLAIN>, dim3(n_lines), dim3(64), wlds, kw);
-                else LAUNCH(c, "k_size_wave", g64::k_size_lds<PAFFY_MASK_ALL>, dim3(n_lines), dim3(64), wlds, kw);
-            }
-            if (lean) LAUNCH(c, "k_size_lds", k_size_lds<PAFFY_MASK_LEAN>, dim3(n_lines), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES + dbg_lds_pad(2), kp);
-            else if (lean_add) LAUNCH(c, "k_size_lds", k_size_lds<PAFFY_MASK_ADD>, dim3(n_lines), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES, kp);
-            else if (sel) LAUNCH(c, "k_size_lds", k_size_lds<PAFFY_MASK_SEL>, dim3(n_lines), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES, kp);
-            else if (plain) LAUNCH(c, "k_size_lds", k_size_lds<PAFFY_MASK_PLAIN>, dim3(n_lines), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES, kp);
-            else LAUNCH(c, "k_size_lds", k_size_lds<PAFFY_MASK_ALL>, dim3(n_lines), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES, kp);
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0)); /* join */
-            LAUNCH(c, "k_arena_size", k_arena_size, dim3(2048), dim3(PAFFY_NT), PAFFY_SIZE_LDS_BYTES, kp);
-            if (kp.rec_stats)
-                LAUNCH(c, "k_stats_reduce", k_stats_reduce, dim3(std::min<uint32_t>(512u, (n_lines + PAFFY_NT - 1) / PAFFY_NT)), dim3(PAFFY_NT), 0, kp.rec_stats, n_lines,
-                       static_cast<DevInfo *>(c->info.p)->stats);
-            if (post_scans()) return PAFFY_E_HIP;
-            if (fetch_info(c)) return PAFFY_E_HIP;
-            if (c->h_info->arena_used <= kp.arena_cap) {
-                if (lvl0_long && c->h_info->lvl0_over > 0) { /* denser cigars than the longer first level takes: back to the safe bound, for good */
-                    c->lvl0_long_ok = false;
-                    c->lvl0_long_off = true;
-                } else if (kp.lvl0_long_bytes) { /* the safe bound was in force and the second level kept count */
-                    c->lvl0_long_ok = c->h_info->lvl0_probe_dense == 0;
-                }
-                break;
-            }
-            /* arena too small: grow to the demand seen so far and redo the sizing pass */
-            /* a record that found no room stopped asking, so the demand seen is a lower bound: at least double what there was */
-            size_t need = (size_t)c->h_info->arena_used * 8 * 2;
-            if (need < c->arena.cap * 2) need = c->arena.cap * 2;
-            if (ensure(c, c->arena, need)) return PAFFY_E_HIP;
-            DevInfo z = *c->h_info;
-            z.arena_used = 0;
-            z.w_count = 0;
-            z.g_count = flat_g_count; /* the records the flat pass left to the four-wave writers stay counted */
-            z.b_count[1] = 0; /* b_count[0] was filled by k_header and stays */
-            for (int k = 0; k < 6; k++) z.stats[k] = 0;
-            z.first_err_key = ~0ull;
-            z.out_bytes = z.out_rows = 0;
-            HIPCHK(c, hipMemcpyAsync(c->info.p, &z, sizeof(z), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (attempt == max_attempts - 1) {
-                c->last_error = "arena demand kept growing";
-                return PAFFY_E_HIP;
-            }
-        }
-    } else if (n_lines == 0 && fetch_info(c)) {
-        return PAFFY_E_HIP;
-    }
+    c->last_error = "arena demand kept growing";
+    return PAFFY_E_HIP;
+}
+
+/* the plan's totals and its first failing record, from the DevInfo fetched last */
+static int plan_finish(paffy_hip_ctx *c, uint32_t n_lines, paffy_plan_info *info) {
     if (c->profile) prof_collect(c);
     if (c->h_info->internal) {
         char buf[128];
@@ -1862,6 +1846,53 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
     return 0;
 }
 
+int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages, const void *d_in, int64_t in_len,
+                   paffy_plan_info *info) {
+    if (!c || !info || (n_stages > 0 && !stages) || n_stages < 0 || n_stages > PAFFY_MAX_STAGES) return PAFFY_E_ARG;
+    if (in_len < 0 || in_len >= (1ll << 31) - 64 || (in_len > 0 && !d_in) || (reinterpret_cast<uintptr_t>(d_in) & 15)) return PAFFY_E_ARG;
+    StageClass s;
+    int rc = classify_stages(c, stages, n_stages, s);
+    if (rc) return rc;
+    if (s.upconvert) return upconvert_plan(c, d_in, in_len, (s.nocheck_mask & 1u) == 0, info);
+    plan_begin(c, PLAN_RECORDS, in_len, info);
+    if (in_len == 0) {
+        c->planned = true;
+        return 0;
+    }
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    const uint32_t len = (uint32_t)in_len;
+    /* Cigars of more than 2 x lvl0_max bytes start at the second store level (k_header queues them), whose 64 KB of ops leave a CU two
+       workgroups: on cfg3 / cfg4 the 7 % of the records there cost as much kernel time as all the others. Two bytes per op is the bound
+       that can never overflow the first level's 8 192-op store, but a cigar of the usual density (2.5-3 bytes per op) fits it up to about
+       LVL0_LONG_BYTES. So a context starts with the safe bound and lets the second level count the records that would have overflowed the
+       longer one (DevInfo::lvl0_probe_dense); a batch without any switches the following batches to the longer first level (cfg4 12.23 ->
+       11.72 ms per step, cfg3 -1.2 to -1.6 %), and the first record that does overflow there (it goes to the arena class: slow, correct)
+       switches the context back for good. */
+    static_assert(LVL0_LONG_BYTES > 2u * PAFFY_OPS_CAP, "the longer first level must be longer than the safe bound");
+    const bool lvl0_long = !s.add_not_last && c->lvl0_long_ok;
+    const uint32_t lvl0_max = s.add_not_last ? PAFFY_OPS_CAP * 5 / 8 : (lvl0_long ? LVL0_LONG_BYTES / 2u : PAFFY_OPS_CAP);
+    uint32_t n_lines = 0;
+    rc = index_and_parse(c, in, len, &n_lines, lvl0_max, s.flat != FLAT_MODE_NONE);
+    if (rc) return rc;
+    if ((s.fix_query || s.fix_target) && n_lines > 0)
+        LAUNCH(c, "k_dechunk", k_dechunk, dim3((n_lines + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, in, static_cast<RecMeta *>(c->meta.p), n_lines,
+               s.fix_query, s.fix_target);
+    c->kp.lvl0_max = lvl0_max;
+    c->kp.lvl0_long_bytes = (!s.add_not_last && !lvl0_long && !c->lvl0_long_off) ? LVL0_LONG_BYTES : 0u;
+    rc = record_params(c, s, in, len, n_lines);
+    if (rc) return rc;
+    if (n_lines == 0) {
+        rc = fetch_info(c);
+    } else {
+        bool need_records = true;
+        uint32_t flat_g_count = 0;
+        if (s.flat == FLAT_MODE_ADD) rc = plan_flat_add(c, n_lines, &need_records);
+        else if (s.flat == FLAT_MODE_PASS) rc = plan_flat(c, s, n_lines, &need_records, &flat_g_count);
+        if (!rc && need_records) rc = plan_records(c, s, n_lines, lvl0_long, flat_g_count);
+    }
+    if (rc) return rc;
+    return plan_finish(c, n_lines, info);
+}
 
 } /* extern "C" */
 
@@ -1874,6 +1905,11 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
 static CovState &cov_state(paffy_hip_ctx *c) {
     if (!c->cov) c->cov = new CovState();
     return *c->cov;
+}
+static int64_t cov_in_bytes(const CovState &S) {
+    int64_t n = 0;
+    for (const CovBatch &b : S.batches) n += b.len;
+    return n;
 }
 static ChainState &chain_state(paffy_hip_ctx *c) {
     if (!c->chain) c->chain = new ChainState();
@@ -1947,14 +1983,7 @@ int paffy_hip_tile_add(paffy_hip_ctx *c, const void *d_in, int64_t in_len) {
 int paffy_hip_tile_run(paffy_hip_ctx *c, paffy_plan_info *info) {
     if (!c || !info) return PAFFY_E_ARG;
     CovState &S = cov_state(c);
-    c->planned = false;
-    c->plan_is_tile = true;
-    c->plan_is_bed = false;
-    memset(info, 0, sizeof(*info));
-    memset(&c->plan, 0, sizeof(c->plan));
-    memset(&c->kp, 0, sizeof(c->kp));
-    c->line_n = 0;
-    for (const CovBatch &b : S.batches) c->plan.in_bytes += b.len;
+    plan_begin(c, PLAN_LINES, cov_in_bytes(S), info);
     c->plan.n_records = (int64_t)S.n_rec;
     const uint64_t n = S.n_rec;
     if (n > 0) {
@@ -1998,14 +2027,7 @@ int paffy_hip_chain_add(paffy_hip_ctx *c, const void *d_in, int64_t in_len) {
 int paffy_hip_chain_run(paffy_hip_ctx *c, const paffy_chain_opts *opts, paffy_plan_info *info) {
     if (!c || !info || !opts) return PAFFY_E_ARG;
     CovState &S = cov_state(c);
-    c->planned = false;
-    c->plan_is_tile = true; /* the output is a line table, as for tile */
-    c->plan_is_bed = false;
-    memset(info, 0, sizeof(*info));
-    memset(&c->plan, 0, sizeof(c->plan));
-    memset(&c->kp, 0, sizeof(c->kp));
-    c->line_n = 0;
-    for (const CovBatch &b : S.batches) c->plan.in_bytes += b.len;
+    plan_begin(c, PLAN_LINES, cov_in_bytes(S), info); /* the output is a line table, as for tile */
     c->plan.n_records = (int64_t)S.n_rec;
     const uint64_t n = S.n_rec;
     if (n > 0) {
@@ -2389,7 +2411,7 @@ __global__ __launch_bounds__(PAFFY_NT) void k_tile_keys_out(const RecMeta *meta,
 }
 int64_t paffy_hip_tile_keys(paffy_hip_ctx *c, int64_t cap_lines, void *d_keys) {
     if (!c || !d_keys) return PAFFY_E_ARG;
-    if (!c->planned || !c->plan_is_tile || !c->cov) return PAFFY_E_STATE;
+    if (!c->planned || c->plan_kind != PLAN_LINES || !c->cov) return PAFFY_E_STATE;
     CovState &S = cov_state(c);
     const uint64_t n = c->line_n;
     if (c->line_meta != static_cast<const RecMeta *>(S.meta.p)) return PAFFY_E_STATE; /* a dedupe plan */
@@ -2402,16 +2424,7 @@ int64_t paffy_hip_tile_keys(paffy_hip_ctx *c, int64_t cap_lines, void *d_keys) {
 /* `paffy upconvert` (impl/paf_upconvert.c:144-156): index, header parse, k_upconvert, then the line writer of tile / dedupe (header + the
    cigar text as it was read) for every record in front of the first failing one */
 static int upconvert_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bool check, paffy_plan_info *info) {
-    c->planned = false;
-    c->plan_is_tile = true;
-    c->plan_is_bed = false;
-    c->flat_left = -1;
-    memset(info, 0, sizeof(*info));
-    memset(&c->plan, 0, sizeof(c->plan));
-    info->in_bytes = c->plan.in_bytes = in_len;
-    memset(&c->kp, 0, sizeof(c->kp));
-    c->tile_n = 0;
-    c->line_n = 0;
+    plan_begin(c, PLAN_LINES, in_len, info);
     if (in_len == 0) {
         c->planned = true;
         return 0;
@@ -2470,14 +2483,13 @@ static int upconvert_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bo
     if (c->profile) prof_collect(c);
     c->plan.out_bytes = total;
     c->plan.n_rows = nk;
-    c->tile_n = total ? nk : 0;
     c->line_batches = static_cast<const uint8_t *const *>(c->one_batch.p);
     c->line_meta = meta;
     c->line_names2 = static_cast<const uint8_t *>(c->up_names.p);
     c->line_order = static_cast<const uint32_t *>(c->tile_order.p);
     c->line_level = static_cast<const int64_t *>(c->tile_level.p);
     c->line_off = static_cast<const uint64_t *>(c->out_off.p);
-    c->line_n = c->tile_n;
+    c->line_n = total ? nk : 0;
     *info = c->plan;
     c->planned = true;
     return 0;
@@ -2567,13 +2579,7 @@ int paffy_hip_dedupe_reset(paffy_hip_ctx *c) {
 int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int check_inverse, paffy_plan_info *info) {
     if (!c || !info) return PAFFY_E_ARG;
     if (in_len < 0 || in_len >= (1ll << 31) - 64 || (in_len > 0 && !d_in) || (reinterpret_cast<uintptr_t>(d_in) & 15)) return PAFFY_E_ARG;
-    c->planned = false;
-    c->plan_is_tile = true; /* same writer as tile: header + the cigar text as it was read */
-    memset(info, 0, sizeof(*info));
-    memset(&c->plan, 0, sizeof(c->plan));
-    info->in_bytes = c->plan.in_bytes = in_len;
-    memset(&c->kp, 0, sizeof(c->kp));
-    c->tile_n = 0;
+    plan_begin(c, PLAN_LINES, in_len, info); /* same writer as tile: header + the cigar text as it was read */
     if (in_len == 0) {
         c->planned = true;
         return 0;
@@ -2640,14 +2646,13 @@ int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, in
     if (c->profile) prof_collect(c);
     c->plan.out_bytes = total;
     c->plan.n_rows = nk;
-    c->tile_n = total ? nk : 0;
     c->line_batches = static_cast<const uint8_t *const *>(c->one_batch.p);
     c->line_meta = static_cast<const RecMeta *>(c->meta.p);
     c->line_names2 = nullptr;
     c->line_order = static_cast<const uint32_t *>(c->tile_order.p);
     c->line_level = static_cast<const int64_t *>(c->tile_level.p);
     c->line_off = static_cast<const uint64_t *>(c->out_off.p);
-    c->line_n = c->tile_n;
+    c->line_n = total ? nk : 0;
     *info = c->plan;
     c->planned = true;
     return 0;
@@ -2655,7 +2660,7 @@ int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, in
 
 int64_t paffy_hip_plan_rows(paffy_hip_ctx *c, int64_t cap, uint32_t *record, int64_t *out_off) {
     if (!c || !record || !out_off) return PAFFY_E_ARG;
-    if (!c->planned || !c->plan_is_tile) return PAFFY_E_STATE;
+    if (!c->planned || c->plan_kind != PLAN_LINES) return PAFFY_E_STATE;
     const int64_t n = (int64_t)c->line_n;
     if (cap < n + 1) return PAFFY_E_CAPACITY;
     if (n > 0) {
@@ -2670,17 +2675,17 @@ int64_t paffy_hip_plan_rows(paffy_hip_ctx *c, int64_t cap, uint32_t *record, int
 int paffy_hip_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap) {
     if (!c) return PAFFY_E_ARG;
     if (!c->planned) return PAFFY_E_STATE;
-    if (c->plan.out_bytes == 0 || (!c->plan_is_tile && !c->plan_is_bed && c->kp.n_rec == 0)) return 0;
+    if (c->plan.out_bytes == 0 || (c->plan_kind == PLAN_RECORDS && c->kp.n_rec == 0)) return 0;
     if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15)) return PAFFY_E_ARG;
     if (out_cap < c->plan.out_bytes) return PAFFY_E_CAPACITY;
-    if (c->plan_is_bed) {
+    if (c->plan_kind == PLAN_BED) {
         const uint64_t n_runs = c->bed_runs;
         LAUNCH(c, "k_bed_lines", k_bed_lines, dim3((unsigned)((n_runs + PAFFY_NT - 1) / PAFFY_NT)), dim3(PAFFY_NT), 0, *c->bed_params,
                static_cast<const uint64_t *>(c->bed_starts.p), n_runs, static_cast<int64_t *>(c->bed_len.p), static_cast<const int64_t *>(c->bed_off.p),
                static_cast<uint8_t *>(d_out));
         return 0;
     }
-    if (c->plan_is_tile) {
+    if (c->plan_kind == PLAN_LINES) {
         if (c->line_n) LAUNCH(c, "k_tile_emit", k_line_emit, dim3((unsigned)((c->line_n + PAFFY_NWAVE - 1) / PAFFY_NWAVE)), dim3(PAFFY_NT), 0, c->line_batches, c->line_meta,
                               c->line_order, c->line_level, c->line_off, (uint64_t)0, c->line_n, (uint64_t)0, static_cast<uint8_t *>(d_out), c->line_names2);
         return 0;
@@ -2689,7 +2694,7 @@ int paffy_hip_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap) {
     kp.out = static_cast<uint8_t *>(d_out);
     const bool shatter = kp.n_stages > 0 && kp.stages[kp.n_stages - 1].kind == PAFFY_SHATTER;
     if (shatter) {
-        LAUNCH(c, "k_emit_rows", k_emit_rows, dim3(kp.n_rec + kp.n_items), dim3(64), PAFFY_ROWS_LDS_BYTES + dbg_lds_pad(0), kp);
+        LAUNCH(c, "k_emit_rows", k_emit_rows, dim3(kp.n_rec + kp.n_items), dim3(64), PAFFY_ROWS_LDS_BYTES, kp);
         if (c->h_info->g_count > 0) LAUNCH(c, "k_emit_lds", k_emit_lds<true>, dim3(kp.n_rec), dim3(PAFFY_NT), PAFFY_EMIT_LDS_BYTES, kp);
         if (c->h_info->w_count > 0) LAUNCH(c, "k_arena_emit", k_arena_emit<true>, dim3(2048), dim3(PAFFY_NT), PAFFY_EMIT_LDS_BYTES, kp);
     } else {
@@ -2706,7 +2711,7 @@ int paffy_hip_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap) {
  * large output through a bounded staging buffer. *bytes = what was written. */
 int paffy_hip_emit_lines(paffy_hip_ctx *c, int64_t first, int64_t n, void *d_out, int64_t out_cap, int64_t *bytes) {
     if (!c || !bytes || first < 0 || n < 0) return PAFFY_E_ARG;
-    if (!c->planned || !c->plan_is_tile) return PAFFY_E_STATE;
+    if (!c->planned || c->plan_kind != PLAN_LINES) return PAFFY_E_STATE;
     *bytes = 0;
     if ((uint64_t)(first + n) > c->line_n) return PAFFY_E_ARG;
     if (n == 0) return 0;
@@ -2941,9 +2946,8 @@ int paffy_hip_stream_read(paffy_hip_stream *s, const char **piece, int64_t *len)
     StreamSlot &sl = s->slot[s->drain];
     if (!sl.busy) return 0;
     if (s->n_issued == 0) HIPCHK(c, hipStreamWaitEvent(s->s_d2h, sl.ev_emit, 0)); /* first piece of this chunk */
-    /* keep two copies in flight: the piece handed out now and the one after it (PAFFY_D2H_INFLIGHT: experiments) */
-    static const int in_flight = getenv("PAFFY_D2H_INFLIGHT") ? atoi(getenv("PAFFY_D2H_INFLIGHT")) : 2;
-    while (s->n_issued < s->n_returned + (in_flight < 1 ? 1 : in_flight > 2 ? 2 : in_flight) && s->issued_at < sl.out_len) {
+    /* keep two copies in flight: the piece handed out now and the one after it */
+    while (s->n_issued < s->n_returned + 2 && s->issued_at < sl.out_len) {
         const int k = s->n_issued % 3;
         const int64_t n = sl.out_len - s->issued_at < (int64_t)s->piece_cap ? sl.out_len - s->issued_at : (int64_t)s->piece_cap;
         HIPCHK(c, hipMemcpyAsync(s->piece[k], static_cast<char *>(sl.d_out) + s->issued_at, (size_t)n, hipMemcpyDeviceToHost, s->s_d2h));
@@ -3001,14 +3005,7 @@ int paffy_hip_bed_run(paffy_hip_ctx *c, const paffy_bed_opts *opts, paffy_plan_i
     if (!c || !info || !opts) return PAFFY_E_ARG;
     CovState &S = cov_state(c);
     if (S.sides != (opts->include_inverted ? 2u : 1u)) return PAFFY_E_STATE;
-    c->planned = false;
-    c->plan_is_tile = false;
-    c->plan_is_bed = true;
-    memset(info, 0, sizeof(*info));
-    memset(&c->plan, 0, sizeof(c->plan));
-    memset(&c->kp, 0, sizeof(c->kp));
-    c->bed_runs = 0;
-    for (const CovBatch &b : S.batches) c->plan.in_bytes += b.len;
+    plan_begin(c, PLAN_BED, cov_in_bytes(S), info);
     c->plan.n_records = (int64_t)S.n_rec;
     if (S.n_rec == 0) {
         *info = c->plan;
@@ -3119,14 +3116,14 @@ int paffy_hip_flat_stats(paffy_hip_ctx *c, int64_t *left, int64_t reasons[16]) {
 
 int paffy_hip_plan_stats(paffy_hip_ctx *c, int64_t sums[6]) {
     if (!c || !sums) return PAFFY_E_ARG;
-    if (!c->planned || c->plan_is_tile) return PAFFY_E_STATE;
+    if (!c->planned || c->plan_kind == PLAN_LINES) return PAFFY_E_STATE;
     for (int k = 0; k < 6; k++) sums[k] = c->plan.in_bytes > 0 ? (int64_t)c->h_info->stats[k] : 0;
     return 0;
 }
 
 int64_t paffy_hip_plan_record_stats(paffy_hip_ctx *c, int64_t cap_records, int64_t *sums) {
     if (!c || !sums || cap_records < 0) return PAFFY_E_ARG;
-    if (!c->planned || c->plan_is_tile || c->plan_is_bed) return PAFFY_E_STATE;
+    if (!c->planned || c->plan_kind != PLAN_RECORDS) return PAFFY_E_STATE;
     const int64_t n = c->plan.n_records;
     if (n == 0) return 0;
     if (!c->kp.rec_stats) return PAFFY_E_STATE; /* no PAFFY_STATS stage in the plan */
@@ -3144,12 +3141,12 @@ __global__ __launch_bounds__(PAFFY_NT) void k_counts_add_sat(uint16_t *acc, cons
 }
 int64_t paffy_hip_bed_sequences(paffy_hip_ctx *c) {
     if (!c) return PAFFY_E_ARG;
-    if (!c->planned || !c->plan_is_bed || !c->cov) return PAFFY_E_STATE;
+    if (!c->planned || c->plan_kind != PLAN_BED || !c->cov) return PAFFY_E_STATE;
     return (int64_t)c->cov->appearance.size();
 }
 int paffy_hip_bed_counts(paffy_hip_ctx *c, int64_t sequence, int64_t start, int64_t end, uint16_t *h_counts, int accumulate) {
     if (!c || !h_counts || sequence < 0 || start < 0 || end < start) return PAFFY_E_ARG;
-    if (!c->planned || !c->plan_is_bed || !c->cov) return PAFFY_E_STATE;
+    if (!c->planned || c->plan_kind != PLAN_BED || !c->cov) return PAFFY_E_STATE;
     CovState &S = *c->cov;
     if ((size_t)sequence >= S.appearance.size()) return PAFFY_E_ARG;
     const uint32_t ci = S.appearance[(size_t)sequence];
@@ -3179,7 +3176,7 @@ int paffy_hip_keep_raw_sequences(paffy_hip_ctx *c, int on) {
 }
 
 static int pretty_params(paffy_hip_ctx *c, int64_t first, int64_t count, PrettyParams *pp) {
-    if (!c->planned || c->plan_is_tile || c->plan_is_bed) return PAFFY_E_STATE;
+    if (!c->planned || c->plan_kind != PLAN_RECORDS) return PAFFY_E_STATE;
     if (first < 0 || count < 0 || first + count > c->plan.n_records) return PAFFY_E_ARG;
     if (c->n_seqs <= 0 || !c->seq_raw.p) {
         c->last_error = "alignment rows: no sequences loaded with paffy_hip_keep_raw_sequences on";

@@ -87,6 +87,20 @@ def test_edges_and_errors(eng):
     check(eng, b"q\t30\t2\t12\t+\tt\t40\t5\t15\t10\t10\t60\n")                                        # no cigar but a non-empty range
 
 
+def test_plan_state_does_not_outlive_its_plan(eng, human_chimp):
+    """One context, one plan after another: a to_bed plan leaves nothing to the dedupe plan after it (its emit writes the dedupe
+    lines, not the BED runs) nor to flat_stats (which describes record plans only)."""
+    import paffy_amd
+
+    eng.run([paffy_amd.stage(paffy_amd.INVERT)], human_chimp)
+    assert eng.flat_stats()[0] >= 0                                           # a record plan through the flat pass
+    check(eng, human_chimp)
+    assert eng.flat_stats()[0] == -1
+    want, werr = O.dedupe(human_chimp)
+    got, info = eng.dedupe(human_chimp, raise_on_error=False)
+    assert info.error.code == werr.code and got == want
+
+
 def test_cli(tmp_path, human_chimp):
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "host"), "-s"])
     src = tmp_path / "in.paf"
