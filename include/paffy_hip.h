@@ -275,6 +275,40 @@ int paffy_hip_chain_begin(paffy_hip_ctx *ctx);
 int paffy_hip_chain_add(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len);
 int paffy_hip_chain_run(paffy_hip_ctx *ctx, const paffy_chain_opts *opts, paffy_plan_info *info);
 int64_t paffy_hip_chain_tags(paffy_hip_ctx *ctx, int64_t cap, int64_t *chain_id, int64_t *chain_score);
+/*
+ * Chain in parts: `paffy chain` sharded by query sequence. The recurrence is independent per (query, target, strand), so
+ * a context that holds ALL records of some query names (the partition of paffy_hip_query_names_counts / paffy_hip_split_to) finds the
+ * links, chain scores and cuts one process would. Three things are global -- the chain numbers (cn), the place of every line, the
+ * failing record that ends the run -- and are settled from 32 bytes per chain and per line; the text never moves after the partition.
+ * paffy_hip_chain_run is these calls with the part's own numbering.
+ *   add_indexed: paffy_hip_chain_add plus the global input record number of every line of the batch (d_gidx: one int64 per line, device
+ *                memory -- what paffy_hip_split_to wrote to d_rec_index; read before the call returns). Batches added with plain
+ *                chain_add get their running local index. Where the reference compares object addresses (impl/chaining.c:18,47,62)
+ *                this number stands in for creation order, and every error.record of the calls below is one.
+ *   run_part:    everything up to and including the cut of the chains, and their numbering inside the part by (strand, chain-end
+ *                score desc, processing key desc, global number desc). No lines are planned (emit refuses). Parse errors and the asserts
+ *                of the trim (PAFFY_ERR_CHAIN_ASSERT) are reported as by chain_run: of a part's lines that do not parse, the one with
+ *                the lowest global number. After an error the part is over: tail_keys / renumber return PAFFY_E_STATE.
+ *   tail_keys:   four int64 per chain of the part into device memory, in the part's chain order: strand class (0 '+', 1 '-'), the
+ *                chain end's score as the recurrence left it (the key of chain_cmp_by_score; not s1, which is the score of the chain as
+ *                cut), the chain end's processing key (trimmed, for '-' mirrored query start), the chain end's global record number.
+ *                A pure function of the records: chains of different parts compare as inside one process, whose numbering is the rank
+ *                by (class asc, score desc, key desc, number desc). Returns the number of chains (cap_chains smaller: PAFFY_E_CAPACITY).
+ *   renumber:    d_global_id: one int64 per chain of the part, in the same order, in [0, 2^31): installed as the chains' cn. Then the
+ *                rest of chain_run: output order inside the part (own score desc, chain id asc, link asc), tags, paf_check of the
+ *                un-trimmed records, line sizes (they depend on the digits of cn). Afterwards paffy_hip_emit, _emit_lines, _plan_rows
+ *                (records: indices into the part's batches, in the order they were added) and _chain_tags work as after chain_run. A
+ *                failing check is reported in info->error and fail_key (may be NULL) gets the failing line's (own score, chain id,
+ *                link). The check runs chain by chain, link by link (impl/chaining.c:321-334, before the sort by score): of several parts
+ *                that fail, the one with the smallest (chain id, link) is what one process reports. Nothing is to be written then.
+ *   line_keys:   four int64 per output line into device memory, in the part's output order: own score, chain id, link position, bytes
+ *                of the line. (Own score desc, chain id, link) is a total order; the whole output is the merge of the parts by it.
+ */
+int paffy_hip_chain_add_indexed(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len, const void *d_gidx);
+int paffy_hip_chain_run_part(paffy_hip_ctx *ctx, const paffy_chain_opts *opts, paffy_plan_info *info);
+int64_t paffy_hip_chain_tail_keys(paffy_hip_ctx *ctx, int64_t cap_chains, void *d_keys);
+int paffy_hip_chain_renumber(paffy_hip_ctx *ctx, const void *d_global_id, paffy_plan_info *info, int64_t fail_key[3]);
+int64_t paffy_hip_chain_line_keys(paffy_hip_ctx *ctx, int64_t cap_lines, void *d_keys);
 
 /*
  * After a tile or dedupe plan: the lines emit will write, in output order -- record[k] = zero-based input record of line k,

@@ -41,7 +41,8 @@ struct ChainRecs {
     int64_t *level;
 };
 
-__global__ __launch_bounds__(PAFFY_NT) void k_chain_keys(const uint8_t *const *batch_in, const RecMeta *meta, uint32_t n, ChainOpts o, ChainRecs R, DevInfo *info, uint32_t salt) {
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_keys(const uint8_t *const *batch_in, const RecMeta *meta, uint32_t n, ChainOpts o, ChainRecs R, DevInfo *info, uint32_t salt,
+                                                         const int64_t *gidx) {
     const uint32_t r = blockIdx.x * PAFFY_NT + threadIdx.x;
     if (r >= n) return;
     const RecMeta m = meta[r];
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_keys(const uint8_t *const *b
     const int64_t mq = (int64_t)fq, mt = (int64_t)ft;
     if (mq < 0 || mt < 0) bad = 1; /* asserts :278-279 */
     if (bad) {
-        atomicMin(&info->first_err_key, ((unsigned long long)r << 16) | (1ull << 8) | (unsigned long long)PAFFY_ERR_CHAIN_ASSERT);
+        /* gidx: the records' global input numbers when the context holds one part of a sharded chain (chain_host.h) */
+        atomicMin(&info->first_err_key, ((unsigned long long)(gidx ? (uint64_t)gidx[r] : r) << 16) | (1ull << 8) | (unsigned long long)PAFFY_ERR_CHAIN_ASSERT);
         return;
     }
     const int64_t t = (mq < mt ? mq : mt) / 2;
@@ -122,12 +124,15 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_group_starts(const uint32_t 
 /* per position (records grouped, processing order inside a group) */
 struct ChainPos {
     int64_t *qs, *qe, *ts, *te, *sc, *mq; /* mq: largest query end of the group up to here */
-    uint32_t *idx, *rank;                 /* input index (the address stand-in), processing index */
+    uint32_t *idx, *rank;                 /* input index, processing index */
+    uint32_t *ai;                         /* the address stand-in: creation order. The input index (ai == idx), or in one part of a sharded chain
+                                             the record's rank by global input number */
     int64_t *best;                        /* chain->score */
     uint32_t *pred;                       /* chain->pChain as a position */
     uint8_t *neg;
 };
-__global__ __launch_bounds__(PAFFY_NT) void k_chain_gather(const RecMeta *meta, ChainRecs R, const uint32_t *ord, const uint32_t *rank, uint32_t n, ChainPos Q) {
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_gather(const RecMeta *meta, ChainRecs R, const uint32_t *ord, const uint32_t *rank, const uint32_t *grank, uint32_t n,
+                                                           ChainPos Q) {
     const uint32_t j = blockIdx.x * PAFFY_NT + threadIdx.x;
     if (j >= n) return;
     const uint32_t r = ord[j];
@@ -137,6 +142,7 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_gather(const RecMeta *meta, 
     Q.te[j] = R.te[r];
     Q.sc[j] = R.sc[r];
     Q.idx[j] = r;
+    if (grank) Q.ai[j] = grank[r];
     Q.rank[j] = rank[r];
     Q.neg[j] = meta[r].same_strand ? 0 : 1;
 }
@@ -183,7 +189,7 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_dp(const uint32_t *start, ui
     uint32_t lo = g0; /* everything before lo ends more than max_gap before the current query start */
     for (uint32_t i = g0; i < g1; i++) {
         const int64_t qs_i = Q.qs[i], ts_i = Q.ts[i], sc_i = Q.sc[i];
-        const uint32_t idx_i = Q.idx[i];
+        const uint32_t idx_i = Q.ai[i];
         while (lo < i && Q.mq[lo] < qs_i - o.max_gap) lo++;
         int64_t b_cs = INT64_MIN, b_te = 0, b_qe = 0;
         uint32_t b_idx = 0, b_p = CHAIN_NONE;
@@ -192,7 +198,7 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_dp(const uint32_t *start, ui
             const int64_t qe_p = Q.qe[p], te_p = Q.te[p];
             if (qs_i < qe_p || qs_i - qe_p > o.max_gap) continue;
             if (ts_i < te_p || ts_i - te_p > o.max_gap) continue;
-            const uint32_t idx_p = Q.idx[p];
+            const uint32_t idx_p = Q.ai[p];
             if (te_p == ts_i && qe_p == qs_i && idx_p > idx_i) continue; /* sorts after the search key (impl/chaining.c:71-79) */
             const int64_t gc = chain_gap_cost(o, qs_i - qe_p, ts_i - te_p);
             if (!(gc < sc_i)) continue;
@@ -282,7 +288,7 @@ __global__ __launch_bounds__(CHAIN_BIG_NT) void k_chain_dp_big(const uint32_t *s
             /* phase 1: the candidates in front of the tile, one record per wave */
             if (i < g1) {
                 const int64_t qs_i = Q.qs[i], ts_i = Q.ts[i], sc_i = Q.sc[i];
-                const uint32_t idx_i = Q.idx[i];
+                const uint32_t idx_i = Q.ai[i];
                 while (lo < base && Q.mq[lo] < qs_i - o.max_gap) lo++;
                 ChainCand b;
                 b.cs = INT64_MIN; b.te = 0; b.qe = 0; b.idx = 0; b.p = CHAIN_NONE;
@@ -295,7 +301,7 @@ __global__ __launch_bounds__(CHAIN_BIG_NT) void k_chain_dp_big(const uint32_t *s
                         const bool in = p < base;
                         qe4[u] = in ? Q.qe[p] : INT64_MAX; /* fails the first test */
                         te4[u] = in ? Q.te[p] : 0;
-                        idx4[u] = in ? Q.idx[p] : 0u;
+                        idx4[u] = in ? Q.ai[p] : 0u;
                         best4[u] = in ? Q.best[p] : 0;
                     }
 #pragma unroll
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(CHAIN_BIG_NT) void k_chain_dp_big(const uint32_t *s
                 const uint32_t n_t = g1 - base < CHAIN_TILE ? g1 - base : CHAIN_TILE;
                 const uint32_t me = base + (lane < n_t ? lane : 0u);
                 const int64_t qs_m = Q.qs[me], ts_m = Q.ts[me], qe_m = Q.qe[me], te_m = Q.te[me], sc_m = Q.sc[me];
-                const uint32_t idx_m = Q.idx[me];
+                const uint32_t idx_m = Q.ai[me];
                 ChainCand mine; /* what phase 1 found for my record */
                 mine.cs = INT64_MIN; mine.te = 0; mine.qe = 0; mine.idx = 0; mine.p = CHAIN_NONE;
                 if (lane < n_t) {
@@ -401,11 +407,14 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_class(const uint32_t *by_sco
     const uint32_t p = by_score[k];
     cls[k] = is_tail[p] ? (neg[p] ? 1u : 0u) : 2u;
 }
-__global__ __launch_bounds__(PAFFY_NT) void k_chain_number(const uint32_t *by_class, const uint8_t *is_tail, uint32_t n, uint32_t *chain_of_tail) {
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_number(const uint32_t *by_class, const uint8_t *is_tail, uint32_t n, uint32_t *chain_of_tail, uint32_t *tails) {
     const uint32_t k = blockIdx.x * PAFFY_NT + threadIdx.x;
     if (k >= n) return;
     const uint32_t p = by_class[k];
-    if (is_tail[p]) chain_of_tail[p] = k; /* the tails come first */
+    if (is_tail[p]) { /* the tails come first */
+        chain_of_tail[p] = k;
+        tails[k] = p;
+    }
 }
 /* per position: the keys of the output order (own score desc; among equals the order the chains were written in: chain, link) */
 __global__ __launch_bounds__(PAFFY_NT) void k_chain_out_keys(ChainPos Q, const uint32_t *tail_of, const uint32_t *chain_of_tail, uint32_t n, uint32_t *chain_id, uint64_t *score_key) {
@@ -436,7 +445,7 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_finish(RecMeta *meta, ChainP
     if (chk) atomicMin(check_key, ((unsigned long long)chain_id[p] << 32) | link[p]);
 }
 __global__ __launch_bounds__(PAFFY_NT) void k_chain_find_failed(const RecMeta *meta, ChainPos Q, const uint32_t *chain_id, const uint32_t *link, uint32_t n,
-                                                                 const unsigned long long *check_key, DevInfo *info) {
+                                                                 const unsigned long long *check_key, const int64_t *gidx, DevInfo *info, int64_t *fail_score) {
     const uint32_t p = blockIdx.x * PAFFY_NT + threadIdx.x;
     if (p >= n || *check_key == ~0ull) return;
     if ((((unsigned long long)chain_id[p] << 32) | link[p]) != *check_key) return;
@@ -445,5 +454,59 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_find_failed(const RecMeta *m
     if (m.qs < 0 || m.qs >= m.qlen) chk = PAFFY_ERR_CHECK_QSTART;
     else if (m.qs > m.qe || m.qe > m.qlen) chk = PAFFY_ERR_CHECK_QEND;
     else if (m.ts < 0 || m.ts >= m.tlen) chk = PAFFY_ERR_CHECK_TSTART;
-    info->first_err_key = ((unsigned long long)Q.idx[p] << 16) | (1ull << 8) | (unsigned long long)chk;
+    info->first_err_key = ((unsigned long long)(gidx ? (uint64_t)gidx[Q.idx[p]] : Q.idx[p]) << 16) | (1ull << 8) | (unsigned long long)chk;
+    *fail_score = Q.sc[p];
+}
+
+/*
+ * Chain in parts (chain_host.h): a context holds the records of some query sequences of a larger input, with their global input
+ * numbers. Groups never span parts, so links, chain scores and cuts are the whole input's; what is global -- the chain numbers, the
+ * place of every line, the failure that ends the run -- is settled from the few numbers per chain and per line exported here.
+ */
+__global__ __launch_bounds__(PAFFY_NT) void k_iota64(int64_t *out, int64_t first, uint32_t n) {
+    const uint32_t i = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (i < n) out[i] = first + i;
+}
+/* the tails stand first in the order by class: their number is where class 2 begins */
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_count(const uint32_t *sorted_cls, uint32_t n, uint32_t *n_chains) {
+    const uint32_t k = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (k < n && sorted_cls[k] < 2u && (k + 1 == n || sorted_cls[k + 1] == 2u)) *n_chains = k + 1;
+}
+/* per chain, local chain order: strand class, the end's score as the recurrence left it (the key of chain_cmp_by_score, not s1), the
+   end's processing key (trimmed, for '-' mirrored query start), the end's global input number */
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_tail_keys(const uint32_t *tails, ChainPos Q, const int64_t *gidx, uint32_t n_chains, int64_t *keys) {
+    const uint32_t k = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (k >= n_chains) return;
+    const uint32_t p = tails[k];
+    keys[4 * (size_t)k + 0] = Q.neg[p];
+    keys[4 * (size_t)k + 1] = Q.best[p];
+    keys[4 * (size_t)k + 2] = Q.qs[p];
+    keys[4 * (size_t)k + 3] = gidx ? gidx[Q.idx[p]] : (int64_t)Q.idx[p];
+}
+/* local chain k becomes chain id[k] of the whole input */
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_renumber(const uint32_t *tails, const int64_t *id, uint32_t n_chains, uint32_t *chain_of_tail, uint32_t *bad) {
+    const uint32_t k = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (k >= n_chains) return;
+    if (id[k] < 0 || id[k] >= (1ll << 31)) atomicOr(bad, 1u);
+    chain_of_tail[tails[k]] = (uint32_t)id[k];
+}
+/* per output line, output order: own score, chain id, link, bytes of the line */
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_line_keys(const uint32_t *out_pos, ChainPos Q, const uint32_t *chain_id, const uint32_t *link, const uint64_t *out_len,
+                                                               uint32_t n, int64_t *keys) {
+    const uint32_t k = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t p = out_pos[k];
+    keys[4 * (size_t)k + 0] = Q.sc[p];
+    keys[4 * (size_t)k + 1] = chain_id[p];
+    keys[4 * (size_t)k + 2] = link[p];
+    keys[4 * (size_t)k + 3] = (int64_t)out_len[k];
+}
+/* a part's first line that did not parse, by global input number: the smallest number, then the record that has it */
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_parse_err_min(const RecMeta *meta, const int64_t *gidx, uint32_t n, unsigned long long *key) {
+    const uint32_t r = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (r < n && meta[r].err) atomicMin(key, ((unsigned long long)gidx[r] << 16) | (unsigned long long)meta[r].err);
+}
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_parse_err_rec(const RecMeta *meta, const int64_t *gidx, uint32_t n, const unsigned long long *key, unsigned long long *rec) {
+    const uint32_t r = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (r < n && meta[r].err && (unsigned long long)gidx[r] == (*key >> 16)) atomicMin(rec, (unsigned long long)r);
 }

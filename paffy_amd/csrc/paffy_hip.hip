@@ -1919,7 +1919,8 @@ static void chain_free(paffy_hip_ctx *c) {
     if (!c->chain) return;
     ChainState &H = *c->chain;
     DevBuf *bufs[] = {&H.qkey, &H.ghash, &H.ord1, &H.ord2, &H.rank, &H.start, &H.gid, &H.idx, &H.prank, &H.pred, &H.neg, &H.taken, &H.is_tail, &H.tail_of, &H.link, &H.total,
-                      &H.chain_of_tail, &H.chain_id, &H.score_key, &H.o1, &H.o2, &H.o3, &H.cls, &H.tag_chain, &H.tag_score, &H.check_key, &H.iota, &H.big_list, &H.n_big, &H.rank_of, &H.claim};
+                      &H.chain_of_tail, &H.chain_id, &H.score_key, &H.o1, &H.o2, &H.o3, &H.cls, &H.tag_chain, &H.tag_score, &H.check_key, &H.iota, &H.big_list, &H.n_big, &H.rank_of, &H.claim,
+                      &H.gidx, &H.gperm, &H.grank, &H.ai, &H.tails, &H.words};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : H.i64)
@@ -2018,11 +2019,37 @@ int paffy_hip_chain_begin(paffy_hip_ctx *c) {
     if (!c) return PAFFY_E_ARG;
     c->planned = false;
     index_drop_all(c); /* indexes kept by paffy_hip_query_names for batches that were never split */
+    ChainState &H = chain_state(c);
+    H.indexed = H.part_ready = false;
+    H.n_chains = 0;
     return cov_begin(c, 1);
+}
+/* records [first, first + n) of the chain state get their global input numbers: the caller's (d_gidx), or the running local index */
+static int chain_number_records(paffy_hip_ctx *c, uint64_t first, uint64_t n, const void *d_gidx) {
+    ChainState &H = chain_state(c);
+    if (n == 0 || (!d_gidx && !H.indexed)) return 0;
+    if (ensure_keep(c, H.gidx, sizeof(int64_t) * (first + n), H.indexed ? sizeof(int64_t) * first : 0)) return PAFFY_E_HIP;
+    int64_t *g = static_cast<int64_t *>(H.gidx.p);
+    if (!H.indexed && first) /* the batches before this one were added without numbers */
+        LAUNCH(c, "k_iota64", k_iota64, dim3((unsigned)((first + PAFFY_NT - 1) / PAFFY_NT)), dim3(PAFFY_NT), 0, g, (int64_t)0, (uint32_t)first);
+    if (d_gidx) {
+        HIPCHK(c, hipMemcpyAsync(g + first, d_gidx, sizeof(int64_t) * n, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); /* d_gidx is the caller's again */
+    } else LAUNCH(c, "k_iota64", k_iota64, dim3((unsigned)((n + PAFFY_NT - 1) / PAFFY_NT)), dim3(PAFFY_NT), 0, g + first, (int64_t)first, (uint32_t)n);
+    H.indexed = true;
+    return 0;
 }
 int paffy_hip_chain_add(paffy_hip_ctx *c, const void *d_in, int64_t in_len) {
     if (!c) return PAFFY_E_ARG;
-    return cov_add(c, d_in, in_len, false);
+    const uint64_t first = cov_state(c).n_rec;
+    int rc = cov_add(c, d_in, in_len, false);
+    return rc ? rc : chain_number_records(c, first, cov_state(c).n_rec - first, nullptr);
+}
+int paffy_hip_chain_add_indexed(paffy_hip_ctx *c, const void *d_in, int64_t in_len, const void *d_gidx) {
+    if (!c || !d_gidx) return PAFFY_E_ARG;
+    const uint64_t first = cov_state(c).n_rec;
+    int rc = cov_add(c, d_in, in_len, false);
+    return rc ? rc : chain_number_records(c, first, cov_state(c).n_rec - first, d_gidx);
 }
 int paffy_hip_chain_run(paffy_hip_ctx *c, const paffy_chain_opts *opts, paffy_plan_info *info) {
     if (!c || !info || !opts) return PAFFY_E_ARG;
@@ -2043,6 +2070,84 @@ int paffy_hip_chain_run(paffy_hip_ctx *c, const paffy_chain_opts *opts, paffy_pl
     *info = c->plan;
     c->planned = true;
     return 0;
+}
+/*
+ * Chain in parts: paffy_hip_chain_run cut where its global decisions begin (chain_host.h). A context that holds the records of some
+ * query sequences runs the part, hands out four numbers per chain, takes the chains' numbers in the whole input, and finishes.
+ */
+int paffy_hip_chain_run_part(paffy_hip_ctx *c, const paffy_chain_opts *opts, paffy_plan_info *info) {
+    if (!c || !info || !opts) return PAFFY_E_ARG;
+    CovState &S = cov_state(c);
+    plan_begin(c, PLAN_LINES, cov_in_bytes(S), info);
+    c->plan.n_records = (int64_t)S.n_rec;
+    const ChainOpts o{opts->gap_open, opts->gap_extend, opts->max_gap_length, opts->trim_fraction};
+    int rc = chain_part(c, o, true, &c->plan.error);
+    if (rc) return rc;
+    if (c->profile) prof_collect(c);
+    *info = c->plan; /* no lines planned: c->planned stays false until paffy_hip_chain_renumber */
+    return 0;
+}
+int64_t paffy_hip_chain_tail_keys(paffy_hip_ctx *c, int64_t cap_chains, void *d_keys) {
+    if (!c) return PAFFY_E_ARG;
+    if (!c->chain || !c->chain->part_ready || c->plan.error.code) return PAFFY_E_STATE;
+    ChainState &H = *c->chain;
+    const uint32_t n = H.n_chains;
+    if (cap_chains < (int64_t)n) return PAFFY_E_CAPACITY;
+    if (n == 0) return 0;
+    if (!d_keys) return PAFFY_E_ARG;
+    LAUNCH(c, "k_chain_tail_keys", k_chain_tail_keys, dim3((n + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(H.tails.p), chain_pos(H),
+           H.indexed ? static_cast<const int64_t *>(H.gidx.p) : nullptr, n, static_cast<int64_t *>(d_keys));
+    return (int64_t)n;
+}
+int paffy_hip_chain_renumber(paffy_hip_ctx *c, const void *d_global_id, paffy_plan_info *info, int64_t fail_key[3]) {
+    if (!c || !info) return PAFFY_E_ARG;
+    if (!c->chain || !c->chain->part_ready || c->plan.error.code) return PAFFY_E_STATE;
+    CovState &S = cov_state(c);
+    ChainState &H = *c->chain;
+    const uint64_t n = S.n_rec;
+    if (H.n_chains && !d_global_id) return PAFFY_E_ARG;
+    c->planned = false;
+    c->line_n = 0; /* a renumber before this one may have planned lines */
+    c->plan.n_rows = c->plan.out_bytes = 0;
+    if (n > 0) {
+        uint32_t *bad = reinterpret_cast<uint32_t *>(static_cast<unsigned long long *>(H.words.p) + 2), hit = 0;
+        HIPCHK(c, hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
+        LAUNCH(c, "k_chain_renumber", k_chain_renumber, dim3((H.n_chains + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(H.tails.p),
+               static_cast<const int64_t *>(d_global_id), H.n_chains, static_cast<uint32_t *>(H.chain_of_tail.p), bad);
+        if (cov_fetch(c, &hit, bad, sizeof(hit))) return PAFFY_E_HIP;
+        if (hit) {
+            c->last_error = "a chain number outside [0, 2^31)";
+            H.part_ready = false;
+            return PAFFY_E_ARG;
+        }
+        int rc = chain_finish(c, &c->plan.error);
+        if (rc) return rc;
+        if (c->plan.error.code) {
+            if (fail_key) memcpy(fail_key, H.fail_key, sizeof(H.fail_key));
+        } else {
+            int rl = lines_plan(c, S, n);
+            if (rl) return rl;
+        }
+        if (c->profile) prof_collect(c);
+    }
+    *info = c->plan;
+    c->planned = true;
+    return 0;
+}
+int64_t paffy_hip_chain_line_keys(paffy_hip_ctx *c, int64_t cap_lines, void *d_keys) {
+    if (!c) return PAFFY_E_ARG;
+    if (!c->planned || c->plan_kind != PLAN_LINES || !c->chain || !c->cov || c->plan.error.code) return PAFFY_E_STATE;
+    CovState &S = cov_state(c);
+    ChainState &H = *c->chain;
+    const uint64_t n = H.n_out;
+    if (n == 0 && c->line_n == 0) return 0; /* a part without records */
+    if (n != c->line_n || c->line_meta != static_cast<const RecMeta *>(S.meta.p)) return PAFFY_E_STATE; /* the last plan was not a chain */
+    if ((uint64_t)cap_lines < n) return PAFFY_E_CAPACITY;
+    if (!d_keys) return PAFFY_E_ARG;
+    LAUNCH(c, "k_chain_line_keys", k_chain_line_keys, dim3((unsigned)((n + PAFFY_NT - 1) / PAFFY_NT)), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(H.o3.p), chain_pos(H),
+           static_cast<const uint32_t *>(H.chain_id.p), static_cast<const uint32_t *>(H.link.p), static_cast<const uint64_t *>(S.out_len.p), (uint32_t)n,
+           static_cast<int64_t *>(d_keys));
+    return (int64_t)n;
 }
 int64_t paffy_hip_chain_tags(paffy_hip_ctx *c, int64_t cap, int64_t *chain_id, int64_t *chain_score) {
     if (!c || cap < 0 || !chain_id || !chain_score) return PAFFY_E_ARG;

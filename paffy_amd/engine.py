@@ -116,6 +116,15 @@ def lib():
         L.paffy_hip_chain_run.argtypes = [vp, C.POINTER(ChainOpts), C.POINTER(PlanInfo)]
         L.paffy_hip_chain_tags.restype = i64
         L.paffy_hip_chain_tags.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64)]
+        L.paffy_hip_chain_add_indexed.argtypes = [vp, vp, i64, vp]
+        L.paffy_hip_chain_run_part.argtypes = [vp, C.POINTER(ChainOpts), C.POINTER(PlanInfo)]
+        L.paffy_hip_chain_tail_keys.restype = i64
+        L.paffy_hip_chain_tail_keys.argtypes = [vp, i64, vp]
+        L.paffy_hip_chain_renumber.argtypes = [vp, vp, C.POINTER(PlanInfo), C.POINTER(i64)]
+        L.paffy_hip_chain_line_keys.restype = i64
+        L.paffy_hip_chain_line_keys.argtypes = [vp, i64, vp]
+        L.paffy_hip_plan_rows.restype = i64
+        L.paffy_hip_plan_rows.argtypes = [vp, i64, C.POINTER(C.c_uint32), C.POINTER(i64)]
         L.paffy_hip_tile_keys.restype = i64
         L.paffy_hip_tile_keys.argtypes = [vp, i64, vp]
         L.paffy_hip_emit_lines.argtypes = [vp, i64, i64, vp, i64, C.POINTER(i64)]
@@ -402,6 +411,59 @@ class Engine:
         if got < 0:
             self._check(int(got), "paffy_hip_chain_tags")
         return list(ids[:got]), list(scores[:got])
+
+    # ---- chain in parts: `paffy chain` sharded by query sequence (include/paffy_hip.h; shard.chain_sharded drives these) ----
+    def chain_part(self, bufs, gidx=None, gap_open=5000, gap_extend=1, max_gap=1000000, trim=1.0):
+        """begin, add every device batch [(uint8 tensor, nbytes)] -- with gidx[b], an int64 device tensor holding the global input
+        record number of every line of batch b, where given -- and run the part: everything up to the cut of the chains. The batches
+        must stay alive until the lines have been written. Returns the PlanInfo (error.record is a global record number)."""
+        L = lib()
+        self._check(L.paffy_hip_chain_begin(self._ctx), "paffy_hip_chain_begin")
+        for b, (buf, nbytes) in enumerate(bufs):
+            g = gidx[b] if gidx is not None else None
+            if g is None:
+                self._check(L.paffy_hip_chain_add(self._ctx, C.c_void_p(buf.data_ptr()), nbytes), "paffy_hip_chain_add")
+            else:
+                if g.dtype != self.torch.int64 or not g.is_contiguous() or g.device != self.device:
+                    raise ValueError("the global record numbers of a batch: a contiguous int64 tensor on the engine's device")
+                self._check(L.paffy_hip_chain_add_indexed(self._ctx, C.c_void_p(buf.data_ptr()), nbytes, C.c_void_p(g.data_ptr())), "paffy_hip_chain_add_indexed")
+        info, opts = PlanInfo(), ChainOpts(gap_open, gap_extend, max_gap, trim)
+        self._check(L.paffy_hip_chain_run_part(self._ctx, C.byref(opts), C.byref(info)), "paffy_hip_chain_run_part")
+        return info
+
+    def chain_tail_keys(self, cap_chains):
+        """After chain_part: int64 device tensor [chains, 4] -- strand class, chain-end score, processing key, global record number of
+        the chain end -- in the part's chain order. cap_chains: an upper bound (the part's records will do)."""
+        keys = self.torch.empty((max(1, cap_chains), 4), dtype=self.torch.int64, device=self.device)
+        n = lib().paffy_hip_chain_tail_keys(self._ctx, cap_chains, C.c_void_p(keys.data_ptr()))
+        if n < 0:
+            self._check(int(n), "paffy_hip_chain_tail_keys")
+        return keys[:n]
+
+    def chain_renumber(self, global_ids):
+        """global_ids: int64 device tensor, the number of every chain of the part in the whole input (the order of chain_tail_keys).
+        Finishes the run. Returns (PlanInfo, None), or with a failed paf_check (PlanInfo, (own score, chain id, link) of that line)."""
+        g = global_ids.to(device=self.device, dtype=self.torch.int64).contiguous()
+        info, fail = PlanInfo(), (C.c_int64 * 3)()
+        self._check(lib().paffy_hip_chain_renumber(self._ctx, C.c_void_p(g.data_ptr()) if g.numel() else None, C.byref(info), fail), "paffy_hip_chain_renumber")
+        return info, (tuple(fail) if info.error.code else None)
+
+    def chain_line_keys(self, n_lines):
+        """After chain_renumber (or a chain run): int64 device tensor [n_lines, 4] -- own score, chain id, link, bytes -- of every output
+        line, in output order."""
+        keys = self.torch.empty((max(1, n_lines), 4), dtype=self.torch.int64, device=self.device)
+        n = lib().paffy_hip_chain_line_keys(self._ctx, n_lines, C.c_void_p(keys.data_ptr()))
+        if n < 0:
+            self._check(int(n), "paffy_hip_chain_line_keys")
+        return keys[:n]
+
+    def plan_rows(self, n_lines):
+        """(input record, first output byte) of every line emit will write, and the total, after a tile / chain / dedupe plan."""
+        rec, off = (C.c_uint32 * (n_lines + 1))(), (C.c_int64 * (n_lines + 1))()
+        n = lib().paffy_hip_plan_rows(self._ctx, n_lines + 1, rec, off)
+        if n < 0:
+            self._check(int(n), "paffy_hip_plan_rows")
+        return list(rec[:n]), list(off[: n + 1])
 
     def dedupe_plan(self, d_in, in_len, check_inverse=False):
         info = PlanInfo()

@@ -459,31 +459,37 @@ class GpuTileWorker:
         self.pieces = pieces if world == 1 else None
         return send[:total], dest_bytes, gidx[:total_r], dest_recs
 
-    def tile(self, recv_buf, pieces=None):
-        """paffy tile over the lines this rank owns -> int64 [n, 5] per output line: chain_score, score, local record, bytes, level.
-        pieces: [(offset, bytes)] -- whole lines starting at multiples of 16 bytes of recv_buf (what exchange_lines / split lay
-        out): they are tiled where they are; a piece too long for a batch, or a buffer without pieces, is cut at line ends into
-        16-byte aligned copies. recv_buf may be a one-element list (tile_sharded hands over its only reference)."""
+    def _cut(self, recv, pieces=None):
+        """[(uint8 tensor, bytes)]: the pieces of recv as text batches -- where they were received when they are 16-byte aligned and
+        short enough, else cut at line ends into 16-byte aligned copies of at most batch_bytes."""
         t = self.eng.torch
-        holder = recv_buf if isinstance(recv_buf, list) else [recv_buf]
-        recv = holder[0].to(self.eng.device)
         if pieces is None:
             pieces = [(0, int(recv.numel()))]
-        self.keep = []
+        keep = []
         in_place = recv.data_ptr() % 16 == 0
         for off, n in pieces:
             room = (n + 15) // 16 * 16
             if n == 0:
                 continue
             if in_place and off % 16 == 0 and n <= self.batch_bytes and off + room <= recv.numel():
-                self.keep.append((recv[off: off + room], n))  # where it was received
+                keep.append((recv[off: off + room], n))  # where it was received
                 continue
             part = recv[off: off + n]
             for a, b in line_cuts(part, self.batch_bytes):
                 piece = t.empty((b - a + 15) // 16 * 16 + 16, dtype=t.uint8, device=self.eng.device)  # batches are 16-byte aligned
                 piece[: b - a] = part[a:b]
                 piece[b - a:] = 0
-                self.keep.append((piece, b - a))
+                keep.append((piece, b - a))
+        return keep
+
+    def tile(self, recv_buf, pieces=None):
+        """paffy tile over the lines this rank owns -> int64 [n, 5] per output line: chain_score, score, local record, bytes, level.
+        pieces: [(offset, bytes)] -- whole lines starting at multiples of 16 bytes of recv_buf (what exchange_lines / split lay
+        out): they are tiled where they are; a piece too long for a batch, or a buffer without pieces, is cut at line ends into
+        16-byte aligned copies. recv_buf may be a one-element list (tile_sharded hands over its only reference)."""
+        holder = recv_buf if isinstance(recv_buf, list) else [recv_buf]
+        recv = holder[0].to(self.eng.device)
+        self.keep = self._cut(recv, pieces)
         if isinstance(recv_buf, list):
             recv_buf.clear()
         self._recv = recv if any(x.data_ptr() >= recv.data_ptr() and x.data_ptr() < recv.data_ptr() + max(1, recv.numel()) for x, _ in self.keep) else None
@@ -619,3 +625,214 @@ def gather_ordered_output(worker, dist, rank, world, lines, line_bytes, offsets,
         src_off[1:] = torch.cumsum(sizes, 0)
         worker.scatter(all_b[r][:nb].to(dev), src_off, all_n[r][:nl, 1].to(dev).contiguous(), out)
     return out[:total]
+
+
+# ---- chain across ranks -------------------------------------------------------------------------
+#
+# `paffy chain` links records of one (query, target, strand) only (impl/chaining.c:37-54), so a partition by query name keeps every
+# group whole and the links, chain scores and cuts of a part are those of the whole input. Steps 1-2 are tile's (names, partition,
+# exchange_lines). Then:
+#   3. every rank runs its part up to the cut of the chains (paffy_hip_chain_run_part), the records carrying their global input numbers;
+#   4. an all-gather of (strand class, chain-end score, processing key, global number) -- 32 bytes per chain -- and global_chain_ids give
+#      every chain the number (cn) one process would;
+#   5. paffy_hip_chain_renumber finishes the part with those numbers: output order, tags, paf_check, line sizes;
+#   6. an all-gather of (own score, chain id, link, line bytes) -- 32 bytes per line -- and chain_line_offsets give every local line its
+#      byte offset in the ordered output; the lines are written there (scatter) or stay where they are.
+# Failures: a part's parse / assert error ends the run for everyone before step 4 (the lowest stage, then the lowest global record, is
+# what one process reports); a failed paf_check after step 5 (the smallest (chain id, link): the order the reference checks in).
+
+
+def global_chain_ids(all_tail_keys):
+    """all_tail_keys: int64 [N, 4] = (strand class, chain-end score, processing key, global record number) of ALL chains, the parts
+    one after the other. Returns int64 [N]: every chain's number in the whole input -- its rank by (class asc, score desc, key desc,
+    number desc), the order one process pulls the chains out in (impl/chaining.c:213-230, '+' before '-', :304-305). Four stable
+    sorts, least significant key first; pure torch, on whatever device the keys are on."""
+    import torch
+
+    k = all_tail_keys
+    order = torch.sort(k[:, 3], descending=True, stable=True).indices
+    order = order[torch.sort(k[order, 2], descending=True, stable=True).indices]
+    order = order[torch.sort(k[order, 1], descending=True, stable=True).indices]
+    order = order[torch.sort(k[order, 0], stable=True).indices]
+    ids = torch.empty(k.shape[0], dtype=torch.int64, device=k.device)
+    ids[order] = torch.arange(k.shape[0], dtype=torch.int64, device=k.device)
+    return ids
+
+
+def chain_line_offsets(all_line_keys, owner, rank):
+    """all_line_keys: int64 [N, 4] = (own score, chain id, link, line bytes) of ALL output lines, every part's in its own output order;
+    owner: the part of every row. The single-process order -- own score desc, then chain id, then link (paf_cmp_by_score over the
+    chains as they were written out, impl/chaining.c:337) -- and the scan of the sizes. Returns (byte offset of every line of `rank`,
+    in that rank's output order; total bytes): global_line_offsets with chain's three keys."""
+    import torch
+
+    k = all_line_keys
+    order = torch.sort(k[:, 2], stable=True).indices
+    order = order[torch.sort(k[order, 1], stable=True).indices]
+    order = order[torch.sort(k[order, 0], descending=True, stable=True).indices]
+    sizes = k[order, 3]
+    ends = torch.cumsum(sizes, 0)
+    offs = ends - sizes
+    mine = owner[order] == rank  # a rank's lines keep their relative order: same comparator, disjoint chains
+    return offs[mine], int(ends[-1].item()) if ends.numel() else 0
+
+
+def first_failure(dist, mine, comm_device="cpu"):
+    """mine: None, or (sort key: three ints, (code, stage, record, aux)) of this rank's failure. Every rank gets the failure with the
+    smallest key over all ranks as a dict, or None when nobody failed: 64 bytes per rank."""
+    import torch
+
+    row = [0] * 8 if mine is None else [1, *mine[0], *mine[1]]
+    rows = torch.tensor([row], dtype=torch.int64, device=comm_device)
+    if dist is not None:
+        everyone = torch.zeros(dist.get_world_size(), 8, dtype=torch.int64, device=comm_device)
+        dist.all_gather_into_tensor(everyone, rows)
+        rows = everyone
+    return least_failure([(tuple(r[1:4]), tuple(r[4:])) for r in rows.cpu().tolist() if r[0]])
+
+
+def least_failure(failures):
+    """[(sort key, (code, stage, record, aux))] -> the failure with the smallest key as a dict, None for an empty list"""
+    if not failures:
+        return None
+    code, stage, record, aux = min(failures)[1]
+    return {"code": code, "stage": stage, "record": record, "aux": aux}
+
+
+def part_failure(info, fail=None):
+    """A part's PlanInfo (and the failing line's key after renumber) as first_failure / least_failure take it. read_pafs parses every
+    line before anything is chained, so stage -1 sorts before the asserts of the trim (stage 0), the lowest global record first; a
+    failed paf_check sorts by (chain id, link): the order the reference checks in (impl/chaining.c:321-334)."""
+    e = info.error
+    if not e.code:
+        return None
+    return ((fail[1], fail[2], 0) if fail else (e.stage, e.record, 0)), (e.code, e.stage, e.record, e.aux)
+
+
+class GpuChainWorker(GpuTileWorker):
+    """The device side of a rank in chain_sharded(): the partition is the tile worker's (query_names, split); the part runs through
+    the chain-in-parts calls of libpaffy_hip. opts: gap_open, gap_extend, max_gap, trim (the command's -d -e -g -t)."""
+
+    def __init__(self, eng, batch_bytes=(1 << 30) + (1 << 29), **opts):
+        super().__init__(eng, batch_bytes)
+        self.opts = opts
+        self.gidx = None
+
+    def release(self):
+        super().release()
+        self.gidx = None
+
+    def run_part(self, recv_buf, recv_gidx, pieces=None):
+        """The part over the lines this rank owns (recv_buf / pieces as for tile(); recv_gidx: the global input number of every line,
+        in the order of the pieces): every piece is added where it lies, with its slice of the numbers. Returns the PlanInfo."""
+        t = self.eng.torch
+        holder = recv_buf if isinstance(recv_buf, list) else [recv_buf]
+        recv = holder[0].to(self.eng.device)
+        self.keep = self._cut(recv, pieces) if recv.numel() else []
+        if isinstance(recv_buf, list):
+            recv_buf.clear()
+        self._recv = recv
+        del holder
+        gidx = recv_gidx.to(device=self.eng.device, dtype=t.int64).contiguous()
+        self.gidx, per_batch, at = gidx, [], 0
+        for buf, n in self.keep:  # every line ends with a newline (the splitter adds the last one)
+            lines = int((buf[:n] == 10).sum().item())
+            per_batch.append(gidx[at: at + lines])
+            at += lines
+        if at != gidx.numel():
+            raise RuntimeError(f"run_part: {gidx.numel()} record numbers for {at} lines")
+        self.info = self.eng.chain_part(self.keep, per_batch, **self.opts)
+        return self.info
+
+    def tail_keys(self):
+        return self.eng.chain_tail_keys(self.info.n_records)
+
+    def renumber(self, ids):
+        self.info, fail = self.eng.chain_renumber(ids)
+        return self.info, fail
+
+    def line_keys(self):
+        return self.eng.chain_line_keys(self.info.n_rows)
+
+    def global_records(self):
+        """The global input number of every output line, in output order (paffy_hip_plan_rows through the received numbers)."""
+        rec, _ = self.eng.plan_rows(self.info.n_rows)
+        return self.gidx[self.eng.torch.tensor(rec, dtype=self.eng.torch.int64, device=self.eng.device)] if rec else self.gidx[:0]
+
+
+def chain_sharded(worker, dist, rank, world, batches, first_record, comm_device="cpu", consume=False):
+    """`paffy chain` over an input spread over the ranks (this rank holds `batches`, whose first record is global record
+    first_record); one rank runs the same code with world = 1 and dist = None. Returns {"error": None, "offsets": byte offset of every
+    local output line in the ordered output, "total": bytes of the whole output, "keys": the [n, 4] line keys (column 3: the line
+    sizes), "chain_ids": the numbers this rank's chains got}; worker.emit() then gives the local lines. When any record of any rank
+    fails: {"error": {"code", "stage", "record", "aux"}, "total": 0, ...} -- the failure one process reports, the same on every rank --
+    and nothing is to be written."""
+    import torch
+
+    dev = worker.eng.device
+    empty = {"offsets": torch.zeros(0, dtype=torch.int64, device=comm_device), "total": 0, "keys": torch.zeros(0, 4, dtype=torch.int64, device=dev), "chain_ids": None}
+    local, per_batch = worker.query_names(batches)
+    weights = merge_name_weights(dist, local, comm_device)
+    owner_of = owner_table(weights, world)
+    try:
+        send, send_bytes, send_gidx, send_records = worker.split(batches, owner_of, world, first_record, per_batch, consume)
+    except Exception:
+        worker.eng.drop_index()  # no kept index outlives a failed partition
+        raise
+    recv, recv_gidx, pieces = exchange_lines(dist, send, send_bytes, send_gidx, send_records, comm_device, getattr(worker, "pieces", None))
+    del send
+    holder = [recv]
+    del recv
+    err = first_failure(dist, part_failure(worker.run_part(holder, recv_gidx, pieces)), comm_device)
+    if err:
+        return dict(empty, error=err, owner_of=owner_of)
+    all_tails, tail_owner = gather_tile_keys(dist, worker.tail_keys(), comm_device)
+    ids = global_chain_ids(all_tails)[tail_owner == rank]
+    err = first_failure(dist, part_failure(*worker.renumber(ids)), comm_device)
+    if err:
+        return dict(empty, error=err, owner_of=owner_of)
+    keys = worker.line_keys()
+    all_keys, owner = gather_tile_keys(dist, keys, comm_device)
+    offsets, total = chain_line_offsets(all_keys, owner, rank)
+    return {"error": None, "offsets": offsets, "total": total, "keys": keys, "chain_ids": ids, "owner_of": owner_of}
+
+
+def chain_in_parts(workers, batches, first_record=0):
+    """chain_sharded without ranks: one process, one GpuChainWorker (one context) per part on the same GPU, taken in turn -- the
+    partition with the real query_names / split_to, the keys exchanged in device memory, every part's lines scattered into one
+    buffer. Returns {"error": None, "out": uint8 tensor with the ordered output, ...} or {"error": {...}, "out": None}."""
+    import torch
+
+    k_parts, w0 = len(workers), workers[0]
+    local, per_batch = w0.query_names(batches)
+    owner_of = owner_table(local, k_parts)
+    send, send_bytes, send_gidx, send_records = w0.split(batches, owner_of, k_parts, first_record, per_batch)
+    failures, at_b, at_r = [], 0, 0
+    for w, nb, nr in zip(workers, send_bytes, send_records):  # a part's lines stand back to back in the send buffer
+        failures.append(part_failure(w.run_part(send, send_gidx[at_r: at_r + nr], [(at_b, nb)] if k_parts > 1 else w0.pieces)))
+        at_b, at_r = at_b + nb, at_r + nr
+    err = least_failure([f for f in failures if f])
+    if err:
+        return {"error": err, "out": None, "total": 0}
+    tails = [w.tail_keys() for w in workers]
+    ids = global_chain_ids(torch.cat(tails))
+    at = 0
+    for w, t in zip(workers, tails):
+        failures.append(part_failure(*w.renumber(ids[at: at + t.shape[0]])))
+        at += t.shape[0]
+    err = least_failure([f for f in failures if f])
+    if err:
+        return {"error": err, "out": None, "total": 0}
+    keys = [w.line_keys() for w in workers]
+    all_keys = torch.cat(keys)
+    owner = torch.cat([torch.full((k.shape[0],), p, dtype=torch.int64, device=k.device) for p, k in enumerate(keys)])
+    out = total = None
+    for p, (w, k) in enumerate(zip(workers, keys)):
+        offsets, total = chain_line_offsets(all_keys, owner, p)
+        if out is None:
+            out = torch.zeros(max(16, (total + 15) // 16 * 16), dtype=torch.uint8, device=all_keys.device)
+        if k.shape[0]:
+            src_off = torch.zeros(k.shape[0] + 1, dtype=torch.int64, device=k.device)
+            src_off[1:] = torch.cumsum(k[:, 3], 0)
+            w.scatter(w.emit(), src_off, offsets.contiguous(), out)
+    return {"error": None, "out": out[:total], "total": total, "chain_ids": ids, "tail_keys": tails, "line_keys": keys}

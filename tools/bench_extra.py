@@ -35,7 +35,10 @@ def main():
     ap.add_argument("--genome-gb", type=float, default=3.1, help="faffy_*: bases of the synthetic genome (24 contigs)")
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
     ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome")
+    ap.add_argument("--parts", type=int, default=0, help="chain: chain in parts -- this many contexts on the one GPU, taken in turn (0: the plain one-context run)")
     a = ap.parse_args()
+    if a.cmd == "chain" and a.parts > 0:
+        return chain_parts_bench(a)
     if a.cmd.startswith("faffy_"):
         return faffy_bench(a)
     if a.cmd == "seqload":
@@ -113,6 +116,51 @@ def main():
     print(json.dumps({**extra, "cmd": a.cmd, "records": a.records, "mean_ops": a.mean_ops, "in_bytes": nbytes, "out_bytes": int(info.out_bytes),
                       "seconds": round(dt, 4), "records_per_s": round(a.records / dt, 1),
                       "GBps": round((nbytes + info.out_bytes) / dt / 1e9, 1), "kernel_ms": prof}))
+
+
+def chain_parts_bench(a):
+    """`paffy chain` in parts (paffy_amd.shard.chain_in_parts): partition by query name, the parts one after the other on one GPU, key
+    exchange in device memory, renumber, ordered write into one buffer. The output is compared with the one-context output before
+    anything is timed. One GPU runs the parts in turn: the figure bounds the added work, it says nothing about N GPUs."""
+    import torch
+
+    import paffy_amd
+    from paffy_amd import shard
+
+    engines = [paffy_amd.Engine() for _ in range(a.parts)]
+    eng = engines[0]
+    buf, nbytes = eng.synth(0x5EED0005, a.mean_ops, 0, a.records, n_contigs=a.contigs)
+    whole = paffy_amd.Engine()
+    L = paffy_amd.engine.lib()
+    assert L.paffy_hip_chain_begin(whole._ctx) == 0 and L.paffy_hip_chain_add(whole._ctx, buf.data_ptr(), nbytes) == 0
+    info, opts = paffy_amd.engine.PlanInfo(), paffy_amd.engine.ChainOpts(5000, 1, 1000000, 1.0)
+    assert L.paffy_hip_chain_run(whole._ctx, opts, info) == 0 and info.error.code == 0
+    want = whole.alloc_out(info.out_bytes)
+    whole.emit(want)
+    whole.sync()
+    workers = [shard.GpuChainWorker(e) for e in engines]
+    res = shard.chain_in_parts(workers, [(buf, nbytes)])
+    torch.cuda.synchronize()
+    assert res["error"] is None and res["total"] == info.out_bytes and torch.equal(res["out"], want[: info.out_bytes]), "the parts do not write the one-context output"
+    del want
+    whole.close()
+    times = []
+    for rep in range(4):
+        if rep == 1:
+            for e in engines:
+                e.profile(True)  # the first repetition warms up
+        t0 = time.perf_counter()
+        res = shard.chain_in_parts(workers, [(buf, nbytes)])
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    dt = min(times[1:])
+    prof = {}
+    for e in engines:
+        for k, v in e.profile_read().items():
+            prof[k] = (prof.get(k, (0.0, 0))[0] + v[0], max(prof.get(k, (0.0, 0))[1], v[1]))
+    print(json.dumps({"cmd": "chain", "parts": a.parts, "records": a.records, "mean_ops": a.mean_ops, "in_bytes": nbytes, "out_bytes": int(res["total"]),
+                      "chains": int(res["chain_ids"].numel()), "verified_against_one_context": True, "seconds": round(dt, 4), "records_per_s": round(a.records / dt, 1),
+                      "GBps": round((nbytes + res["total"]) / dt / 1e9, 1), "kernel_ms_all_parts_per_run": {k: round(ms / max(1, cnt), 3) for k, (ms, cnt) in prof.items()}}))
 
 
 def synth_genome(torch, dev, gb, n_contigs=24, seed=0x5EED00FA):
