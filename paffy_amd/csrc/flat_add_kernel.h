@@ -229,7 +229,10 @@ __global__ __launch_bounds__(256) void k_add_final(AddParams A) {
             n_seg += seg_ops ? 1u : 0u;
             if (fits) {
                 item0 = atomicAdd(&P.info->n_items, n_seg);
-                if (item0 + n_seg > P.items_cap) fits = false;
+                if (item0 + n_seg > P.items_cap) { /* no room: the reserved slots inside the list name no record (the writers skip them) */
+                    for (uint32_t g = item0; g < P.items_cap && g < item0 + n_seg; g++) P.items[g].rec = FLAT_NO_CHUNK;
+                    fits = false;
+                }
             }
         }
         if (fits) {

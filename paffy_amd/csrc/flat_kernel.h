@@ -1490,7 +1490,11 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
     if (itemised) {
         if (lane == 0) item0 = atomicAdd(&P.info->n_items, n_seg);
         item0 = uni(item0);
-        if (item0 + n_seg > P.items_cap) return flat_leave(F, rec, FLAT_WHY_ROW_SHAPE); /* cannot happen: the host sizes the list for every op of the text */
+        if (item0 + n_seg > P.items_cap) { /* cannot happen: the host sizes the list for every op of the text; the reserved slots name no record */
+            if (lane == 0)
+                for (uint32_t g = item0; g < P.items_cap && g < item0 + n_seg; g++) P.items[g].rec = FLAT_NO_CHUNK;
+            return flat_leave(F, rec, FLAT_WHY_ROW_SHAPE);
+        }
     }
     const bool four_waves = !shatter && !line_kernel && !copy;
     if (lane == 0) {

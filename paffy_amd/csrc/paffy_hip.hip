@@ -1658,7 +1658,14 @@ static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records)
         ap.text_cnt = static_cast<uint32_t *>(c->add_text.p);
         ap.rec_bad = static_cast<uint32_t *>(c->add_bad.p);
         ap.flat_done = static_cast<uint8_t *>(c->flat_done.p);
-        { /* segments of the lines that become more than PAFFY_ROWS_MAX_OPS ops */
+        { /* segments of the lines that become more than PAFFY_ROWS_MAX_OPS ops. A segment closes only when the next piece would take it
+             past ADD_SEG_OPS (16 384), so two neighbouring segments hold more than 16 384 new ops and a line of T new ops has at most
+             T / 8192 + 1 segments. new_words / 8192 covers the first term of every line; the list runs out only when more lines than
+             len / 16 384 + 64 + (new_words - total) / 8192 use their "+ 1". A line does that with five segments over a little more than
+             32 768 new ops (pieces of about 0, 16 400, 200, 16 400, 200 new ops), which takes 3 KiB of text: 4.03 x 1.125 + 0.19 < 5
+             once the second try has sized new_words to 1.125 x total, so some 250 such lines in a batch overflow it. That is left so:
+             k_add_final gives the lines that find no room to the record kernels, marks the slots they reserved inside the list, and
+             n_items is cut to the list below (test_gpu_flat_edges.py::test_add_item_list_overflow_goes_to_the_record_kernels). */
             const size_t items_cap = new_words / (PAFFY_ROWS_MAX_OPS / 4u) + ((size_t)len >> 14) + 64;
             if (ensure(c, c->flat_items, sizeof(EmitItem) * items_cap)) return PAFFY_E_HIP;
             kp.items = static_cast<EmitItem *>(c->flat_items.p);
@@ -1681,7 +1688,7 @@ static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records)
         kp.new_ops = ap.new_ops;
         if (post_scans(c, n_lines)) return PAFFY_E_HIP;
         if (fetch_info(c)) return PAFFY_E_HIP;
-        kp.n_items = c->h_info->n_items;
+        kp.n_items = std::min(c->h_info->n_items, kp.items_cap); /* reservations past the list's end were not written (k_add_final) */
         if (c->h_info->add_scr_total <= ap.scr_cap && c->h_info->add_new_total <= ap.new_cap) break;
         if (attempt == 2) {
             c->last_error = "add_mismatches: the scratch demand kept growing";
@@ -1736,7 +1743,7 @@ static int plan_flat(paffy_hip_ctx *c, const StageClass &s, uint32_t n_lines, bo
     if (post_scans(c, n_lines)) return PAFFY_E_HIP;
     if (fetch_info(c)) return PAFFY_E_HIP;
     *g_count = c->h_info->g_count;
-    kp.n_items = c->h_info->n_items;
+    kp.n_items = std::min(c->h_info->n_items, kp.items_cap);
     *need_records = c->h_info->flat_legacy > 0;
     c->flat_left = c->h_info->flat_legacy;
     for (int k = 0; k < 16; k++) c->flat_reasons[k] = c->h_info->flat_reason[k];

@@ -3684,6 +3684,7 @@ __global__ __launch_bounds__(64, PAFFY_ROWS_OCC) void k_emit_rows(KParams P) {
     } else {
         rec = P.emit_order ? P.emit_order[blockIdx.x - P.n_items] : blockIdx.x - P.n_items; /* long records first */
     }
+    if (rec >= P.n_rec) return; /* a slot of the item list that a record reserved and could not use */
     if (rec >= (uint32_t)(P.info->first_err_key >> 16)) return; /* nothing at or after the first failure */
     if ((P.status[rec] >> 16) != KLASS_LDS) return;
     const RecPlan &pl = static_cast<const RecPlan *>(P.rec_plan)[rec];
@@ -3747,6 +3748,7 @@ __global__ __launch_bounds__(64, PAFFY_EMIT_OCC) void k_emit_line(KParams P) {
     } else {
         rec = P.emit_order ? P.emit_order[blockIdx.x - P.n_items] : blockIdx.x - P.n_items; /* long records first */
     }
+    if (rec >= P.n_rec) return; /* a slot of the item list that a record reserved and could not use */
     if (rec >= (uint32_t)(P.info->first_err_key >> 16)) return;
     if ((P.status[rec] >> 16) != KLASS_LDS) return;
     const RecPlan &pl = static_cast<const RecPlan *>(P.rec_plan)[rec];

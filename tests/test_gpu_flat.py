@@ -3,7 +3,9 @@ text whatever record they belong to, and sized per record from the pieces' summa
 every offset inside a 1 KiB tile and ops whose digits straddle tile and chunk boundaries, what the pass leaves to the record kernels
 (numbers of five digits or with leading zeros, lengths of 8 192 and more, zero lengths, = and X ops, bad characters, a cigar that ends
 in digits, failing checks) next to records it keeps, records of more than 64 pieces (their summaries are scanned in place), trims that
-cut deep into a record, and the very long records of SURVEY section 5 (about 100 000 and 1 000 000 ops; impl/paf.c:398-403)."""
+cut deep into a record, and the very long records of SURVEY section 5 (about 100 000 and 1 000 000 ops; impl/paf.c:398-403): with names
+the one-wave row writer takes (the flat pass sizes them itself, as segments of FLAT_SEG_OPS ops) and with names it does not (the record
+kernels' arena class), segment counts to either side of every multiple of FLAT_SEG_OPS, and the item list from one plan to the next."""
 import hashlib
 import os
 import random
@@ -66,17 +68,74 @@ def random_ops(rng, n, lens=(1, 2, 3, 7, 12, 40, 99, 150, 1234), indel=(1, 2, 3,
     return ops
 
 
-def run_both(eng, data, pipes=LEAN_PIPES, params=None):
+_ORACLE = {}  # (pipe, parameters, digest of the input) -> (error code, error record, length, digest) of the oracle's output
+
+
+def oracle_digest(pipe, params, data):
+    key = (tuple(pipe), repr(sorted((params or {}).items())), hashlib.sha256(data).hexdigest())
+    if key not in _ORACLE:
+        want, werr = O.run([O.stage(k, *(params or {}).get(k, ())) for k in pipe], data)
+        _ORACLE[key] = (werr.code, werr.record, len(want), hashlib.sha256(want).hexdigest())
+    return _ORACLE[key]
+
+
+def run_both(eng, data, pipes=LEAN_PIPES, params=None, kept=False, want_left=None):
+    """error code, length and SHA-256 of the whole output against the oracle's, pipe by pipe. kept: the flat pass must have sized every
+    record itself (none left to the record kernels); want_left: (records left, reason index) instead"""
     import paffy_amd
 
     for pipe in pipes:
-        ost = [O.stage(k, *(params or {}).get(k, ())) for k in pipe]
         gst = [paffy_amd.stage(k, *(params or {}).get(k, ())) for k in pipe]
-        want, werr = O.run(ost, data)
+        wcode, wrec, wlen, wsha = oracle_digest(pipe, params, data)
         got, info = eng.run(gst, data, raise_on_error=False)
-        STATS.append((os.environ.get("PYTEST_CURRENT_TEST", "").split("::")[-1].split(" ")[0], tuple(pipe), eng.flat_stats()))
-        assert info.error.code == werr.code, (pipe, info.error.code, werr.code, info.error.record, werr.record)
-        assert len(got) == len(want) and hashlib.sha256(got).hexdigest() == hashlib.sha256(want).hexdigest(), pipe
+        left, why = eng.flat_stats()
+        STATS.append((os.environ.get("PYTEST_CURRENT_TEST", "").split("::")[-1].split(" ")[0], tuple(pipe), (left, why)))
+        print("flat stats", STATS[-1])
+        assert info.error.code == wcode, (pipe, info.error.code, wcode, info.error.record, wrec)
+        assert len(got) == wlen and hashlib.sha256(got).hexdigest() == wsha, (pipe, len(got), wlen)
+        if kept:
+            assert left == 0, (pipe, left, list(why))
+        if want_left is not None:
+            assert left == want_left[0] and why[want_left[1]] == want_left[0], (pipe, left, list(why))
+
+
+def exact_ops(rng, n, **kw):
+    """random_ops of exactly n ops (random_ops closes an even count with one more M op)"""
+    ops = random_ops(rng, n if n % 2 else n - 1, **kw)
+    if len(ops) < n:
+        ops.append((7, "M"))
+    assert len(ops) == n
+    return ops
+
+
+def cigar_of(out_line):
+    return out_line.split(b"cg:Z:")[1].split(b"\t")[0].strip()
+
+
+def n_ops_of(cigar):
+    return sum(cigar.count(c) for c in b"MID=X")
+
+
+def trimmed_to(seed, want, strand, measure, make_core, n_front=400, n_back=300, **kw):
+    """A record of noisy ends round a clean core whose identity trim (default thresholds) leaves exactly measure(cigar left) == want,
+    proven on the oracle: the core (make_core(rng, size)) is resized until it does. Returns (line, ops)."""
+    for attempt in range(6):  # (a resizing that ends up going back and forth starts again from other ends)
+        size = want
+        for _ in range(8):
+            rng = random.Random(seed + 1000 * attempt)
+            front = [(1, "M") if i % 2 == 0 else (30, "ID"[i // 2 % 2]) for i in range(n_front + 2 * attempt)]
+            back = [(30, "ID"[i // 2 % 2]) if i % 2 == 0 else (1, "M") for i in range(n_back + 2 * attempt)]
+            ops = front + make_core(rng, size) + back
+            line = record(ops, strand, rng=rng, **kw)
+            out, err = O.run([O.stage(O.TRIM_IDENTITY)], line.encode())
+            if err.code:  # the trim's own assert on this record: other ends
+                break
+            got = measure(cigar_of(out))
+            if got == want:
+                assert got < measure("".join(f"{L}{c}" for L, c in ops).encode())  # the trim did cut
+                return line, ops
+            size -= got - want
+    raise AssertionError(want)
 
 
 def test_every_tile_offset_and_boundary_straddles(eng):
@@ -173,17 +232,90 @@ def test_records_of_more_than_64_pieces(eng):
     run_both(eng, "".join(recs).encode())
 
 
+SHATTER_LONG_PIPES = ([O.SHATTER], [O.INVERT, O.TRIM_IDENTITY, O.SHATTER], [O.INVERT], [O.TRIM_IDENTITY], [O.INVERT, O.INVERT, O.SHATTER])
+WHY_ROW_SHAPE = 8  # FLAT_WHY_ROW_SHAPE of flat_kernel.h
+
+
+def long_ops(rng, n_ops):
+    """n_ops ops: a quarter of long M ops at either end, short ones between (a fixed trim of half the aligned bases leaves most of the text)"""
+    q = n_ops // 4
+    return (exact_ops(rng, q, lens=(60, 110)) + [(1, "I")] + exact_ops(rng, n_ops - 2 * q - 2, lens=(1, 5, 30)) + [(1, "D")] + exact_ops(rng, q, lens=(60, 110)))
+
+
+def long_batch(n_ops, inside=True):
+    """a long record and a short one on either strand; inside: names the one-wave row writer takes (first row piece of 18 bytes before and
+    after an invert), else the names of 1 and 46 characters it does not (pieces of 12 and 57 bytes). The coordinates cross no power of ten."""
+    rng = random.Random(4107 + n_ops)
+    names = (("hs.chr3", "pt.chr9"), ("hs.chr3", "pt.chr9")) if inside else (("q", "t"), ("hs.chr" + "Q" * 40, "pt.chr" + "T" * 44))
+    recs, longs = [], []
+    for strand, (qn, tn) in zip("+-", names):
+        recs.append(record(random_ops(rng, 50), strand, rng=rng))
+        longs.append(record(long_ops(rng, n_ops), strand, qname=qn, tname=tn, qs=120_000_000 + rng.randrange(1000), ts=110_000_000 + rng.randrange(1000)))
+        recs.append(longs[-1])
+    return "".join(recs).encode(), longs
+
+
 @pytest.mark.parametrize("n_ops", [100_001, 1_000_001])
 def test_very_long_records(eng, n_ops):
-    """real lines reach megabytes -- one record of about 100 000 ops and one of about 1 000 000 (the reference grows its
-    buffers by doubling, impl/paf.c:398-403), both strands, long and short names, through the stream pipes"""
-    rng = random.Random(4107 + n_ops)
+    """real lines reach megabytes -- one record of 100 001 ops and one of 1 000 001 (the reference grows its buffers by
+    doubling, impl/paf.c:398-403), both strands. With names inside the one-wave row writer's gate (row pieces of 16 to 48 bytes) the flat
+    pass sizes every record itself: the shatter pipes cut the record into segments of FLAT_SEG_OPS ops (EmitItem, k_emit_rows), and no
+    record may leave. A fixed trim with a fraction that leaves most of the record (the oracle's output is checked to be longer than half
+    the cigar). With names outside the gate exactly the two long records leave the shatter pipes, with reason FLAT_WHY_ROW_SHAPE: the
+    record kernels' arena class writes them -- the cliff is pinned here, so removing the gate has to change this test."""
+    data, longs = long_batch(n_ops)
+    assert all(n_ops_of(cigar_of(l.encode())) == n_ops for l in longs)
+    run_both(eng, data, pipes=SHATTER_LONG_PIPES, kept=True)
+    for f in (0.1, 0.5):
+        params = {O.TRIM_FIXED: (0.05, f)}
+        for pipe in ([O.TRIM_FIXED], [O.INVERT, O.TRIM_FIXED]):
+            want, werr = O.run([O.stage(k, *params.get(k, ())) for k in pipe], data)
+            assert werr.code == 0
+            for src, line in zip(longs, want.splitlines()[1::2]):
+                assert len(cigar_of(line)) > len(cigar_of(src.encode())) // 2, (f, len(cigar_of(line)), len(cigar_of(src.encode())))
+        run_both(eng, data, pipes=([O.TRIM_FIXED], [O.INVERT, O.TRIM_FIXED]), params=params, kept=True)
+    outside, _ = long_batch(n_ops, inside=False)
+    run_both(eng, outside, pipes=([O.SHATTER], [O.INVERT, O.TRIM_IDENTITY, O.SHATTER], [O.INVERT, O.INVERT, O.SHATTER]), want_left=(2, WHY_ROW_SHAPE))
+    run_both(eng, outside, pipes=([O.INVERT], [O.TRIM_IDENTITY]), kept=True)
+
+
+SEG = 16_384  # FLAT_SEG_OPS of flat_kernel.h: ops of a segment of a long shatter record (PAFFY_ROWS_MAX_OPS is 32 768)
+
+
+def test_segment_counts_either_side_of_every_boundary(eng):
+    """Shatter records of k x 16 384 - 1, k x 16 384 and k x 16 384 + 1 ops for k = 2, 3, 4, 61 and of 1 000 000 ops exactly: the last
+    segment of a record holds one op, a whole segment, or does not exist (k = 2: the one-wave row writer takes 32 767 and 32 768 ops whole,
+    32 769 go as three segments). Both strands; the same counts as what an identity trim leaves of a longer record with noisy ends (the
+    count is proven on the oracle); and two long records whose query / target range crosses a power of ten in the middle (the rows behind it
+    have a digit more: flat_cross_digits on segments). Every record stays with the flat pass."""
+    rng = random.Random(4110)
+    counts = [k * SEG + d for k in (2, 3, 4, 61) for d in (-1, 0, 1)] + [1_000_000]
     recs = []
-    for strand, qn, tn in (("+", "q", "t"), ("-", "hs.chr" + "Q" * 40, "pt.chr" + "T" * 44)):
-        recs.append(record(random_ops(rng, 50), strand, rng=rng))
-        recs.append(record(random_ops(rng, n_ops, lens=(1, 5, 30, 60, 110)), strand, qname=qn, tname=tn, rng=rng))
-    data = "".join(recs).encode()
-    run_both(eng, data, pipes=([O.SHATTER], [O.INVERT, O.TRIM_IDENTITY, O.SHATTER], [O.INVERT], [O.TRIM_IDENTITY], [O.TRIM_FIXED]))
+    for i, n in enumerate(counts):
+        recs.append(record(exact_ops(rng, n, lens=(1, 5, 30, 60, 110)), "+-"[i & 1], qs=120_000_000 + 7 * i, ts=110_000_000 + 3 * i))
+        recs.append(record(random_ops(rng, 40), "+-"[i & 1], rng=rng))
+    recs.append(record(exact_ops(rng, 4 * SEG + 5, lens=(60, 110)), "-", qs=100_000_000 - 1_400_000, ts=110_000_000))  # query crosses 10^8
+    recs.append(record(exact_ops(rng, 5 * SEG + 1, lens=(60, 110)), "+", qs=120_000_000, ts=100_000_000 - 1_500_000))  # target crosses 10^8
+    for line in recs[-2:]:
+        c = line.split("\t")
+        assert int(c[2]) < 10 ** 8 - 500_000 and int(c[3]) > 10 ** 8 + 500_000 or int(c[7]) < 10 ** 8 - 500_000 and int(c[8]) > 10 ** 8 + 500_000
+    run_both(eng, "".join(recs).encode(), pipes=([O.SHATTER], [O.INVERT, O.SHATTER]), kept=True)
+    trimmed = []
+    for i, n in enumerate([2 * SEG, 2 * SEG + 1, 3 * SEG - 1, 4 * SEG]):
+        line, _ = trimmed_to(4111 + i, n, "+-"[i & 1], n_ops_of, lambda r, k: exact_ops(r, k, lens=(40, 99, 150, 1234), indel=(1, 2)), qs=120_000_000, ts=110_000_000)
+        trimmed.append(line)
+    run_both(eng, "".join(trimmed).encode(), pipes=([O.TRIM_IDENTITY, O.SHATTER],), kept=True)
+
+
+def test_item_list_from_one_plan_to_the_next(eng):
+    """the 1 000 001-op batch (124 segments), then 300 short records (no segment), then the long batch again, on one engine: the number of
+    items and the list itself are the plan's own, nothing of the plan before is read"""
+    rng = random.Random(4112)
+    long_data, _ = long_batch(1_000_001)
+    short = "".join(record(random_ops(rng, rng.choice((1, 3, 40, 300))), "+-"[k & 1], rng=rng) for k in range(300)).encode()
+    pipes = ([O.SHATTER], [O.INVERT, O.TRIM_IDENTITY, O.SHATTER])
+    for data in (long_data, short, long_data, short):
+        run_both(eng, data, pipes=pipes, kept=True)
 
 
 def test_no_flat_switch_gives_the_same_bytes(eng, human_chimp):
