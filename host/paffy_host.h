@@ -60,7 +60,11 @@ void host_set_stats_lines(FILE *fh);
 int host_tile(FILE *in, FILE *out);
 /* `paffy to_bed`: reads all of `in`, one bed_plan + emit, writes `out` */
 int host_to_bed(FILE *in, FILE *out, const paffy_bed_opts *opts);
-/* `paffy chain`: reads all of `in`, chains on the GPU, writes the records with their cn / s1 tags by descending score */
+/* `paffy chain`: reads all of `in`, chains on the GPU, writes the records with their cn / s1 tags by descending score. Under the N-GPU
+ * launcher (PAFFY_CHAIN_PART=<file prefix of the part>, PAFFY_CHAIN_FDS=<from_launcher>,<to_launcher>: two inherited pipe descriptors)
+ * `in` is one part of an input partitioned by query name: the records carry the global numbers of <part>.idx, the chain keys go to
+ * <part>.tails, the chain numbers come from <part>.ids, the line keys go to <part>.lkeys, and a failure is reported up the pipe and
+ * printed only when the launcher says that it is the one the whole run ends with (host/paffy_stream.c, host/paffy_launch.c). */
 int host_chain(FILE *in, FILE *out, const paffy_chain_opts *opts);
 /* paffy split_file: normalised lines (cigar text verbatim) routed to "<prefix><contig>.paf" / "<prefix>small_<k>.paf" */
 int host_split_file(FILE *in, const char *prefix, int by_query, int64_t min_length);

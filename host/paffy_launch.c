@@ -15,17 +15,35 @@
  *     global line number, each worker tiles its sequences, and the outputs -- each already in (s1 desc, AS desc, input order) order
  *     (paf_cmp_by_descending_score, impl/paf_tile.c:28-34) -- are merged by that same key. A failing record means no output at all,
  *     as in the reference (it writes after the last record).
+ *   chain: records link inside one (query, target, strand) only (impl/chaining.c:37-54), so the partition is tile's (by query name,
+ *     every line with its global line number). Three things are global and are settled here, on the host, from 32 bytes per chain and
+ *     per line that every worker leaves in key files next to its spools:
+ *       the failure that ends the run -- every worker holds its message back and reports (stage, record) after the chaining,
+ *         (chain id, link) after paf_check; the launcher picks the least and only that worker speaks and sets the status;
+ *       the chain numbers (cn) -- <rank>.tails: (strand class, chain-end score, processing key, global record) per chain; all chains
+ *         are ranked by (class asc, score desc, key desc, number desc) and every worker gets <rank>.ids, one int64 per chain;
+ *       the order of the lines -- <rank>.lkeys: (own score, chain id, link, bytes) per output line; the output is the K-way merge of
+ *         the <rank>.out files by (own score desc, chain id asc, link asc), every line's length taken from its key.
+ *     A chain worker is told its part by PAFFY_CHAIN_PART=<spooldir>/<rank> (it reads <part>.idx and <part>.ids, writes <part>.tails
+ *     and <part>.lkeys) and talks over two inherited pipe descriptors, PAFFY_CHAIN_FDS=<from_launcher>,<to_launcher>: after each of the
+ *     two phases it writes one record of eight int64 {phase, failed, sort key x 3, count, 0, 0} and reads one int64 verdict (0: go on,
+ *     1: you are the failure -- say so and end as the reference would, 2: end silently). A worker that dies before it reports shows as
+ *     end-of-file on its pipe: the run ends with that worker's status and nothing is written; a worker that reads end-of-file instead
+ *     of a verdict exits. Nothing is written before both phases have passed everywhere (impl/paf_chain.c:128-132 writes last).
  * Everything between the workers goes through files under PAFFY_TMPDIR (default /dev/shm, else TMPDIR, else /tmp): host-mediated, no
  * GPU-to-GPU traffic -- a CLI's input comes from the host and its output goes back there. Other commands run on one GPU.
  *
  * Environment: PAFFY_GPUS=N; PAFFY_ONE_DEVICE=1 (rehearsal: every worker uses device 0); PAFFY_WORKER=path (another worker binary:
- * the CPU tests put a stand-in there); PAFFY_TMPDIR.
+ * the CPU tests put a stand-in there); PAFFY_TMPDIR. Set for the workers: PAFFY_RANK, PAFFY_WORLD, PAFFY_DEVICE, PAFFY_RANGE (stream),
+ * PAFFY_ROWS_FILE (tile), PAFFY_CHAIN_PART and PAFFY_CHAIN_FDS (chain).
  */
 #define _GNU_SOURCE
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
 #include <limits.h>
+#include <strings.h>
+#include <time.h>
 #include <signal.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -42,14 +60,16 @@
 static char g_worker[PATH_MAX];
 static char g_tmpdir[PATH_MAX];  /* where the private spool directory is made */
 static char g_spooldir[PATH_MAX]; /* mkdtemp(<tmpdir>/paffy.XXXXXX), mode 0700: nobody else can plant a link under a name we open */
-static char g_spool[MAX_RANKS][4][PATH_MAX]; /* per rank: input, output, rows, index */
+enum { SP_IN, SP_OUT, SP_ROWS, SP_IDX, SP_TAILS, SP_IDS, SP_LKEYS, SPOOL_KINDS };
+static const char *const k_spool_ext[SPOOL_KINDS] = {"in", "out", "rows", "idx", "tails", "ids", "lkeys"};
+static char g_spool[MAX_RANKS][SPOOL_KINDS][PATH_MAX]; /* per rank: input, output, rows (tile), index, and chain's tail keys, chain ids, line keys */
 static char g_stdin_spool[PATH_MAX];
 static int g_n = 0;
 static volatile pid_t g_pids[MAX_RANKS]; /* workers that are running (0: none) */
 
 static void cleanup(void) {
     for (int r = 0; r < g_n; r++)
-        for (int k = 0; k < 4; k++)
+        for (int k = 0; k < SPOOL_KINDS; k++)
             if (g_spool[r][k][0]) unlink(g_spool[r][k]);
     if (g_stdin_spool[0]) unlink(g_stdin_spool);
     if (g_spooldir[0]) rmdir(g_spooldir);
@@ -108,8 +128,8 @@ static int is_stream_cmd(const char *c) {
 
 /*
  * The command line of a sharded command, parsed the way the worker will parse it: getopt_long with the subcommand's own option string
- * and long options (/root/reference/impl/paf_invert.c:41-76, paf_trim.c:45-100, paf_add_mismatches.c:40-85, paf_filter.c:50-115,
- * paf_tile.c:100-150, paf_dechunk.c:55-66, paf_upconvert.c:84-91) -- clustered short flags (`trim -fi in.paf`), abbreviated long
+ * and long options (impl/paf_invert.c:41-76, paf_trim.c:45-100, paf_add_mismatches.c:40-85, paf_filter.c:50-115,
+ * paf_tile.c:100-150, paf_dechunk.c:55-66, paf_upconvert.c:84-91, paf_chain.c:62-73) -- clustered short flags (`trim -fi in.paf`), abbreviated long
  * options (`--input x`), an option's value that looks like an option (`-l -i`) all mean here what they mean there. The worker's command line is rebuilt from the parse: every
  * option but -i / -o as the worker would have seen it, then the positional arguments, then our own -i / -o. Anything getopt_long
  * rejects, and -h, leaves the command to a single worker (which prints what the reference prints).
@@ -142,6 +162,10 @@ static const struct option k_dechunk[] = {{"logLevel", required_argument, 0, 'l'
 static const struct option k_upconvert[] = {{"logLevel", required_argument, 0, 'l'}, {"inFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
                                             {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
 
+static const struct option k_chain[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
+                                        {"maxGapLength", required_argument, 0, 'g'}, {"trimFraction", required_argument, 0, 't'}, {"chainGapOpen", required_argument, 0, 'd'},
+                                        {"chainGapExtend", required_argument, 0, 'e'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+
 static void parse_cmdline(int argc, char **argv, CmdLine *cl) {
     memset(cl, 0, sizeof(*cl));
     const char *cmd = argv[1];
@@ -152,6 +176,7 @@ static void parse_cmdline(int argc, char **argv, CmdLine *cl) {
     else if (!strcmp(cmd, "filter")) { optstring = "l:i:o:s:t:u:v:w:xh"; lopts = k_filter; }
     else if (!strcmp(cmd, "dechunk")) { optstring = "l:i:o:hqt"; lopts = k_dechunk; }
     else if (!strcmp(cmd, "upconvert")) { optstring = "l:o:hi:"; lopts = k_upconvert; }
+    else if (!strcmp(cmd, "chain")) { optstring = "l:i:o:hg:t:d:e:"; lopts = k_chain; }
     /* getopt_long permutes the array it is given: a copy of argv[1..] (argv[1], the subcommand, stands where the program name would) */
     char **v = (char **)calloc((size_t)argc + 1, sizeof(char *));
     for (int i = 1; i < argc; i++) v[i - 1] = argv[i];
@@ -217,7 +242,14 @@ static char **worker_argv(const char *cmd, const CmdLine *cl, const char *in_pat
     return v;
 }
 
-static pid_t spawn(char **wargv, int rank, int world, int one_device, const char *range, const char *rows_path) {
+/* chain: the part's file prefix and the two pipe ends of this worker (every pipe end is close-on-exec: a worker holds its own two only,
+   so the death of a worker is end-of-file on its pipe whatever the others do) */
+typedef struct {
+    const char *part;
+    int from_launcher, to_launcher;
+} ChainLink;
+
+static pid_t spawn(char **wargv, int rank, int world, int one_device, const char *range, const char *rows_path, const ChainLink *link) {
     pid_t pid = fork();
     if (pid != 0) return pid;
     char b[64];
@@ -232,6 +264,16 @@ static pid_t spawn(char **wargv, int rank, int world, int one_device, const char
     else unsetenv("PAFFY_RANGE");
     if (rows_path) setenv("PAFFY_ROWS_FILE", rows_path, 1);
     else unsetenv("PAFFY_ROWS_FILE");
+    if (link) {
+        snprintf(b, sizeof(b), "%d,%d", link->from_launcher, link->to_launcher);
+        setenv("PAFFY_CHAIN_PART", link->part, 1);
+        setenv("PAFFY_CHAIN_FDS", b, 1);
+        fcntl(link->from_launcher, F_SETFD, 0);
+        fcntl(link->to_launcher, F_SETFD, 0);
+    } else {
+        unsetenv("PAFFY_CHAIN_PART");
+        unsetenv("PAFFY_CHAIN_FDS");
+    }
     execv(wargv[0], wargv);
     fprintf(stderr, "paffy: cannot start the worker %s: %s\n", wargv[0], strerror(errno));
     _exit(127);
@@ -281,11 +323,11 @@ static int run_stream(const char *cmd, const CmdLine *cl, int n, int one_device,
     close(fd);
     pid_t pids[MAX_RANKS];
     for (int r = 0; r < n; r++) {
-        snprintf(g_spool[r][1], PATH_MAX, "%s/%d.out", g_spooldir, r);
+        snprintf(g_spool[r][SP_OUT], PATH_MAX, "%s/%d.out", g_spooldir, r);
         char range[64];
         snprintf(range, sizeof(range), "%lld:%lld", (long long)cut[r], (long long)cut[r + 1]);
-        char **wv = worker_argv(cmd, cl, in_path, g_spool[r][1]);
-        pids[r] = spawn(wv, r, n, one_device, range, NULL);
+        char **wv = worker_argv(cmd, cl, in_path, g_spool[r][SP_OUT]);
+        pids[r] = spawn(wv, r, n, one_device, range, NULL, NULL);
         free(wv);
         if (pids[r] < 0) {
             fprintf(stderr, "paffy: fork failed\n");
@@ -307,7 +349,7 @@ static int run_stream(const char *cmd, const CmdLine *cl, int n, int one_device,
         int st = 0;
         while (waitpid(pids[r], &st, 0) < 0 && errno == EINTR) {}
         g_pids[r] = 0;
-        int sfd = open(g_spool[r][1], O_RDONLY | O_NOFOLLOW);
+        int sfd = open(g_spool[r][SP_OUT], O_RDONLY | O_NOFOLLOW);
         if (sfd >= 0) {
             if (copy_fd(sfd, out_fd) != 0) rc = 1;
             close(sfd);
@@ -439,11 +481,16 @@ static const void *map_file(const char *path, size_t *len) {
     return p == MAP_FAILED ? NULL : p;
 }
 
-static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path) {
+/*
+ * The partition by query name that tile and chain share: two passes over the input (bytes of every query name; heaviest name to the
+ * lightest worker, contig_partition of paffy_amd/shard.py), every line to <rank>.in and its global line number to <rank>.idx.
+ * spooled[r]: the lines worker r got. 0, or 1 after a message.
+ */
+static int partition_by_query(const char *cmd, int n, const char *in_path, int64_t *spooled) {
     size_t in_len = 0;
     const char *in = (const char *)map_file(in_path, &in_len);
     if (!in) {
-        fprintf(stderr, "paffy tile: cannot open %s\n", in_path);
+        fprintf(stderr, "paffy %s: cannot open %s\n", cmd, in_path);
         return 1;
     }
     /* pass 1: the bytes of every query name's lines */
@@ -456,7 +503,7 @@ static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_pat
         tab_find(&tab, name_hash(p, nlen), 1)->weight += (int64_t)(le - p);
         p = le;
     }
-    /* heaviest name to the lightest worker (contig_partition of paffy_amd/shard.py) */
+    /* heaviest name to the lightest worker */
     {
         NameSlot **order = (NameSlot **)malloc(sizeof(NameSlot *) * (tab.used + 1));
         size_t m = 0;
@@ -476,18 +523,17 @@ static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_pat
     /* pass 2: every line to its worker's spool, with its global line number */
     FILE *fin[MAX_RANKS], *fidx[MAX_RANKS];
     for (int r = 0; r < n; r++) {
-        const char *ext[4] = {"in", "out", "rows", "idx"};
-        for (int k = 0; k < 4; k++) snprintf(g_spool[r][k], PATH_MAX, "%s/%d.%s", g_spooldir, r, ext[k]);
-        fin[r] = fopen(g_spool[r][0], "wx"); /* O_EXCL: inside our own 0700 directory nothing can be there */
-        fidx[r] = fopen(g_spool[r][3], "wx");
+        for (int k = 0; k < SPOOL_KINDS; k++) snprintf(g_spool[r][k], PATH_MAX, "%s/%d.%s", g_spooldir, r, k_spool_ext[k]);
+        fin[r] = fopen(g_spool[r][SP_IN], "wx"); /* O_EXCL: inside our own 0700 directory nothing can be there */
+        fidx[r] = fopen(g_spool[r][SP_IDX], "wx");
         if (!fin[r] || !fidx[r]) {
-            fprintf(stderr, "paffy tile: cannot write under %s\n", g_tmpdir);
+            fprintf(stderr, "paffy %s: cannot write under %s\n", cmd, g_tmpdir);
             return 1;
         }
         setvbuf(fin[r], NULL, _IOFBF, 1 << 22);
+        spooled[r] = 0;
     }
     uint64_t line_no = 0;
-    int64_t spooled[MAX_RANKS] = {0}; /* lines routed to each worker */
     for (const char *p = in, *end = in + in_len; p < end; line_no++) {
         const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
         const char *le = nl ? nl + 1 : end;
@@ -502,12 +548,18 @@ static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_pat
     }
     int werr = 0;
     for (int r = 0; r < n; r++) werr |= fclose(fin[r]) | fclose(fidx[r]);
-    munmap((void *)in, in_len);
+    if (in_len) munmap((void *)in, in_len);
     free(tab.slot);
     if (werr) {
-        fprintf(stderr, "paffy tile: writing the spools under %s failed\n", g_tmpdir);
+        fprintf(stderr, "paffy %s: writing the spools under %s failed\n", cmd, g_tmpdir);
         return 1;
     }
+    return 0;
+}
+
+static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path) {
+    int64_t spooled[MAX_RANKS]; /* lines routed to each worker */
+    if (partition_by_query("tile", n, in_path, spooled) != 0) return 1;
     /* the workers: one per GPU that has lines to tile. Fewer query names than GPUs (one per-contig split of the input is the reference's
        own workflow, tests/paf_pipeline_test.sh:42-67) or an empty input leave workers without a line: they are not started, and the
        merge below has nothing to take from them -- the reference writes an empty output and exits 0 for an empty input */
@@ -515,8 +567,8 @@ static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_pat
     for (int r = 0; r < n; r++) {
         pids[r] = 0;
         if (spooled[r] == 0) continue;
-        char **wv = worker_argv("tile", cl, g_spool[r][0], g_spool[r][1]);
-        pids[r] = spawn(wv, r, n, one_device, NULL, g_spool[r][2]);
+        char **wv = worker_argv("tile", cl, g_spool[r][SP_IN], g_spool[r][SP_OUT]);
+        pids[r] = spawn(wv, r, n, one_device, NULL, g_spool[r][SP_ROWS], NULL);
         free(wv);
         if (pids[r] < 0) {
             fprintf(stderr, "paffy: fork failed\n");
@@ -546,9 +598,9 @@ static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_pat
     for (int r = 0; r < n; r++) {
         Cursor *c = &cur[r];
         if (pids[r] <= 0) continue; /* no lines, no worker: line_end stays NULL */
-        c->out = (const char *)map_file(g_spool[r][1], &c->out_len);
-        c->rows = (const uint32_t *)map_file(g_spool[r][2], &c->rows_len);
-        c->idx = (const uint64_t *)map_file(g_spool[r][3], &c->idx_len);
+        c->out = (const char *)map_file(g_spool[r][SP_OUT], &c->out_len);
+        c->rows = (const uint32_t *)map_file(g_spool[r][SP_ROWS], &c->rows_len);
+        c->idx = (const uint64_t *)map_file(g_spool[r][SP_IDX], &c->idx_len);
         if (c->out && c->out_len == 0 && !c->rows) { /* a worker that ended well and wrote nothing had nothing to list either */
             c->rows = (const uint32_t *)"";
             c->rows_len = 0;
@@ -592,17 +644,326 @@ static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_pat
     return rc;
 }
 
+/* ---------------- chain ---------------- */
+
+enum { V_GO_ON = 0, V_YOU_FAILED = 1, V_END = 2 }; /* the verdicts */
+
+typedef struct {
+    pid_t pid;         /* 0: not started, or reaped */
+    int to_fd, from_fd; /* our ends: verdicts down, reports up (-1: closed) */
+    int dead, st;      /* ended without reporting; its wait status */
+    int64_t rep[8];    /* the last report: phase, failed, key x 3, count, 0, 0 */
+} ChainWorker;
+
+static int read_all(int fd, void *buf, size_t n) { /* 0: n bytes; -1: end-of-file or an error before that */
+    for (size_t got = 0; got < n;) {
+        ssize_t k = read(fd, (char *)buf + got, n - got);
+        if (k < 0 && errno == EINTR) continue;
+        if (k <= 0) return -1;
+        got += (size_t)k;
+    }
+    return 0;
+}
+
+static void reap(ChainWorker *w, int r) {
+    if (w->pid <= 0) return;
+    while (waitpid(w->pid, &w->st, 0) < 0 && errno == EINTR) {}
+    g_pids[r] = 0;
+    w->pid = 0;
+}
+
+static void hang_up(ChainWorker *w) {
+    if (w->to_fd >= 0) close(w->to_fd);
+    if (w->from_fd >= 0) close(w->from_fd);
+    w->to_fd = w->from_fd = -1;
+}
+
+/* a verdict to a worker that may be gone already: the write must not end us with SIGPIPE */
+static void send_verdict(ChainWorker *w, int64_t verdict) {
+    if (w->to_fd < 0) return;
+    struct sigaction ign, old;
+    memset(&ign, 0, sizeof(ign));
+    ign.sa_handler = SIG_IGN;
+    sigaction(SIGPIPE, &ign, &old);
+    while (write(w->to_fd, &verdict, sizeof(verdict)) < 0 && errno == EINTR) {}
+    sigaction(SIGPIPE, &old, NULL);
+}
+
+/*
+ * One phase's reports from every running worker, in rank order (each of them either reports or ends: nothing here can wait for ever on a
+ * dead peer). Returns -1 when all go on; else the rank whose failure ends the run -- a worker that ended without a report (the first
+ * by rank) before any reported failure, among those the least sort key -- after that worker has been told to speak, every other one to
+ * end, and all of them have been reaped. *st: the wait status to end with.
+ */
+static int chain_phase(ChainWorker *w, int n, int64_t phase, int *st) {
+    int loser = -1, dead = -1;
+    for (int r = 0; r < n; r++) {
+        if (w[r].pid <= 0) continue;
+        if (read_all(w[r].from_fd, w[r].rep, sizeof(w[r].rep)) != 0 || w[r].rep[0] != phase) {
+            w[r].dead = 1;
+            if (dead < 0) dead = r;
+            continue;
+        }
+        if (!w[r].rep[1]) continue;
+        if (loser < 0) { loser = r; continue; }
+        const int64_t *a = w[r].rep + 2, *b = w[loser].rep + 2;
+        if (a[0] != b[0] ? a[0] < b[0] : (a[1] != b[1] ? a[1] < b[1] : a[2] < b[2])) loser = r;
+    }
+    if (dead < 0 && loser < 0) return -1;
+    if (dead >= 0) loser = dead;
+    for (int r = 0; r < n; r++)
+        if (w[r].pid > 0 && !w[r].dead) send_verdict(&w[r], r == loser ? V_YOU_FAILED : V_END);
+    for (int r = 0; r < n; r++) {
+        hang_up(&w[r]); /* whoever still waits for a verdict reads end-of-file and exits */
+        reap(&w[r], r);
+    }
+    *st = w[loser].st;
+    return loser;
+}
+
+typedef struct {
+    int64_t cls, score, key, number; /* a chain's tail key */
+    int32_t part;
+    int64_t at; /* its place in the part's chain order */
+} ChainTail;
+
+/* the order one process pulls the chains out in (impl/chaining.c:213-230, '+' before '-', :304-305): shard.global_chain_ids */
+static int by_chain_rank(const void *a, const void *b) {
+    const ChainTail *x = (const ChainTail *)a, *y = (const ChainTail *)b;
+    if (x->cls != y->cls) return x->cls < y->cls ? -1 : 1;
+    if (x->score != y->score) return x->score > y->score ? -1 : 1;
+    if (x->key != y->key) return x->key > y->key ? -1 : 1;
+    if (x->number != y->number) return x->number > y->number ? -1 : 1;
+    return 0;
+}
+
+/* every worker's <rank>.tails -> every worker's <rank>.ids */
+static int number_chains(const ChainWorker *w, int n) {
+    int64_t total = 0;
+    for (int r = 0; r < n; r++)
+        if (w[r].pid > 0) total += w[r].rep[5];
+    if (total >= ((int64_t)1 << 31)) {
+        fprintf(stderr, "paffy chain: %lld chains: more than a cn tag of the worker holds\n", (long long)total);
+        return 1;
+    }
+    ChainTail *all = (ChainTail *)malloc(sizeof(ChainTail) * (size_t)(total + 1));
+    int64_t *ids = (int64_t *)malloc(sizeof(int64_t) * (size_t)(total + 1));
+    int64_t first[MAX_RANKS + 1], m = 0;
+    int rc = !all || !ids;
+    for (int r = 0; r < n && !rc; r++) {
+        first[r] = m;
+        if (w[r].pid <= 0) continue;
+        size_t len = 0;
+        const int64_t *t = (const int64_t *)map_file(g_spool[r][SP_TAILS], &len);
+        if (!t || w[r].rep[5] < 0 || len != (size_t)w[r].rep[5] * 32) {
+            fprintf(stderr, "paffy chain: worker %d left no chain keys\n", r);
+            rc = 1;
+            break;
+        }
+        for (int64_t c = 0; c < w[r].rep[5]; c++, m++) {
+            ChainTail e = {t[4 * c], t[4 * c + 1], t[4 * c + 2], t[4 * c + 3], r, m};
+            all[m] = e;
+        }
+        if (len) munmap((void *)t, len);
+    }
+    first[n] = m;
+    if (!rc) {
+        qsort(all, (size_t)m, sizeof(ChainTail), by_chain_rank);
+        for (int64_t k = 0; k < m; k++) ids[all[k].at] = k; /* `at` runs over the parts one after the other */
+        for (int r = 0; r < n && !rc; r++) {
+            if (w[r].pid <= 0) continue;
+            FILE *f = fopen(g_spool[r][SP_IDS], "wx");
+            const size_t cnt = (size_t)(first[r + 1] - first[r]);
+            if (!f || fwrite(ids + first[r], sizeof(int64_t), cnt, f) != cnt || fclose(f) != 0) {
+                fprintf(stderr, "paffy chain: cannot write under %s\n", g_tmpdir);
+                rc = 1;
+            }
+        }
+    }
+    free(all);
+    free(ids);
+    return rc;
+}
+
+typedef struct {
+    const char *p, *end;   /* the worker's output lines */
+    const int64_t *key;    /* (own score, chain id, link, bytes) of the next line; NULL: none left */
+    const int64_t *key_end;
+} ChainCursor;
+
+/* the K-way merge of the workers' outputs by (own score desc, chain id asc, link asc): paf_cmp_by_score over the chains as they were
+   written out (impl/chaining.c:337), shard.chain_line_offsets. A line's length is column 3 of its key. */
+static int merge_chain_lines(const ChainWorker *w, int n, FILE *out) {
+    ChainCursor cur[MAX_RANKS];
+    memset(cur, 0, sizeof(cur));
+    for (int r = 0; r < n; r++) {
+        if (w[r].rep[5] <= 0) continue; /* no worker, or no line */
+        size_t out_len = 0, key_len = 0;
+        const char *text = (const char *)map_file(g_spool[r][SP_OUT], &out_len);
+        const int64_t *keys = (const int64_t *)map_file(g_spool[r][SP_LKEYS], &key_len);
+        int64_t bytes = 0;
+        int ok = text && keys && key_len == (size_t)w[r].rep[5] * 32;
+        for (int64_t k = 0; ok && k < w[r].rep[5]; k++) {
+            if (keys[4 * k + 3] <= 0 || keys[4 * k + 3] > (int64_t)out_len - bytes) ok = 0;
+            else bytes += keys[4 * k + 3];
+        }
+        if (!ok || bytes != (int64_t)out_len) {
+            fprintf(stderr, "paffy chain: worker %d left no output\n", r);
+            return 1;
+        }
+        cur[r].p = text;
+        cur[r].end = text + out_len;
+        cur[r].key = keys;
+        cur[r].key_end = keys + 4 * w[r].rep[5];
+    }
+    for (;;) {
+        int best = -1;
+        for (int r = 0; r < n; r++) {
+            const int64_t *a = cur[r].key;
+            if (!a) continue;
+            if (best < 0) {
+                best = r;
+                continue;
+            }
+            const int64_t *b = cur[best].key;
+            if (a[0] != b[0] ? a[0] > b[0] : (a[1] != b[1] ? a[1] < b[1] : a[2] < b[2])) best = r;
+        }
+        if (best < 0) break;
+        ChainCursor *c = &cur[best];
+        if (fwrite(c->p, 1, (size_t)c->key[3], out) != (size_t)c->key[3]) return 1;
+        c->p += c->key[3];
+        c->key += 4;
+        if (c->key == c->key_end) c->key = NULL;
+    }
+    return 0;
+}
+
+static double seconds_now(void) {
+    struct timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+}
+
+static int run_chain(const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path) {
+    int info = 0; /* -l INFO / DEBUG: our own steps' times go to stderr */
+    for (int i = 0; i + 1 < cl->n_opts; i++)
+        if (!strcmp(cl->opts[i], "-l")) {
+            info = !strcasecmp(cl->opts[i + 1], "INFO") || !strcasecmp(cl->opts[i + 1], "DEBUG");
+            i++;
+        }
+    double t0 = seconds_now(), t_number = 0.0;
+    int64_t spooled[MAX_RANKS];
+    if (partition_by_query("chain", n, in_path, spooled) != 0) return 1;
+    /* where one worker opens it (impl/paf_chain.c:125-126): a run that fails leaves the same empty file */
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) {
+        fprintf(stderr, "paffy chain: cannot open %s\n", out_path);
+        return 1;
+    }
+    const double t_partition = seconds_now() - t0;
+    ChainWorker w[MAX_RANKS];
+    memset(w, 0, sizeof(w));
+    int started = 0;
+    for (int r = 0; r < n; r++) w[r].to_fd = w[r].from_fd = -1;
+    for (int r = 0; r < n; r++) { /* workers without a line are not started */
+        if (spooled[r] == 0) continue;
+        int down[2], up[2];
+        char part[PATH_MAX];
+        snprintf(part, sizeof(part), "%s/%d", g_spooldir, r);
+        if (pipe2(down, O_CLOEXEC) != 0) down[0] = down[1] = -1;
+        if (down[0] < 0 || pipe2(up, O_CLOEXEC) != 0) up[0] = up[1] = -1;
+        pid_t pid = -1;
+        if (up[0] >= 0) {
+            const ChainLink link = {part, down[0], up[1]};
+            char **wv = worker_argv("chain", cl, g_spool[r][SP_IN], g_spool[r][SP_OUT]);
+            pid = spawn(wv, r, n, one_device, NULL, NULL, &link);
+            free(wv);
+        }
+        if (down[0] >= 0) close(down[0]);
+        if (up[0] >= 0) close(up[1]);
+        if (pid < 0) {
+            fprintf(stderr, "paffy: cannot start worker %d: %s\n", r, strerror(errno));
+            if (down[0] >= 0) close(down[1]);
+            if (up[0] >= 0) close(up[0]);
+            for (int q = 0; q < r; q++) {
+                send_verdict(&w[q], V_END);
+                hang_up(&w[q]);
+                reap(&w[q], q);
+            }
+            return 1;
+        }
+        w[r].pid = g_pids[r] = pid;
+        w[r].to_fd = down[1];
+        w[r].from_fd = up[0];
+        started++;
+    }
+    int st = 0;
+    for (int64_t phase = 1; phase <= 2; phase++) {
+        const int loser = chain_phase(w, n, phase, &st);
+        if (loser >= 0) { /* nothing is written; we end the way that worker ended */
+            if (!WIFSIGNALED(st) && WEXITSTATUS(st) == 0) {
+                fprintf(stderr, "paffy chain: worker %d ended without a result\n", loser);
+                return 1;
+            }
+            return status_of(st);
+        }
+        if (phase == 1) {
+            t0 = seconds_now();
+            if (number_chains(w, n) != 0) {
+                for (int r = 0; r < n; r++) {
+                    send_verdict(&w[r], V_END);
+                    hang_up(&w[r]);
+                    reap(&w[r], r);
+                }
+                return 1;
+            }
+            t_number = seconds_now() - t0;
+        }
+        for (int r = 0; r < n; r++)
+            if (w[r].pid > 0) send_verdict(&w[r], V_GO_ON);
+    }
+    int any_bad = 0;
+    for (int r = 0; r < n; r++) { /* the workers write their lines and end */
+        if (w[r].pid <= 0) {
+            w[r].rep[5] = 0;
+            continue;
+        }
+        hang_up(&w[r]);
+        reap(&w[r], r);
+        if (!any_bad && (WIFSIGNALED(w[r].st) || WEXITSTATUS(w[r].st) != 0)) {
+            any_bad = 1;
+            st = w[r].st;
+        }
+    }
+    if (any_bad) return status_of(st);
+    t0 = seconds_now();
+    setvbuf(out, NULL, _IOFBF, 1 << 22);
+    int rc = merge_chain_lines(w, n, out);
+    rc |= fflush(out) != 0;
+    if (out != stdout) rc |= fclose(out) != 0;
+    if (info)
+        fprintf(stderr, "paffy chain: %d workers; launcher: partition %.3f s, chain numbers %.3f s, merge %.3f s\n", started, t_partition, t_number,
+                seconds_now() - t0);
+    return rc;
+}
+
 int main(int argc, char **argv) {
     find_worker();
     const char *g = getenv("PAFFY_GPUS");
     int n = g ? atoi(g) : 1;
     if (n > MAX_RANKS) n = MAX_RANKS;
-    int shard = n > 1 && argc >= 2 && (is_stream_cmd(argv[1]) || !strcmp(argv[1], "tile"));
+    const int is_chain = argc >= 2 && !strcmp(argv[1], "chain");
+    int shard = n > 1 && argc >= 2 && (is_stream_cmd(argv[1]) || !strcmp(argv[1], "tile") || is_chain);
     CmdLine cl;
     memset(&cl, 0, sizeof(cl));
     if (shard) {
         parse_cmdline(argc, argv, &cl);
         shard = cl.ok; /* -h, or something getopt_long would reject: the one worker says what the reference says */
+        if (shard && is_chain && cl.in_path) { /* and so it does for an input that cannot be opened */
+            const int fd = open(cl.in_path, O_RDONLY);
+            if (fd < 0) shard = 0;
+            else close(fd);
+        }
     }
     if (!shard) { /* one GPU (or a command that does not shard): this process becomes the worker; it has not touched a GPU */
         free(cl.copy);
@@ -638,7 +999,8 @@ int main(int argc, char **argv) {
         close(fd);
         in_path = g_stdin_spool;
     }
-    const int rc = !strcmp(argv[1], "tile") ? run_tile(&cl, n, one_device, in_path, out_path) : run_stream(argv[1], &cl, n, one_device, in_path, out_path);
+    const int rc = !strcmp(argv[1], "tile") ? run_tile(&cl, n, one_device, in_path, out_path)
+                   : (is_chain ? run_chain(&cl, n, one_device, in_path, out_path) : run_stream(argv[1], &cl, n, one_device, in_path, out_path));
     free(cl.copy);
     return rc;
 }

@@ -5,6 +5,7 @@
  */
 #define _GNU_SOURCE
 #include <inttypes.h>
+#include <errno.h>
 #include <signal.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -652,6 +653,132 @@ int host_split_file(FILE *in, const char *prefix, int by_query, int64_t min_leng
     return rc;
 }
 
+/*
+ * ---- `paffy chain` as one of N workers of the launcher (host/paffy_launch.c): the part mode ----
+ * PAFFY_CHAIN_PART=<prefix> names the part's files -- <prefix>.idx (read: the global record number of every input line, one int64 each),
+ * <prefix>.tails (written: four int64 per chain), <prefix>.ids (read: one int64 per chain, its number in the whole input), <prefix>.lkeys
+ * (written: four int64 per output line) -- and PAFFY_CHAIN_FDS=<from_launcher>,<to_launcher> two inherited pipe descriptors. After each of
+ * the two phases the worker writes eight int64 {phase, failed, sort key x 3, count, 0, 0} and reads one int64: 0 go on, 1 this worker's
+ * failure is the one the user sees (it ends as die_like_reference ends), anything else, or end-of-file: end silently. Every
+ * error.record is a global record number (paffy_hip_chain_add_indexed), so the message is the one-worker run's.
+ */
+typedef struct {
+    const char *prefix;
+    int from_fd, to_fd;
+    FILE *idx;
+} chain_part;
+
+static int chain_part_open(chain_part *p) { /* 1: part mode; 0: not under the launcher; -1 after a message */
+    const char *prefix = getenv("PAFFY_CHAIN_PART"), *fds = getenv("PAFFY_CHAIN_FDS");
+    if (!prefix || !*prefix || !fds) return 0;
+    char path[4096];
+    p->prefix = prefix;
+    snprintf(path, sizeof(path), "%s.idx", prefix);
+    if (sscanf(fds, "%d,%d", &p->from_fd, &p->to_fd) != 2 || !(p->idx = fopen(path, "r"))) {
+        fprintf(stderr, "paffy chain: cannot use the part %s (PAFFY_CHAIN_FDS=%s)\n", prefix, fds);
+        return -1;
+    }
+    return 1;
+}
+
+/* a batch of the part: its lines' global record numbers go to the device with it */
+static int chain_part_add(paffy_hip_ctx *ctx, chain_part *p, const void *d, const char *buf, size_t use) {
+    size_t lines = use > 0 && buf[use - 1] != '\n';
+    for (const char *q = buf, *e = buf + use; q < e && (q = (const char *)memchr(q, '\n', (size_t)(e - q))) != NULL; q++) lines++;
+    int64_t *g = (int64_t *)malloc(sizeof(int64_t) * (lines + 1));
+    void *d_g = NULL;
+    int rc = -1;
+    if (g && fread(g, sizeof(int64_t), lines, p->idx) == lines && paffy_hip_malloc(&d_g, (int64_t)(sizeof(int64_t) * lines) + 64) == 0 &&
+        paffy_hip_memcpy_h2d(d_g, g, (int64_t)(sizeof(int64_t) * lines)) == 0)
+        rc = paffy_hip_chain_add_indexed(ctx, d, (int64_t)use, d_g);
+    if (d_g) paffy_hip_free(d_g); /* read before the call returned */
+    free(g);
+    return rc;
+}
+
+/* `count` rows of four int64 from device memory to <prefix>.<ext>, complete before the report that mentions them */
+static int chain_part_keys(paffy_hip_ctx *ctx, const chain_part *p, const char *ext, const void *d_keys, int64_t count) {
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.%s", p->prefix, ext);
+    const size_t bytes = (size_t)count * 32;
+    char *h = (char *)malloc(bytes + 1);
+    int rc = !h || paffy_hip_sync(ctx) != 0 || (bytes && paffy_hip_memcpy_d2h(h, d_keys, (int64_t)bytes) != 0);
+    FILE *f = rc ? NULL : fopen(path, "w");
+    if (!f || fwrite(h, 1, bytes, f) != bytes) rc = 1;
+    if (f && fclose(f) != 0) rc = 1;
+    free(h);
+    return rc;
+}
+
+/* the report of a phase, then the launcher's verdict: returns on "go on", ends the process otherwise */
+static void chain_part_report(const chain_part *p, int64_t phase, const paffy_error *e, const int64_t key[3], int64_t count) {
+    const int64_t rep[8] = {phase, e->code != 0, key[0], key[1], key[2], count, 0, 0};
+    int64_t verdict = -1;
+    size_t at = 0;
+    while (at < sizeof(rep)) {
+        const ssize_t k = write(p->to_fd, (const char *)rep + at, sizeof(rep) - at);
+        if (k < 0 && errno == EINTR) continue;
+        if (k <= 0) exit(1); /* the launcher is gone */
+        at += (size_t)k;
+    }
+    for (at = 0; at < sizeof(verdict);) {
+        const ssize_t k = read(p->from_fd, (char *)&verdict + at, sizeof(verdict) - at);
+        if (k < 0 && errno == EINTR) continue;
+        if (k <= 0) exit(1); /* end-of-file in place of a verdict */
+        at += (size_t)k;
+    }
+    if (verdict == 0 && !e->code) return;
+    if (verdict == 1 && e->code) die_like_reference(e, 0);
+    exit(verdict == 2 ? 0 : 1);
+}
+
+/* paffy_hip_chain_run in two phases with the launcher between them; 0 with the lines planned, or the failing call's code */
+static int chain_part_run(paffy_hip_ctx *ctx, const paffy_chain_opts *opts, chain_part *p, paffy_plan_info *info) {
+    int rc = paffy_hip_chain_run_part(ctx, opts, info);
+    if (rc) return rc;
+    void *d_keys = NULL;
+    int64_t key[3] = {info->error.stage, info->error.record, 0}, n_chains = 0; /* shard.part_failure */
+    if (!info->error.code) {
+        const int64_t cap = info->n_records > 0 ? info->n_records : 1; /* every chain has a record of its own */
+        if (paffy_hip_malloc(&d_keys, cap * 32 + 64) != 0) return PAFFY_E_HIP;
+        n_chains = paffy_hip_chain_tail_keys(ctx, cap, d_keys);
+        if (n_chains >= 0 && chain_part_keys(ctx, p, "tails", d_keys, n_chains) != 0) n_chains = PAFFY_E_HIP;
+        paffy_hip_free(d_keys);
+        if (n_chains < 0) return (int)n_chains;
+    }
+    chain_part_report(p, 1, &info->error, key, n_chains);
+    /* the chains' numbers in the whole input */
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.ids", p->prefix);
+    int64_t *ids = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n_chains + 1));
+    FILE *f = fopen(path, "r");
+    void *d_ids = NULL;
+    int64_t fail_key[3] = {0, 0, 0};
+    rc = PAFFY_E_HIP;
+    if (ids && f && fread(ids, sizeof(int64_t), (size_t)n_chains, f) == (size_t)n_chains && paffy_hip_malloc(&d_ids, n_chains * 8 + 64) == 0 &&
+        paffy_hip_memcpy_h2d(d_ids, ids, n_chains * 8) == 0)
+        rc = paffy_hip_chain_renumber(ctx, n_chains ? d_ids : NULL, info, fail_key);
+    else
+        fprintf(stderr, "paffy chain: cannot read %s\n", path);
+    if (f) fclose(f);
+    if (d_ids) paffy_hip_free(d_ids);
+    free(ids);
+    if (rc) return rc;
+    key[0] = fail_key[1]; /* a failed paf_check: (chain id, link), the order the reference checks in */
+    key[1] = fail_key[2];
+    if (!info->error.code) {
+        const int64_t cap = info->n_rows > 0 ? info->n_rows : 1;
+        if (paffy_hip_malloc(&d_keys, cap * 32 + 64) != 0) return PAFFY_E_HIP;
+        int64_t n_lines = paffy_hip_chain_line_keys(ctx, cap, d_keys);
+        if (n_lines >= 0 && n_lines != info->n_rows) n_lines = PAFFY_E_STATE;
+        if (n_lines >= 0 && chain_part_keys(ctx, p, "lkeys", d_keys, n_lines) != 0) n_lines = PAFFY_E_HIP;
+        paffy_hip_free(d_keys);
+        if (n_lines < 0) return (int)n_lines;
+    }
+    chain_part_report(p, 2, &info->error, key, info->n_rows);
+    return 0;
+}
+
 static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paffy_chain_opts *chain);
 int host_tile(FILE *in, FILE *out) { return whole_file(in, out, NULL, NULL); }
 /* paffy to_bed: every record counts before anything is written, like tile */
@@ -671,6 +798,10 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
         return 1;
     }
     const char *what = bed ? "to_bed" : (chain ? "chain" : "tile");
+    chain_part part; /* chain under the N-GPU launcher */
+    memset(&part, 0, sizeof(part));
+    const int in_part = chain ? chain_part_open(&part) : 0;
+    if (in_part < 0) return 1;
     const size_t cap = chunk_bytes();
     size_t buf_cap = cap + (1 << 20), have = 0;
     char *buf = (char *)malloc(buf_cap);
@@ -712,7 +843,7 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
         }
         void *d = NULL;
         if (paffy_hip_malloc(&d, (int64_t)use + 64) != 0 || paffy_hip_memcpy_h2d(d, buf, (int64_t)use) != 0 ||
-            (bed ? paffy_hip_bed_add(ctx, d, (int64_t)use) : (chain ? paffy_hip_chain_add(ctx, d, (int64_t)use) : paffy_hip_tile_add(ctx, d, (int64_t)use))) != 0) {
+            (bed ? paffy_hip_bed_add(ctx, d, (int64_t)use) : (chain ? (in_part ? chain_part_add(ctx, &part, d, buf, use) : paffy_hip_chain_add(ctx, d, (int64_t)use)) : paffy_hip_tile_add(ctx, d, (int64_t)use))) != 0) {
             fprintf(stderr, "paffy %s: GPU call failed: %s (the input must fit the GPU's memory)\n", what, paffy_hip_last_error(ctx));
             if (d) paffy_hip_free(d);
             rc = 1;
@@ -726,7 +857,7 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
     free(buf);
     paffy_plan_info info;
     memset(&info, 0, sizeof(info));
-    if (!rc && (bed ? paffy_hip_bed_run(ctx, bed, &info) : (chain ? paffy_hip_chain_run(ctx, chain, &info) : paffy_hip_tile_run(ctx, &info))) != 0) {
+    if (!rc && (bed ? paffy_hip_bed_run(ctx, bed, &info) : (chain ? (in_part ? chain_part_run(ctx, chain, &part, &info) : paffy_hip_chain_run(ctx, chain, &info)) : paffy_hip_tile_run(ctx, &info))) != 0) {
         fprintf(stderr, "paffy %s: GPU call failed: %s\n", what, paffy_hip_last_error(ctx));
         rc = 1;
     }
@@ -788,6 +919,7 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
     }
     for (size_t i = 0; i < n_batches; i++) paffy_hip_free(d_batches[i]);
     free(d_batches);
+    if (part.idx) fclose(part.idx);
     paffy_hip_destroy(ctx);
     fflush(out);
     return rc;
