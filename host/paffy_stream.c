@@ -202,9 +202,8 @@ static int stats_lines(paffy_hip_ctx *ctx, const char *buf, const paffy_record *
             rows = (char *)malloc((size_t)(off[rows_end] - off[rows_first]) + 1);
             paffy_error e;
             rc = paffy_hip_plan_alignment_rows(ctx, rows_first, rows_end - rows_first, off + rows_first, rows, &e);
-            if (!rc && e.code) {
+            if (!rc && e.code) { /* e.record counts from the batch's first record, whichever piece it was fetched in */
                 fflush(g_stats_lines);
-                e.record += rows_first;
                 die_like_reference(&e, record_base);
             }
             if (rc) break;

@@ -369,6 +369,15 @@ int paffy_hip_flat_stats(paffy_hip_ctx *ctx, int64_t *left, int64_t reasons[16])
 /* The same six sums for every record of the batch (6 * n_records values, record by record): the numbers of the per-alignment line of
  * `paffy view` (paf_pretty_print, impl/paf.c:269-281). Returns n_records or a negative error. */
 int64_t paffy_hip_plan_record_stats(paffy_hip_ctx *ctx, int64_t cap_records, int64_t *sums);
+/*
+ * Diagnostics of the last paffy_hip_plan, read only: for records [first, first + count) of the planned batch, flags[i] = the record's
+ * RecPlan.flags (paffy_amd/csrc/record_types.h: bit 0 reversed view, bit 1 I / D exchanged, bit 2 query / target exchanged, bit 3 has a
+ * cigar, bit 17 4-byte ops in an arena block, bit 18 2-byte words in the mirror, bit 20 the arena block is the flat add pass's) and
+ * klass[i] = its class (0 LDS, 1 arena: 8-byte ops). Both are meaningful for records the plan did not fail on. The outputs do not depend
+ * on how a record's ops are kept; the tests use this to know which representation the code under test really read.
+ * PAFFY_E_STATE without a record plan, PAFFY_E_ARG for a range outside the batch.
+ */
+int paffy_hip_plan_record_layout(paffy_hip_ctx *ctx, int64_t first, int64_t count, uint32_t *flags, uint32_t *klass);
 
 /*
  * The base-level rows of paf_pretty_print(..., include_alignment = true) (impl/paf.c:283-315; `paffy view -a`, impl/paf_view.c:158-160)
@@ -377,7 +386,10 @@ int64_t paffy_hip_plan_record_stats(paffy_hip_ctx *ctx, int64_t cap_records, int
  * in the case they were loaded in, so the sequences must have been set after paffy_hip_keep_raw_sequences(ctx, 1).
  * _sizes gives the bytes of each record's block (0: no cigar); _rows writes the blocks to h_out at h_off[i] - h_off[0] (h_off:
  * count + 1 running sums of the sizes, so that a batch can be fetched in pieces). A record whose sequences are missing or shorter
- * than its coordinates (the reference reads outside the strings) is reported in *err (stage -1) and h_out is then not complete.
+ * than its coordinates (the reference reads outside the strings) is reported in *err (stage -1) and h_out is then not complete:
+ * err->record is the record's index in the planned batch, as in every other paffy_error -- not its index in [first, first + count) --
+ * and of several failing records of the call the one with the smallest index is reported. PAFFY_E_ARG when first + count exceeds the
+ * batch; PAFFY_E_STATE without a record plan (a tile, dedupe, chain or to_bed plan made since does not count) or without raw sequences.
  * The batch text must still be in place (names are looked up in it when the plan had no PAFFY_ADD_MISMATCHES stage).
  */
 int paffy_hip_keep_raw_sequences(paffy_hip_ctx *ctx, int on);

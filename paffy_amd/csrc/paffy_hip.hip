@@ -3244,6 +3244,22 @@ int64_t paffy_hip_plan_record_stats(paffy_hip_ctx *c, int64_t cap_records, int64
     return n;
 }
 
+int paffy_hip_plan_record_layout(paffy_hip_ctx *c, int64_t first, int64_t count, uint32_t *flags, uint32_t *klass) {
+    if (!c || (count > 0 && (!flags || !klass))) return PAFFY_E_ARG;
+    if (!c->planned || c->plan_kind != PLAN_RECORDS) return PAFFY_E_STATE;
+    if (first < 0 || count < 0 || first + count > c->plan.n_records) return PAFFY_E_ARG;
+    if (count == 0) return 0;
+    std::vector<RecPlan> pl((size_t)count);
+    HIPCHK(c, hipMemcpyAsync(pl.data(), static_cast<const RecPlan *>(c->rec_plan.p) + first, sizeof(RecPlan) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(klass, c->kp.status + first, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < count; i++) {
+        flags[i] = pl[(size_t)i].flags;
+        klass[i] >>= 16;
+    }
+    return 0;
+}
+
 /* ---- the counters of a to_bed run, for hosts that keep SequenceCountArray objects (inc/paf.h:214-233) ---- */
 __global__ __launch_bounds__(PAFFY_NT) void k_counts_add_sat(uint16_t *acc, const uint16_t *add, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * PAFFY_NT + threadIdx.x;
@@ -3310,6 +3326,7 @@ static int pretty_params(paffy_hip_ctx *c, int64_t first, int64_t count, PrettyP
     pp->arena = c->kp.arena;
     pp->arena_off = c->kp.arena_off;
     pp->ops_mirror = c->kp.ops_mirror;
+    pp->new_ops = c->kp.new_ops;
     pp->seq_raw = static_cast<const uint8_t *>(c->seq_raw.p);
     pp->seqs = static_cast<const SeqEntry *>(c->seq_table.p);
     pp->rec_qseq = static_cast<const int32_t *>(c->rec_qseq.p);

@@ -9,6 +9,7 @@
  *     row_off[rec] + (col / 150) * 453 + col % 150 + {0, w + 1, 2 w + 2},   w = the window's width (150, the last one less)
  * so the block is the reference's text byte for byte. The bases are the sequences as loaded (seq_raw, case kept); on the
  * - strand the query is read backwards through stString_reverseComplementChar (A<->T, C<->G in both cases, others kept).
+ * A record that fails is reported by its index in the planned batch (first + the workgroup), whatever piece of the batch the call fetches.
  */
 #pragma once
 
@@ -22,6 +23,7 @@ struct PrettyParams {
     const uint64_t *arena;
     const uint64_t *arena_off;
     const uint32_t *ops_mirror;
+    const uint32_t *new_ops;    /* flat_add_kernel.h: the rebuilt cigars (RecPlan flag bit 20: arena_off counts 4-byte words of it) */
     const uint8_t *seq_raw;
     const SeqEntry *seqs;
     const int32_t *rec_qseq, *rec_tseq;
@@ -60,11 +62,17 @@ __device__ __forceinline__ void pretty_scan3(int64_t v[3], int64_t (*tmp)[3], in
     __syncthreads();
 }
 
+/* the 4-byte (or, in the mirror, 2-byte) ops of a record that is not of the arena class: emit_ops_of of record_kernel.h */
+__device__ __forceinline__ const uint32_t *pretty_ops4(const PrettyParams &P, const RecMeta &m, const RecPlan &pl, uint32_t rec) {
+    if (pl.flags & 0x100000u) return P.new_ops + P.arena_off[rec];
+    return (pl.flags & 0x20000u) ? reinterpret_cast<const uint32_t *>(P.arena + P.arena_off[rec]) : P.ops_mirror + (m.cg_off >> 1);
+}
+
 /* the record's columns: the sum of its op lengths */
 __device__ __forceinline__ int64_t pretty_columns(const PrettyParams &P, const RecMeta &m, const RecPlan &pl, uint32_t rec, int64_t (*tmp)[3]) {
     const bool rev = (pl.flags & 1u) != 0, wide = (P.status[rec] >> 16) == KLASS_ARENA;
     const uint64_t *ops8 = P.arena + P.arena_off[rec];
-    const uint32_t *ops4 = (pl.flags & 0x20000u) ? reinterpret_cast<const uint32_t *>(P.arena + P.arena_off[rec]) : P.ops_mirror + (m.cg_off >> 1);
+    const uint32_t *ops4 = pretty_ops4(P, m, pl, rec);
     const bool half = (pl.flags & 0x60000u) == 0x40000u; /* the mirror holds 2-byte words (record_kernel.h: emit_ops_half) */
     int64_t part = 0;
     for (uint32_t i = threadIdx.x; i < pl.n; i += PRETTY_NT) {
@@ -115,7 +123,7 @@ __global__ __launch_bounds__(PRETTY_NT) void k_pretty_rows(PrettyParams P) {
     const bool same = m.same_strand != 0;
     const bool wide = (P.status[rec] >> 16) == KLASS_ARENA; /* 8-byte ops in the arena */
     const uint64_t *ops8 = P.arena + P.arena_off[rec];
-    const uint32_t *ops4 = (pl.flags & 0x20000u) ? reinterpret_cast<const uint32_t *>(P.arena + P.arena_off[rec]) : P.ops_mirror + (m.cg_off >> 1);
+    const uint32_t *ops4 = pretty_ops4(P, m, pl, rec);
     const bool half = (pl.flags & 0x60000u) == 0x40000u; /* the mirror holds 2-byte words (record_kernel.h: emit_ops_half) */
     /* the width of the last window needs the number of columns: one pass over the ops first */
     const int64_t cols_total = pretty_columns(P, m, pl, rec, tmp);

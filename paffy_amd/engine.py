@@ -186,6 +186,11 @@ def lib():
         L.paffy_hip_fasta_index_headers.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64)]
         L.paffy_hip_fasta_seen.argtypes = [vp, vp, i64, C.c_int, C.POINTER(C.c_uint8)]
         L.paffy_hip_keep_raw_sequences.argtypes = [vp, C.c_int]
+        L.paffy_hip_plan_record_stats.restype = i64
+        L.paffy_hip_plan_record_stats.argtypes = [vp, i64, C.POINTER(i64)]
+        L.paffy_hip_plan_record_layout.argtypes = [vp, i64, i64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.paffy_hip_plan_alignment_sizes.argtypes = [vp, i64, i64, C.POINTER(i64)]
+        L.paffy_hip_plan_alignment_rows.argtypes = [vp, i64, i64, C.POINTER(i64), C.c_void_p, C.POINTER(_Error)]
         _lib = L
     return _lib
 
@@ -590,6 +595,47 @@ class Engine:
         out = (C.c_int64 * 6)()
         self._check(lib().paffy_hip_plan_stats(self._ctx, out), "paffy_hip_plan_stats")
         return tuple(out)
+
+    def record_stats(self, n):
+        """The six sums of plan_stats for each of the n records of the last plan (a STATS stage in it): a list of 6-tuples, the numbers of
+        the per-alignment line of `paffy view`."""
+        out = (C.c_int64 * (6 * max(1, n)))()
+        got = lib().paffy_hip_plan_record_stats(self._ctx, n, out)
+        if got < 0:
+            self._check(int(got), "paffy_hip_plan_record_stats")
+        return [tuple(out[6 * i:6 * i + 6]) for i in range(got)]
+
+    def record_layout(self, first, count):
+        """(RecPlan flags, classes) of records [first, first + count) of the last plan: how each record's ops are kept (diagnostics, as
+        flat_stats: the tests use it to know which representation was read)."""
+        flags, klass = (C.c_uint32 * max(1, count))(), (C.c_uint32 * max(1, count))()
+        self._check(lib().paffy_hip_plan_record_layout(self._ctx, first, count, flags, klass), "paffy_hip_plan_record_layout")
+        return list(flags[:count]), list(klass[:count])
+
+    def alignment_sizes(self, first, count):
+        """Bytes of the base-level rows (`paffy view -a`) of records [first, first + count) of the last plan."""
+        out = (C.c_int64 * max(1, count))()
+        self._check(lib().paffy_hip_plan_alignment_sizes(self._ctx, first, count, out), "paffy_hip_plan_alignment_sizes")
+        return list(out[:count])
+
+    def alignment_rows(self, first, count, offsets=None, guard=0):
+        """The rows of records [first, first + count) of the last plan, block after block: (bytes, error), error = None or (code, record)
+        with the record's index in the planned batch. offsets: count + 1 running sums of the sizes (default: built from
+        alignment_sizes); only their differences count, so the slice of a whole batch's offsets fetches a piece of it. guard: that
+        many bytes of 0xA5 are kept behind the host buffer and returned with the rows (the tests check that nothing wrote there)."""
+        if offsets is None:
+            offsets = [0]
+            for b in self.alignment_sizes(first, count):
+                offsets.append(offsets[-1] + b)
+        if len(offsets) != count + 1:
+            raise ValueError("count + 1 offsets")
+        off = (C.c_int64 * (count + 1))(*offsets)
+        total = offsets[count] - offsets[0]
+        buf = (C.c_ubyte * (max(0, total) + guard + 1))()
+        C.memset(C.addressof(buf) + max(0, total), 0xA5, guard)
+        err = _Error()
+        self._check(lib().paffy_hip_plan_alignment_rows(self._ctx, first, count, off, C.cast(buf, C.c_void_p), C.byref(err)), "paffy_hip_plan_alignment_rows")
+        return bytes(buf[: total + guard]), ((err.code, err.record) if err.code else None)
 
     def synth4_setup(self, seed, mean_ops, n_contigs=24, tlen_min=50_000_000, tlen_span=200_000_000, genomes=True):
         """cfg4 workload: master alignments of n_contigs contig pairs and, with `genomes`, both genomes

@@ -284,6 +284,40 @@ static void pretty(void) {
     paf_destruct(p);
 }
 
+/* paf_pretty_print of a record another call has changed: paf_invert, then paf_trim_ends -- the text the GPU plans (PAFFY_STATS alone) is
+   the one hand_over rebuilt from the struct. argv: a file with one PAF line, the two sequences as files of bases (query, target), the
+   output file; the caller compares with the oracle's text. */
+static char *slurp(const char *path) {
+    FILE *fh = fopen(path, "r");
+    if (!fh) return NULL;
+    fseek(fh, 0, SEEK_END);
+    long n = ftell(fh);
+    rewind(fh);
+    char *buf = malloc((size_t)n + 1);
+    if (fread(buf, 1, (size_t)n, fh) != (size_t)n) n = 0;
+    fclose(fh);
+    while (n > 0 && buf[n - 1] == '\n') n--;
+    buf[n] = '\0';
+    return buf;
+}
+static int pretty_changed(const char *line_path, const char *q_path, const char *t_path, const char *out_path, int64_t end_bases) {
+    char *line = slurp(line_path), *q = slurp(q_path), *t = slurp(t_path);
+    FILE *out = fopen(out_path, "w");
+    if (!line || !q || !t || !out) return 1;
+    Paf *p = paf_parse(line, true);
+    paf_pretty_print(p, q, t, out, true);
+    paf_invert(p); /* the names and with them the sequences change places */
+    paf_pretty_print(p, t, q, out, true);
+    paf_trim_ends(p, end_bases);
+    paf_pretty_print(p, t, q, out, true);
+    paf_destruct(p);
+    fclose(out);
+    free(line);
+    free(q);
+    free(t);
+    return 0;
+}
+
 /* the library transforms check nothing and keep the tags they do not compute (impl/paf.c:463-490) */
 static void unchecked_and_preserved(void) {
     Paf *p = make_paf("q", 100, 0, 9, true, "t", 100, 0, 10, 10, 10, 60, "10M"); /* cigar and query coordinates disagree */
@@ -413,6 +447,7 @@ int main(int argc, char **argv) {
         must_fail(atoi(argv[2]));
         return 0; /* not reached when the failure is detected */
     }
+    if (argc == 7 && strcmp(argv[1], "--pretty") == 0) return pretty_changed(argv[2], argv[3], argv[4], argv[5], atoll(argv[6]));
     cigars();
     parsing();
     inverting();
