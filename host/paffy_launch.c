@@ -31,7 +31,8 @@
  *     end-of-file on its pipe: the run ends with that worker's status and nothing is written; a worker that reads end-of-file instead
  *     of a verdict exits. Nothing is written before both phases have passed everywhere (impl/paf_chain.c:128-132 writes last).
  * Everything between the workers goes through files under PAFFY_TMPDIR (default /dev/shm, else TMPDIR, else /tmp): host-mediated, no
- * GPU-to-GPU traffic -- a CLI's input comes from the host and its output goes back there. Other commands run on one GPU.
+ * GPU-to-GPU traffic -- a CLI's input comes from the host and its output goes back there. Other commands run on one GPU (to_bed has its
+ * sharded form in the library and in paffy_amd/shard.py, to_bed_sharded, but not yet behind this launcher).
  *
  * Environment: PAFFY_GPUS=N; PAFFY_ONE_DEVICE=1 (rehearsal: every worker uses device 0); PAFFY_WORKER=path (another worker binary:
  * the CPU tests put a stand-in there); PAFFY_TMPDIR. Set for the workers: PAFFY_RANK, PAFFY_WORLD, PAFFY_DEVICE, PAFFY_RANGE (stream),

@@ -259,6 +259,50 @@ int64_t paffy_hip_bed_sequences(paffy_hip_ctx *ctx);
 int paffy_hip_bed_counts(paffy_hip_ctx *ctx, int64_t sequence, int64_t start, int64_t end, uint16_t *h_counts, int accumulate);
 
 /*
+ * to_bed in parts: `paffy to_bed` sharded by sequence. The counters are per sequence (2 bytes per base) and all records that
+ * count on a sequence must meet in one context; with include_inverted a record counts on its query sequence AND on its target sequence
+ * (impl/paf_to_bed.c:170-177), which may have different owners. So a line travels to owner(query name) and, when that is another part,
+ * to owner(target name) too, every copy with a one-byte SIDE MASK: bit 0 = count the query side here, bit 1 = count the target side
+ * (as the inverted record would). One copy with mask 3 where both owners coincide, copies with masks 1 and 2 otherwise, mask 1 always
+ * without include_inverted. A line that does not parse far enough to have a target name goes with its query side only.
+ *   side_names_counts: paffy_hip_query_names_counts over the names of the counted sides: per distinct name its hash and the bytes and
+ *                lines of the records that name it as query or (include_inverted) as target -- the weights a partitioner balances. A
+ *                record counts once per side (a line without a target name mentions its query name twice, the second time with no
+ *                bytes). Without include_inverted this is exactly the query-name pass. The batch's index is kept as there.
+ *   split_sides_count: bytes and lines every part gets of this batch under the owner table (ascending hashes, a name the table lacks
+ *                goes to hash % n_parts, as paffy_hip_split_to): NOT the sums of the per-name counts, a line whose two names share an
+ *                owner is sent once. Nothing is written and the batch's kept index stays, so a caller sizes its send buffer, its index
+ *                array and its mask array exactly before it splits the first batch.
+ *   split_sides_to: paffy_hip_split_to by sides: part p's lines go to d_out + part_dst[p] in input order, the global input index
+ *                (+ rec_base) of every written line to d_rec_index + rec_dst[p] (int64, may be NULL) and its side mask to
+ *                d_sides + rec_dst[p] (one byte per line). Destinations are checked against out_cap / rec_index_cap (entries of both
+ *                arrays) before anything is written: PAFFY_E_CAPACITY. A failing call drops every kept index.
+ *   bed_add_sides: paffy_hip_bed_add with one mask byte per line of the batch (d_sides: device memory, read before the call returns).
+ *                An entry whose side is masked off bumps nothing, creates no sequence, takes no part in the length assert
+ *                (impl/paf.c:675-688) and raises no failure of its own; a line that does not parse is still reported. With
+ *                include_inverted = 0 only bit 0 is looked at. d_sides NULL: every side -- a run of NULL masks only is paffy_hip_bed_add.
+ *   bed_failure_side: after a bed run that reported a failure: 0 = found on the record's query side, 1 = on its target side, -1 = the
+ *                line did not parse (or there is no failure). Of a record's failures one context reports the first of (parse, query
+ *                side, target side); parts are compared by (global record, that order).
+ *   bed_sequence_keys: after a bed run without failure: three int64 per sequence into device memory, in the run's order of first
+ *                appearance -- the local entry it first appeared with (2 * record + side; record counts the lines of the run's batches
+ *                in the order they were added), the bytes of its block of BED lines, the number of those lines. A sequence whose lines
+ *                are all excluded has 0 bytes and still has a key. The emitted output is the blocks back to back in this order, so
+ *                paffy_hip_scatter_lines places blocks as it places lines. Returns the number of sequences.
+ * paffy_hip_bed_sequences / paffy_hip_bed_counts after such a run address this context's sequences only.
+ */
+int64_t paffy_hip_side_names_counts(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len, int include_inverted, int64_t cap, uint64_t *hashes, int64_t *weights,
+                                    int64_t *records);
+int paffy_hip_split_sides_count(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len, int include_inverted, int32_t n_parts, const uint64_t *table_hash,
+                                const uint32_t *table_owner, int64_t n_table, int64_t *part_bytes, int64_t *part_records, int64_t *n_records);
+int paffy_hip_split_sides_to(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len, int include_inverted, int32_t n_parts, const uint64_t *table_hash,
+                             const uint32_t *table_owner, int64_t n_table, void *d_out, int64_t out_cap, const int64_t *part_dst, const int64_t *rec_dst, int64_t rec_base,
+                             int64_t *part_bytes, int64_t *part_records, void *d_rec_index, void *d_sides, int64_t rec_index_cap, int64_t *n_records);
+int paffy_hip_bed_add_sides(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len, const void *d_sides);
+int paffy_hip_bed_failure_side(paffy_hip_ctx *ctx);
+int64_t paffy_hip_bed_sequence_keys(paffy_hip_ctx *ctx, int64_t cap_sequences, void *d_keys);
+
+/*
  * `paffy chain` (impl/paf_chain.c:123-127, paf_chain impl/chaining.c:266-343): the records of all batches are chained per (query,
  * target, strand) with the affine gap cost of impl/paf_chain.c:36-45 (no gap: 0, else gap_open + gap_extend * (query gap + target
  * gap)); every record gets its chain's id (cn) and score (s1) and the lines come out by descending own score. begin / add / run

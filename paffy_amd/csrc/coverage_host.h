@@ -31,6 +31,11 @@ struct CovState {
     std::vector<uint64_t> h_contig_cov;
     uint64_t n_out = 0; /* lines emit writes */
     uint32_t sides = 1; /* entries per record: 2 for to_bed -n */
+    /* to_bed in parts (paffy_hip_bed_add_sides): one byte per record, bit k = its entry k is counted in this context */
+    DevBuf side_mask, active;
+    bool has_mask = false;
+    int fail_side = -1;     /* the side (0 query, 1 target) the last run's failure was found on; -1: while parsing, or no failure */
+    std::vector<uint32_t> h_first_entry; /* per sequence in order of first appearance: the entry it first appeared with */
     uint32_t name_salt = 0; /* salt of the name hash the last run's grouping passed its byte check with (0 unless names collided) */
 };
 
@@ -206,6 +211,8 @@ static int cov_begin(paffy_hip_ctx *c, uint32_t sides) {
     S.batches.clear();
     S.n_rec = 0;
     S.n_out = 0;
+    S.has_mask = false;
+    S.fail_side = -1;
     if (ensure(c, S.info, sizeof(DevInfo))) return PAFFY_E_HIP;
     DevInfo zero;
     memset(&zero, 0, sizeof(zero));
@@ -242,6 +249,25 @@ static int cov_add(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bool with
     HIPCHK(c, hipStreamSynchronize(c->stream)); /* c->meta is reused by the next batch */
     S.batches.push_back(CovBatch{static_cast<const uint8_t *>(d_in), (uint32_t)in_len, n, first});
     S.n_rec = total;
+    return 0;
+}
+
+/* cov_add plus the batch's side mask (d_sides: one byte per line in device memory, read before this returns; NULL: every side).
+   Batches added without a mask count every side: their bytes are 3 once any batch of the run brought a mask. */
+static int cov_add_sides(paffy_hip_ctx *c, const void *d_in, int64_t in_len, const void *d_sides) {
+    CovState &S = cov_state(c);
+    const uint64_t first = S.n_rec;
+    int rc = cov_add(c, d_in, in_len, false);
+    if (rc) return rc;
+    const uint64_t n = S.n_rec - first;
+    if ((!d_sides && !S.has_mask) || S.n_rec == 0) return 0;
+    if (ensure_keep(c, S.side_mask, (size_t)S.n_rec + 16, S.has_mask ? (size_t)first : 0)) return PAFFY_E_HIP;
+    uint8_t *mask = static_cast<uint8_t *>(S.side_mask.p);
+    if (!S.has_mask && first) HIPCHK(c, hipMemsetAsync(mask, 3, (size_t)first, c->stream));
+    if (n && d_sides) HIPCHK(c, hipMemcpyAsync(mask + first, d_sides, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    if (n && !d_sides) HIPCHK(c, hipMemsetAsync(mask + first, 3, (size_t)n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    S.has_mask = true;
     return 0;
 }
 
@@ -284,6 +310,8 @@ static int cov_run(paffy_hip_ctx *c, int mode, paffy_error *err) {
     S.n_contigs = 0;
     S.cov_total = 0;
     S.appearance.clear();
+    S.h_first_entry.clear();
+    S.fail_side = -1;
     if (n == 0) return 0;
     if ((uint64_t)n * sides >= (1ull << 31)) return PAFFY_E_UNSUPPORTED;
     const uint32_t n_ent = n * sides;
@@ -299,6 +327,7 @@ static int cov_run(paffy_hip_ctx *c, int mode, paffy_error *err) {
             CovEntry E;
             if (cov_fetch(c, &E, static_cast<CovEntry *>(S.entries.p) + rec, sizeof(E))) return PAFFY_E_HIP;
             rec = E.rec;
+            S.fail_side = E.side ? 1 : 0;
         }
         err->record = (int64_t)rec;
         if (err->stage < 0) {
@@ -362,18 +391,39 @@ static int cov_run(paffy_hip_ctx *c, int mode, paffy_error *err) {
     if (ensure(c, S.scan32, sizeof(uint32_t) * ((size_t)n_ent + 1))) return PAFFY_E_HIP;
     uint32_t *flags = static_cast<uint32_t *>(S.flags.p), *scan32 = static_cast<uint32_t *>(S.scan32.p);
     uint32_t n_contigs = 0;
+    /* a side mask: only the entries it leaves are grouped into sequences (ascending, so a run's head is still its first entry) */
+    const uint8_t *side_mask = (mode == 1 && S.has_mask) ? static_cast<const uint8_t *>(S.side_mask.p) : nullptr;
+    uint32_t n_grouped = n_ent;
+    if (side_mask) {
+        if (ensure(c, S.active, sizeof(uint32_t) * ((size_t)n_ent + 1))) return PAFFY_E_HIP;
+        LAUNCH(c, "k_cov_active_flags", k_cov_active_flags, dim3(g_ent), dim3(PAFFY_NT), 0, side_mask, sides, n_ent, flags);
+        if (cov_incl_scan32(c, S, flags, scan32, n_ent)) return PAFFY_E_HIP;
+        if (cov_fetch(c, &n_grouped, scan32 + (n_ent - 1), sizeof(uint32_t))) return PAFFY_E_HIP;
+        LAUNCH(c, "k_cov_active_list", k_cov_active_list, dim3(g_ent), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(flags), static_cast<const uint32_t *>(scan32), n_ent,
+               static_cast<uint32_t *>(S.active.p));
+        if (n_grouped == 0) { /* nothing is counted here: only a line that does not parse can fail */
+            if (hinfo.first_err_key != ~0ull) return report(hinfo.first_err_key);
+            return 0;
+        }
+    }
+    const uint32_t g_grp = (n_grouped + PAFFY_NT - 1) / PAFFY_NT;
     /* sequences: entries grouped by name hash, the names then checked against their group's first (impl/paf.c:675-688 looks the name up
        by string equality): two names under one hash -> the grouping again with the next salt */
     for (uint32_t salt = 0;; salt++) {
         LAUNCH(c, "k_cov_entry_init", k_cov_entry_init, dim3(g_ent), dim3(PAFFY_NT), 0, P, mode == 0 ? order : nullptr, sides, static_cast<uint64_t *>(S.name_hash.p),
-               static_cast<int64_t *>(S.seq_len.p), salt);
-        LAUNCH(c, "k_iota32", k_iota32, dim3(g_ent), dim3(PAFFY_NT), 0, v32a, n_ent);
-        if (cov_sort_pairs(c, S, static_cast<const uint64_t *>(S.name_hash.p), k64a, v32a, v32b, n_ent)) return PAFFY_E_HIP;
-        LAUNCH(c, "k_cov_run_heads", k_cov_run_heads, dim3(g_ent), dim3(PAFFY_NT), 0, k64a, n_ent, flags);
-        if (cov_incl_scan32(c, S, flags, scan32, n_ent)) return PAFFY_E_HIP;
-        if (cov_fetch(c, &n_contigs, scan32 + (n_ent - 1), sizeof(uint32_t))) return PAFFY_E_HIP;
+               static_cast<int64_t *>(S.seq_len.p), salt, side_mask);
+        if (!side_mask) {
+            LAUNCH(c, "k_iota32", k_iota32, dim3(g_ent), dim3(PAFFY_NT), 0, v32a, n_ent);
+            if (cov_sort_pairs(c, S, static_cast<const uint64_t *>(S.name_hash.p), k64a, v32a, v32b, n_ent)) return PAFFY_E_HIP;
+        } else {
+            LAUNCH(c, "k_gather_u64", k_gather_u64, dim3(g_grp), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(S.name_hash.p), static_cast<const uint32_t *>(S.active.p), n_grouped, k64b);
+            if (cov_sort_pairs(c, S, k64b, k64a, static_cast<const uint32_t *>(S.active.p), v32b, n_grouped)) return PAFFY_E_HIP;
+        }
+        LAUNCH(c, "k_cov_run_heads", k_cov_run_heads, dim3(g_grp), dim3(PAFFY_NT), 0, k64a, n_grouped, flags);
+        if (cov_incl_scan32(c, S, flags, scan32, n_grouped)) return PAFFY_E_HIP;
+        if (cov_fetch(c, &n_contigs, scan32 + (n_grouped - 1), sizeof(uint32_t))) return PAFFY_E_HIP;
         if (ensure(c, S.first_entry, sizeof(uint32_t) * (size_t)n_contigs)) return PAFFY_E_HIP;
-        LAUNCH(c, "k_cov_assign_contig", k_cov_assign_contig, dim3(g_ent), dim3(PAFFY_NT), 0, P, v32b, static_cast<const uint32_t *>(flags), static_cast<const uint32_t *>(scan32), n_ent,
+        LAUNCH(c, "k_cov_assign_contig", k_cov_assign_contig, dim3(g_grp), dim3(PAFFY_NT), 0, P, v32b, static_cast<const uint32_t *>(flags), static_cast<const uint32_t *>(scan32), n_grouped,
                static_cast<uint32_t *>(S.first_entry.p));
         uint32_t *collide = flags + n_ent + 1, hit = 0;
         HIPCHK(c, hipMemsetAsync(collide, 0, sizeof(uint32_t), c->stream));
@@ -563,6 +613,8 @@ static int cov_run(paffy_hip_ctx *c, int mode, paffy_error *err) {
     S.n_contigs = n_contigs;
     S.cov_total = cov_total;
     S.appearance = appearance;
+    S.h_first_entry.resize(n_contigs);
+    for (uint32_t k = 0; k < n_contigs; k++) S.h_first_entry[k] = cname[appearance[k]].pad;
     S.h_contig_len = clen;
     S.h_contig_cov.assign(ccov.begin(), ccov.end());
     /* names of the sequences as one blob (to_bed prints them) */

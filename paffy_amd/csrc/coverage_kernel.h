@@ -41,11 +41,14 @@ struct CovEntry {      /* one walk, in visiting order (index = rank) */
     int64_t lo, hi;    /* range walked on the sequence, clamped to it: [lo, hi); lo == hi: nothing */
     uint64_t bm_off;   /* first word of the bitmap; word 0 holds bases [32 * (lo >> 5), +32) */
     uint32_t rec;      /* record (index into the concatenated RecMeta of all batches) */
-    uint32_t side;     /* 0: query sequence. 1 / 2: target sequence of a + / - record, as the inverted record walks it (to_bed -n) */
+    uint32_t side;     /* 0: query sequence. 1 / 2: target sequence of a + / - record, as the inverted record walks it (to_bed -n).
+                          COV_SIDE_OFF: the side is not counted here (paffy_hip_bed_add_sides): no sequence, no walk, no failure */
     uint32_t contig;   /* sequence id */
     uint32_t pair_base; /* first (entry, slice) pair of this entry = its first partial-histogram slot */
     uint32_t first_slice, n_slices;
 };
+
+#define COV_SIDE_OFF 4u
 
 struct CovSlot { /* partial level histogram of one (entry, slice): counts of levels [mn, mn + n), dense, in the arena */
     uint64_t off;
@@ -176,6 +179,7 @@ __global__ __launch_bounds__(G::NT) void k_cov_bitmap(CovParams P, int null_ciga
     const uint32_t tid = threadIdx.x;
     const uint32_t e = P.e0 + blockIdx.x;
     const CovEntry E = P.entries[e];
+    if (E.side == COV_SIDE_OFF) return; /* workgroup-uniform */
     const RecMeta &m = P.meta[E.rec];
     {
         const uint32_t route = (m.err || !m.has_cg) ? 0xffffffffu : m.cg_len; /* no cigar to read: the four-wave shape's few lines */
@@ -731,11 +735,27 @@ __global__ __launch_bounds__(PAFFY_NT) void k_gather_u64(const uint64_t *src, co
     if (i < n) dst[i] = src[idx[i]];
 }
 
-/* entry e (visiting order) -> record, side, clamped range, sequence name hash, sequence length */
-__global__ __launch_bounds__(PAFFY_NT) void k_cov_entry_init(CovParams P, const uint32_t *order, uint32_t sides, uint64_t *name_hash, int64_t *seq_len, uint32_t salt) {
+/* entry e (visiting order) -> record, side, clamped range, sequence name hash, sequence length. side_mask (to_bed in parts, or NULL:
+   every side): one byte per record, bit k = entry k of the record is counted here; an entry whose bit is clear becomes COV_SIDE_OFF */
+__global__ __launch_bounds__(PAFFY_NT) void k_cov_entry_init(CovParams P, const uint32_t *order, uint32_t sides, uint64_t *name_hash, int64_t *seq_len, uint32_t salt,
+                                                              const uint8_t *side_mask) {
     const uint32_t e = blockIdx.x * PAFFY_NT + threadIdx.x;
     if (e >= P.n_entries) return;
     const uint32_t rec = order ? order[e / sides] : e / sides;
+    if (side_mask && !((side_mask[rec] >> (e % sides)) & 1u)) {
+        CovEntry E;
+        E.lo = E.hi = 0;
+        E.bm_off = 0;
+        E.rec = rec;
+        E.side = COV_SIDE_OFF;
+        E.contig = 0;
+        E.pair_base = 0;
+        E.first_slice = E.n_slices = 0;
+        P.entries[e] = E;
+        name_hash[e] = 0;
+        seq_len[e] = 0;
+        return;
+    }
     const RecMeta &m = P.meta[rec];
     const uint32_t side = (e % sides) == 0 ? 0u : (m.same_strand ? 1u : 2u);
     const CovWalkSide S = cov_side(m, side);
@@ -771,12 +791,22 @@ __global__ __launch_bounds__(PAFFY_NT) void k_cov_verify_names(CovParams P, cons
     const uint32_t e = blockIdx.x * PAFFY_NT + threadIdx.x;
     if (e >= P.n_entries) return;
     const CovEntry &E = P.entries[e];
+    if (E.side == COV_SIDE_OFF) return;
     const uint32_t h = first_entry[E.contig];
     if (h == e) return;
     const CovEntry &H = P.entries[h];
     const RecMeta &m = P.meta[E.rec], &mh = P.meta[H.rec];
     const uint8_t *a = P.batch_in[m.pad1] + (E.side ? m.tname_off : m.qname_off), *b = P.batch_in[mh.pad1] + (H.side ? mh.tname_off : mh.qname_off);
     if (!cov_same_bytes(a, E.side ? m.tname_len : m.qname_len, b, H.side ? mh.tname_len : mh.qname_len)) atomicOr(collide, 1u);
+}
+/* the entries a side mask leaves, in ascending order: flag[e] = 1 where entry e is counted, then (after an inclusive scan) the list */
+__global__ __launch_bounds__(PAFFY_NT) void k_cov_active_flags(const uint8_t *side_mask, uint32_t sides, uint32_t n, uint32_t *flag) {
+    const uint32_t e = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (e < n) flag[e] = (side_mask[e / sides] >> (e % sides)) & 1u;
+}
+__global__ __launch_bounds__(PAFFY_NT) void k_cov_active_list(const uint32_t *flag, const uint32_t *scan, uint32_t n, uint32_t *list) {
+    const uint32_t e = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (e < n && flag[e]) list[scan[e] - 1u] = e;
 }
 /* sorted name hashes -> sequence ids: flag[i] = first of its run */
 __global__ __launch_bounds__(PAFFY_NT) void k_cov_run_heads(const uint64_t *sorted, uint32_t n, uint32_t *flag) {
@@ -802,6 +832,11 @@ __global__ __launch_bounds__(PAFFY_NT) void k_cov_entry_sizes(CovParams P, const
     const uint32_t e = blockIdx.x * PAFFY_NT + threadIdx.x;
     if (e >= P.n_entries) return;
     CovEntry &E = P.entries[e];
+    if (E.side == COV_SIDE_OFF) { /* belongs to no sequence */
+        bm_words[e] = 0;
+        n_pairs[e] = 0;
+        return;
+    }
     if (seq_len[e] != P.contig_len[E.contig]) {
         cov_fail(P, e, E.rec, PAFFY_ERR_TILE_ASSERT, 1);
         E.hi = E.lo; /* a sequence of another length: nothing of it is walked here */

@@ -1080,7 +1080,8 @@ struct paffy_hip_ctx {
     DevBuf flat_nd, flat_rec, flat_chunks, flat_sums, flat_done, flat_items, flat_pieces; /* the flat sizing pass (flat_kernel.h) */
     DevBuf add_pieces, add_scr_cnt, add_scr_off, add_new_cnt, add_new_off, add_text, add_bad, add_part, add_scratch, add_new_ops; /* flat_add_kernel.h */
     uint32_t flat_piece_slots = 0;
-    DevBuf bed_keys, bed_tab, bed_starts, bed_len, bed_off, bed_tiles;
+    DevBuf bed_keys; /* paffy_hip_bed_sequence_keys: the first entry of every sequence, staged for k_bed_seq_keys */
+    DevBuf bed_tab, bed_starts, bed_len, bed_off, bed_tiles;
     struct BedParams *bed_params = nullptr; /* host copy */
     uint64_t bed_runs = 0;
     const uint8_t *tile_in = nullptr;
@@ -2275,6 +2276,8 @@ __global__ __launch_bounds__(PAFFY_NT) void k_scatter_lines(const uint8_t *src, 
     copy_line(src + src_off[k], (uint64_t)(src_off[k + 1] - src_off[k]), dst + dst_off[k], false);
 }
 
+#include "bed_parts_kernel.h"
+
 /* the kept indexes (see paffy_hip_ctx::kept_index): copy out after query_names, copy back for split_by_owner */
 static void index_drop(paffy_hip_ctx *c, const void *d_in) {
     for (size_t i = 0; i < c->kept_index.size(); i++)
@@ -2305,7 +2308,7 @@ static int index_keep(paffy_hip_ctx *c, const void *d_in, int64_t in_len, uint32
     return 0;
 }
 /* 0: the index buffers describe d_in again; 1: nothing kept for it */
-static int index_restore(paffy_hip_ctx *c, const void *d_in, int64_t in_len, uint32_t *n) {
+static int index_restore(paffy_hip_ctx *c, const void *d_in, int64_t in_len, uint32_t *n, bool keep = false) {
     for (size_t i = 0; i < c->kept_index.size(); i++) {
         paffy_hip_ctx::KeptIndex &k = c->kept_index[i];
         if (k.in != d_in || k.len != in_len) continue;
@@ -2317,7 +2320,7 @@ static int index_restore(paffy_hip_ctx *c, const void *d_in, int64_t in_len, uin
             hipStreamSynchronize(c->stream) != hipSuccess) /* the kept copy is freed below */
             return 1;
         *n = k.n;
-        index_drop(c, d_in);
+        if (!keep) index_drop(c, d_in);
         return 0;
     }
     return 1;
@@ -2327,7 +2330,7 @@ static void index_drop_all(paffy_hip_ctx *c) {
     while (!c->kept_index.empty()) index_drop(c, c->kept_index.back().in);
     c->indexed_in = nullptr;
 }
-static int64_t query_names_impl(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int64_t cap, uint64_t *hashes, int64_t *weights, int64_t *records) {
+static int64_t query_names_impl(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int64_t cap, uint64_t *hashes, int64_t *weights, int64_t *records, bool with_target = false) {
     if (!c || !hashes || !weights || cap < 0) return PAFFY_E_ARG;
     if (in_len < 0 || in_len >= (1ll << 31) - 64 || (in_len > 0 && !d_in) || (reinterpret_cast<uintptr_t>(d_in) & 15)) return PAFFY_E_ARG;
     if (in_len == 0) return 0;
@@ -2342,6 +2345,8 @@ static int64_t query_names_impl(paffy_hip_ctx *c, const void *d_in, int64_t in_l
     c->indexed_len = in_len;
     c->indexed_n = n;
     if (index_keep(c, d_in, in_len, n)) return PAFFY_E_HIP;
+    const uint32_t n_lines = n, g_lines = (n + PAFFY_NT - 1) / PAFFY_NT;
+    if (with_target) n = 2 * n_lines; /* an item per side (n_lines < 2^31) */
     const uint32_t g = (n + PAFFY_NT - 1) / PAFFY_NT;
     if (ensure(c, S.k64a, sizeof(uint64_t) * ((size_t)n + 1)) || ensure(c, S.k64b, sizeof(uint64_t) * ((size_t)n + 1)) || ensure(c, S.name_hash, sizeof(uint64_t) * ((size_t)n + 1)) ||
         ensure(c, S.v32a, sizeof(uint32_t) * ((size_t)n + 1)) || ensure(c, S.v32b, sizeof(uint32_t) * ((size_t)n + 1)) || ensure(c, S.flags, sizeof(uint32_t) * ((size_t)n + 1)) ||
@@ -2349,8 +2354,12 @@ static int64_t query_names_impl(paffy_hip_ctx *c, const void *d_in, int64_t in_l
         return PAFFY_E_HIP;
     uint64_t *hash = static_cast<uint64_t *>(S.name_hash.p), *len = static_cast<uint64_t *>(S.k64b.p), *sorted = static_cast<uint64_t *>(S.k64a.p);
     uint32_t *idx = static_cast<uint32_t *>(S.v32a.p), *sidx = static_cast<uint32_t *>(S.v32b.p), *flags = static_cast<uint32_t *>(S.flags.p), *scan = static_cast<uint32_t *>(S.scan32.p);
-    LAUNCH(c, "k_query_hash", k_query_hash, dim3(g), dim3(PAFFY_NT), 0, in, static_cast<const RecMeta *>(c->meta.p), static_cast<const uint32_t *>(c->sep_pos.p),
-           static_cast<const uint32_t *>(c->nl_idx.p), n, (uint32_t)in_len, hash, len, idx);
+    if (with_target)
+        LAUNCH(c, "k_side_hash", k_side_hash, dim3(g_lines), dim3(PAFFY_NT), 0, in, static_cast<const RecMeta *>(c->meta.p), static_cast<const uint32_t *>(c->sep_pos.p),
+               static_cast<const uint32_t *>(c->nl_idx.p), n_lines, hash, len, idx);
+    else
+        LAUNCH(c, "k_query_hash", k_query_hash, dim3(g), dim3(PAFFY_NT), 0, in, static_cast<const RecMeta *>(c->meta.p), static_cast<const uint32_t *>(c->sep_pos.p),
+               static_cast<const uint32_t *>(c->nl_idx.p), n, (uint32_t)in_len, hash, len, idx);
     if (cov_sort_pairs(c, S, hash, sorted, idx, sidx, n)) return PAFFY_E_HIP;
     LAUNCH(c, "k_cov_run_heads", k_cov_run_heads, dim3(g), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(sorted), n, flags);
     if (cov_incl_scan32(c, S, flags, scan, n)) return PAFFY_E_HIP;
@@ -2487,6 +2496,119 @@ int paffy_hip_split_to(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int32
     if (!part_dst || !rec_dst) return PAFFY_E_ARG;
     return split_impl(c, d_in, in_len, n_parts, table_hash, table_owner, n_table, d_out, out_cap, part_dst, rec_dst, rec_base, part_bytes, part_records, d_rec_index,
                       rec_index_cap, n_records);
+}
+int64_t paffy_hip_side_names_counts(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int include_inverted, int64_t cap, uint64_t *hashes, int64_t *weights, int64_t *records) {
+    if (!records) return PAFFY_E_ARG;
+    const int64_t n = query_names_impl(c, d_in, in_len, cap, hashes, weights, records, include_inverted != 0);
+    if (n < 0 && c) index_drop_all(c);
+    return n;
+}
+
+/* the partition by the names of both sides: sizes only (d_out NULL; the batch's kept index stays) or the copy */
+static int split_sides_impl0(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bool with_target, int32_t n_parts, const uint64_t *table_hash, const uint32_t *table_owner,
+                             int64_t n_table, bool count_only, void *d_out, int64_t out_cap, const int64_t *part_dst, const int64_t *rec_dst, int64_t rec_base,
+                             int64_t *part_bytes, int64_t *part_records, void *d_rec_index, void *d_sides, int64_t rec_index_cap, int64_t *n_records) {
+    if (!c || n_parts < 1 || n_table < 0 || (n_table > 0 && (!table_hash || !table_owner)) || !part_bytes || !part_records || !n_records) return PAFFY_E_ARG;
+    if (in_len < 0 || in_len >= (1ll << 31) - 64 || (in_len > 0 && !d_in) || (reinterpret_cast<uintptr_t>(d_in) & 15)) return PAFFY_E_ARG;
+    if (!count_only && (!part_dst || !rec_dst)) return PAFFY_E_ARG;
+    for (int32_t p = 0; p < n_parts; p++) part_bytes[p] = part_records[p] = 0;
+    *n_records = 0;
+    if (in_len == 0) return 0;
+    if (!count_only && (!d_out || !d_sides)) return PAFFY_E_ARG;
+    CovState &S = cov_state(c);
+    uint32_t n = 0;
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    if (c->indexed_in == d_in && c->indexed_len == in_len) { /* the index buffers describe this batch */
+        n = c->indexed_n;
+        if (!count_only) index_drop(c, d_in);
+    } else if (index_restore(c, d_in, in_len, &n, count_only) != 0) {
+        int rc = index_and_parse(c, in, (uint32_t)in_len, &n);
+        if (rc) return rc;
+    }
+    c->indexed_in = nullptr;
+    *n_records = n;
+    if (n == 0) return 0;
+    if (count_only) { /* the split of the same batch may follow at once */
+        c->indexed_in = d_in;
+        c->indexed_len = in_len;
+        c->indexed_n = n;
+    }
+    const uint32_t n_items = with_target ? 2 * n : n, np1 = (uint32_t)n_parts + 1u;
+    const uint32_t g = (n + PAFFY_NT - 1) / PAFFY_NT, gi = (n_items + PAFFY_NT - 1) / PAFFY_NT;
+    if (ensure(c, S.k64a, sizeof(uint64_t) * ((size_t)n_items + 1)) || ensure(c, S.k64b, sizeof(uint64_t) * ((size_t)n_items + 1)) || ensure(c, S.name_hash, sizeof(uint64_t) * ((size_t)n + 1)) ||
+        ensure(c, S.v32a, sizeof(uint32_t) * ((size_t)n + 1)) || ensure(c, S.v32b, (size_t)n_items + 16) || ensure(c, S.bm_words, sizeof(uint64_t) * ((size_t)n_items + 1)) ||
+        ensure(c, S.bm_off, sizeof(uint64_t) * ((size_t)n_items + 2)) || ensure(c, S.pairs, (sizeof(uint64_t) + sizeof(uint32_t)) * ((size_t)n_table + 1)) ||
+        ensure(c, S.pairs2, sizeof(int64_t) * 4 * (size_t)np1) || ensure(c, S.seq_len, sizeof(uint64_t) * ((size_t)n + 1)))
+        return PAFFY_E_HIP;
+    uint64_t *hash = static_cast<uint64_t *>(S.name_hash.p), *len = static_cast<uint64_t *>(S.seq_len.p), *key = static_cast<uint64_t *>(S.k64a.p), *skey = static_cast<uint64_t *>(S.bm_words.p);
+    uint64_t *lens = static_cast<uint64_t *>(S.k64b.p), *off = static_cast<uint64_t *>(S.bm_off.p);
+    uint8_t *item_mask = static_cast<uint8_t *>(S.v32b.p);
+    uint64_t *d_th = static_cast<uint64_t *>(S.pairs.p);
+    uint32_t *d_to = reinterpret_cast<uint32_t *>(d_th + n_table + 1);
+    if (n_table) {
+        HIPCHK(c, hipMemcpyAsync(d_th, table_hash, sizeof(uint64_t) * (size_t)n_table, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_to, table_owner, sizeof(uint32_t) * (size_t)n_table, hipMemcpyHostToDevice, c->stream));
+    }
+    LAUNCH(c, "k_query_hash", k_query_hash, dim3(g), dim3(PAFFY_NT), 0, in, static_cast<const RecMeta *>(c->meta.p), static_cast<const uint32_t *>(c->sep_pos.p),
+           static_cast<const uint32_t *>(c->nl_idx.p), n, (uint32_t)in_len, hash, len, static_cast<uint32_t *>(S.v32a.p));
+    LAUNCH(c, "k_side_owner_keys", k_side_owner_keys, dim3(g), dim3(PAFFY_NT), 0, in, static_cast<const RecMeta *>(c->meta.p), n, with_target ? 1u : 0u,
+           static_cast<const uint64_t *>(d_th), static_cast<const uint32_t *>(d_to), (uint32_t)n_table, (uint32_t)n_parts, key, item_mask);
+    if (cov_sort_keys(c, S, key, skey, n_items)) return PAFFY_E_HIP; /* (part, record, side): input order inside a part */
+    LAUNCH(c, "k_side_gather_len", k_side_gather_len, dim3(gi), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(skey), static_cast<const uint64_t *>(len), n_items, (uint32_t)n_parts, lens);
+    if (cov_excl_scan64(c, S, lens, off, n_items)) return PAFFY_E_HIP;
+    int64_t *d_tot = static_cast<int64_t *>(S.pairs2.p);
+    HIPCHK(c, hipMemsetAsync(d_tot, 0xff, sizeof(int64_t) * 2 * (size_t)np1, c->stream));
+    LAUNCH(c, "k_side_part_bounds", k_side_part_bounds, dim3(gi), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(skey), static_cast<const uint64_t *>(off), n_items, d_tot, d_tot + np1);
+    std::vector<int64_t> tot(2 * (size_t)np1);
+    uint64_t all_bytes = 0;
+    HIPCHK(c, hipMemcpyAsync(&all_bytes, off + n_items, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (cov_fetch(c, tot.data(), d_tot, sizeof(int64_t) * 2 * (size_t)np1)) return PAFFY_E_HIP;
+    int64_t next_first = (int64_t)n_items, next_start = (int64_t)all_bytes; /* a part ends where the next non-empty one starts */
+    for (int32_t p = n_parts; p >= 0; p--) {
+        const int64_t first = tot[(size_t)p], start = tot[(size_t)np1 + p];
+        if (first < 0) continue;
+        if (p < n_parts) {
+            part_records[p] = next_first - first;
+            part_bytes[p] = next_start - start;
+        }
+        next_first = first;
+        next_start = start;
+    }
+    if (count_only) return 0;
+    const int64_t n_sent = tot[(size_t)n_parts] >= 0 ? tot[(size_t)n_parts] : (int64_t)n_items;
+    std::vector<int64_t> dst(2 * (size_t)n_parts);
+    for (int32_t p = 0; p < n_parts; p++) {
+        if (part_dst[p] < 0 || rec_dst[p] < 0 || part_dst[p] + part_bytes[p] > out_cap || rec_dst[p] + part_records[p] > rec_index_cap) {
+            for (int32_t q = 0; q < n_parts; q++) part_bytes[q] = part_records[q] = 0;
+            return PAFFY_E_CAPACITY;
+        }
+        dst[(size_t)p] = part_dst[p];
+        dst[(size_t)n_parts + p] = rec_dst[p];
+    }
+    HIPCHK(c, hipMemcpyAsync(d_tot + 2 * np1, dst.data(), sizeof(int64_t) * 2 * (size_t)n_parts, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* `dst` is a local */
+    if (n_sent > 0)
+        LAUNCH(c, "k_split_sides_copy", k_split_sides_copy, dim3((unsigned)n_sent), dim3(PAFFY_NT), 0, in, (uint32_t)in_len, static_cast<const uint32_t *>(c->sep_pos.p),
+               static_cast<const uint32_t *>(c->nl_idx.p), static_cast<const uint64_t *>(skey), static_cast<const uint64_t *>(off), static_cast<uint8_t *>(d_out),
+               static_cast<const int64_t *>(d_tot), static_cast<const int64_t *>(d_tot + np1), static_cast<const int64_t *>(d_tot + 2 * np1),
+               static_cast<const int64_t *>(d_tot + 2 * np1 + n_parts), n, static_cast<const uint8_t *>(item_mask), static_cast<int64_t *>(d_rec_index),
+               static_cast<uint8_t *>(d_sides), rec_base);
+    return 0;
+}
+int paffy_hip_split_sides_count(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int include_inverted, int32_t n_parts, const uint64_t *table_hash, const uint32_t *table_owner,
+                                int64_t n_table, int64_t *part_bytes, int64_t *part_records, int64_t *n_records) {
+    const int rc = split_sides_impl0(c, d_in, in_len, include_inverted != 0, n_parts, table_hash, table_owner, n_table, true, nullptr, 0, nullptr, nullptr, 0, part_bytes,
+                                     part_records, nullptr, nullptr, 0, n_records);
+    if (rc && c) index_drop_all(c);
+    return rc;
+}
+int paffy_hip_split_sides_to(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int include_inverted, int32_t n_parts, const uint64_t *table_hash, const uint32_t *table_owner,
+                             int64_t n_table, void *d_out, int64_t out_cap, const int64_t *part_dst, const int64_t *rec_dst, int64_t rec_base, int64_t *part_bytes,
+                             int64_t *part_records, void *d_rec_index, void *d_sides, int64_t rec_index_cap, int64_t *n_records) {
+    const int rc = split_sides_impl0(c, d_in, in_len, include_inverted != 0, n_parts, table_hash, table_owner, n_table, false, d_out, out_cap, part_dst, rec_dst, rec_base,
+                                     part_bytes, part_records, d_rec_index, d_sides, rec_index_cap, n_records);
+    if (rc && c) index_drop_all(c);
+    return rc;
 }
 int paffy_hip_drop_index(paffy_hip_ctx *c, const void *d_in) {
     if (!c) return PAFFY_E_ARG;
@@ -3113,6 +3235,10 @@ int paffy_hip_bed_add(paffy_hip_ctx *c, const void *d_in, int64_t in_len) {
     if (!c) return PAFFY_E_ARG;
     return cov_add(c, d_in, in_len, false);
 }
+int paffy_hip_bed_add_sides(paffy_hip_ctx *c, const void *d_in, int64_t in_len, const void *d_sides) {
+    if (!c) return PAFFY_E_ARG;
+    return cov_add_sides(c, d_in, in_len, d_sides);
+}
 int paffy_hip_bed_run(paffy_hip_ctx *c, const paffy_bed_opts *opts, paffy_plan_info *info) {
     if (!c || !info || !opts) return PAFFY_E_ARG;
     CovState &S = cov_state(c);
@@ -3266,6 +3392,31 @@ __global__ __launch_bounds__(PAFFY_NT) void k_counts_add_sat(uint16_t *acc, cons
     if (i >= n) return;
     const uint32_t s = (uint32_t)acc[i] + add[i]; /* one record at a time stops at INT16_MAX - 1 (impl/paf.c:701); so does the sum */
     acc[i] = acc[i] >= 32766 ? acc[i] : (uint16_t)(s < 32766u ? s : 32766u);
+}
+int paffy_hip_bed_failure_side(paffy_hip_ctx *c) {
+    if (!c || !c->planned || c->plan_kind != PLAN_BED || !c->cov || !c->plan.error.code) return -1;
+    return c->cov->fail_side;
+}
+int64_t paffy_hip_bed_sequence_keys(paffy_hip_ctx *c, int64_t cap_sequences, void *d_keys) {
+    if (!c || cap_sequences < 0) return PAFFY_E_ARG;
+    if (!c->planned || c->plan_kind != PLAN_BED || !c->cov || c->plan.error.code) return PAFFY_E_STATE;
+    CovState &S = *c->cov;
+    const size_t ns = S.appearance.size();
+    if (S.n_rec == 0 || ns == 0) return 0;
+    if (!d_keys) return PAFFY_E_ARG;
+    if ((size_t)cap_sequences < ns) return PAFFY_E_CAPACITY;
+    /* A run that wrote nothing (every line excluded) returned before the run finder: bed_starts / bed_len / bed_off are an earlier run's, but
+       plan_begin has set bed_runs to 0, so k_bed_seq_keys reads none of them and gives every sequence 0 bytes (b0 = b1 = out_bytes = 0)
+       and 0 lines. */
+    std::vector<int64_t> first(ns);
+    for (size_t k = 0; k < ns; k++) first[k] = S.sides == 2 ? (int64_t)S.h_first_entry[k] : 2 * (int64_t)S.h_first_entry[k]; /* 2 * record + side */
+    if (ensure(c, c->bed_keys, sizeof(int64_t) * ns)) return PAFFY_E_HIP;
+    HIPCHK(c, hipMemcpyAsync(c->bed_keys.p, first.data(), sizeof(int64_t) * ns, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* `first` is a local */
+    LAUNCH(c, "k_bed_seq_keys", k_bed_seq_keys, dim3((unsigned)ns), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(c->bed_starts.p), c->bed_runs,
+           static_cast<const int64_t *>(c->bed_len.p), static_cast<const int64_t *>(c->bed_off.p), c->plan.out_bytes, c->bed_params->contig_base, (uint32_t)ns,
+           static_cast<const int64_t *>(c->bed_keys.p), static_cast<int64_t *>(d_keys));
+    return (int64_t)ns;
 }
 int64_t paffy_hip_bed_sequences(paffy_hip_ctx *c) {
     if (!c) return PAFFY_E_ARG;

@@ -140,6 +140,17 @@ def lib():
         L.paffy_hip_split_to.argtypes = [vp, vp, i64, i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), i64, vp, i64, C.POINTER(i64), C.POINTER(i64), i64, C.POINTER(i64),
                                          C.POINTER(i64), vp, i64, C.POINTER(i64)]
         L.paffy_hip_drop_index.argtypes = [vp, vp]
+        L.paffy_hip_side_names_counts.restype = i64
+        L.paffy_hip_side_names_counts.argtypes = [vp, vp, i64, C.c_int, i64, C.POINTER(C.c_uint64), C.POINTER(i64), C.POINTER(i64)]
+        L.paffy_hip_split_sides_count.argtypes = [vp, vp, i64, C.c_int, i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        L.paffy_hip_split_sides_to.argtypes = [vp, vp, i64, C.c_int, i32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), i64, vp, i64, C.POINTER(i64), C.POINTER(i64), i64,
+                                               C.POINTER(i64), C.POINTER(i64), vp, vp, i64, C.POINTER(i64)]
+        L.paffy_hip_bed_add_sides.argtypes = [vp, vp, i64, vp]
+        L.paffy_hip_bed_failure_side.argtypes = [vp]
+        L.paffy_hip_bed_sequence_keys.restype = i64
+        L.paffy_hip_bed_sequence_keys.argtypes = [vp, i64, vp]
+        L.paffy_hip_bed_sequences.restype = i64
+        L.paffy_hip_bed_sequences.argtypes = [vp]
         L.paffy_hip_scatter_lines.argtypes = [vp, vp, vp, vp, i64, vp]
         L.paffy_hip_stream_open.argtypes = [vp, C.POINTER(Stage), i32, i64, i64, C.POINTER(vp)]
         L.paffy_hip_stream_input.restype = vp
@@ -289,15 +300,19 @@ class Engine:
             raise RuntimeError(f"paffy_hip_query_names failed ({n}): {lib().paffy_hip_last_error(self._ctx).decode()}")
         return {int(h[i]): int(w[i]) for i in range(n)}
 
-    def query_names_counts(self, d_in, in_len, cap=1 << 20):
-        """Distinct query names of a device batch as {hash: (bytes of its lines, number of its lines)}."""
+    def query_names_counts(self, d_in, in_len, cap=1 << 20, sides=None):
+        """Distinct query names of a device batch as {hash: (bytes of its lines, number of its lines)}. sides (None, or the
+        include_inverted of a to_bed in parts): the names of the counted sides instead (paffy_hip_side_names_counts)."""
         cap0 = 4096  # the usual input has a few dozen sequences; the host arrays are kept and grown on demand
         while True:
             arrs = getattr(self, "_name_arrays", None)
             if arrs is None or len(arrs[0]) < cap0:
                 arrs = self._name_arrays = ((C.c_uint64 * cap0)(), (C.c_int64 * cap0)(), (C.c_int64 * cap0)())
             h, w, r = arrs
-            n = lib().paffy_hip_query_names_counts(self._ctx, C.c_void_p(d_in.data_ptr()), in_len, len(h), h, w, r)
+            if sides is None:
+                n = lib().paffy_hip_query_names_counts(self._ctx, C.c_void_p(d_in.data_ptr()), in_len, len(h), h, w, r)
+            else:
+                n = lib().paffy_hip_side_names_counts(self._ctx, C.c_void_p(d_in.data_ptr()), in_len, int(bool(sides)), len(h), h, w, r)
             if n == -4 and len(h) < cap:  # PAFFY_E_CAPACITY: more names than the arrays hold
                 cap0 = min(cap, len(h) * 16)
                 continue
@@ -336,6 +351,64 @@ class Engine:
         self._check(lib().paffy_hip_split_to(self._ctx, C.c_void_p(d_in.data_ptr()), in_len, n_parts, th, to, nt, C.c_void_p(d_out.data_ptr()), d_out.numel(), pd, rd, rec_base,
                                              pb, pr, C.c_void_p(d_rec_index.data_ptr()), d_rec_index.numel(), C.byref(nrec)), "paffy_hip_split_to")
         return list(pb), list(pr), nrec.value
+
+    # ---- to_bed in parts: `paffy to_bed` sharded by sequence (include/paffy_hip.h; shard.to_bed_sharded drives these) ----
+    def side_names_counts(self, d_in, in_len, include_inverted, cap=1 << 20):
+        """{hash: (bytes, lines)} of the names a device batch counts on: its query names and, with include_inverted, its target names."""
+        return self.query_names_counts(d_in, in_len, cap, sides=bool(include_inverted))
+
+    def split_sides_count(self, d_in, in_len, include_inverted, n_parts, owner_arrays):
+        """(bytes per part, lines per part, records of the batch) split_sides_to would write: a line whose two names share an owner is
+        sent once, so these are not sums over names. Nothing is written, the batch's kept index stays."""
+        th, to, nt = owner_arrays
+        pb, pr, nrec = (C.c_int64 * n_parts)(), (C.c_int64 * n_parts)(), C.c_int64()
+        self._check(lib().paffy_hip_split_sides_count(self._ctx, C.c_void_p(d_in.data_ptr()), in_len, int(bool(include_inverted)), n_parts, th, to, nt, pb, pr, C.byref(nrec)),
+                    "paffy_hip_split_sides_count")
+        return list(pb), list(pr), nrec.value
+
+    def split_sides_to(self, d_in, in_len, include_inverted, n_parts, owner_arrays, d_out, part_dst, d_rec_index, d_sides, rec_dst, rec_base):
+        """split_to by the names of both sides: part p's lines to d_out[part_dst[p]:], the global index of every one of them to
+        d_rec_index[rec_dst[p]:] (int64) and its side mask to d_sides[rec_dst[p]:] (uint8). Returns (bytes per part, lines per part,
+        records of the batch)."""
+        th, to, nt = owner_arrays
+        pb, pr, nrec = (C.c_int64 * n_parts)(), (C.c_int64 * n_parts)(), C.c_int64()
+        pd, rd = (C.c_int64 * n_parts)(*part_dst), (C.c_int64 * n_parts)(*rec_dst)
+        self._check(lib().paffy_hip_split_sides_to(self._ctx, C.c_void_p(d_in.data_ptr()), in_len, int(bool(include_inverted)), n_parts, th, to, nt, C.c_void_p(d_out.data_ptr()),
+                                                   d_out.numel(), pd, rd, rec_base, pb, pr, C.c_void_p(d_rec_index.data_ptr()), C.c_void_p(d_sides.data_ptr()),
+                                                   min(d_rec_index.numel(), d_sides.numel()), C.byref(nrec)), "paffy_hip_split_sides_to")
+        return list(pb), list(pr), nrec.value
+
+    def bed_part(self, bufs, sides=None, binary=False, exclude_unaligned=False, exclude_aligned=False, min_size=1, include_inverted=False):
+        """begin, add every device batch [(uint8 tensor, nbytes)] -- with sides[b], a uint8 device tensor holding the side mask of every
+        line of batch b, where given (None: every side) -- and run. Returns the PlanInfo (error.record counts the lines added)."""
+        L = lib()
+        opts = BedOpts(int(binary), int(exclude_unaligned), int(exclude_aligned), int(include_inverted), min_size)
+        self._check(L.paffy_hip_bed_begin(self._ctx, C.byref(opts)), "paffy_hip_bed_begin")
+        for b, (buf, nbytes) in enumerate(bufs):
+            m = sides[b] if sides is not None else None
+            if m is not None and (m.dtype != self.torch.uint8 or not m.is_contiguous() or m.device != self.device):
+                raise ValueError("the side masks of a batch: a contiguous uint8 tensor on the engine's device")
+            self._check(L.paffy_hip_bed_add_sides(self._ctx, C.c_void_p(buf.data_ptr()), nbytes, C.c_void_p(m.data_ptr()) if m is not None and m.numel() else None),
+                        "paffy_hip_bed_add_sides")
+        info = PlanInfo()
+        self._check(L.paffy_hip_bed_run(self._ctx, C.byref(opts), C.byref(info)), "paffy_hip_bed_run")
+        return info
+
+    def bed_failure_side(self):
+        """After a bed run that failed: 0 = on the record's query side, 1 = on its target side, -1 = the line did not parse."""
+        return int(lib().paffy_hip_bed_failure_side(self._ctx))
+
+    def bed_sequence_keys(self):
+        """After a bed run: int64 device tensor [sequences, 3] -- the local entry (2 * record + side) a sequence first appeared with, the
+        bytes of its block of BED lines, its number of lines -- in the run's order of first appearance (the order of the output)."""
+        n = lib().paffy_hip_bed_sequences(self._ctx)
+        if n < 0:
+            self._check(int(n), "paffy_hip_bed_sequences")
+        keys = self.torch.empty((max(1, n), 3), dtype=self.torch.int64, device=self.device)
+        got = lib().paffy_hip_bed_sequence_keys(self._ctx, n, C.c_void_p(keys.data_ptr()))
+        if got < 0:
+            self._check(int(got), "paffy_hip_bed_sequence_keys")
+        return keys[:got]
 
     def drop_index(self, d_in=None):
         """Forget the line index query_names kept for a batch that will not be split (None: for every batch)."""

@@ -699,13 +699,19 @@ def least_failure(failures):
     return {"code": code, "stage": stage, "record": record, "aux": aux}
 
 
-def part_failure(info, fail=None):
+def part_failure(info, fail=None, side=None, record=None):
     """A part's PlanInfo (and the failing line's key after renumber) as first_failure / least_failure take it. read_pafs parses every
     line before anything is chained, so stage -1 sorts before the asserts of the trim (stage 0), the lowest global record first; a
-    failed paf_check sorts by (chain id, link): the order the reference checks in (impl/chaining.c:321-334)."""
+    failed paf_check sorts by (chain id, link): the order the reference checks in (impl/chaining.c:321-334).
+    side (to_bed in parts: -1 the line did not parse, 0 query side, 1 target side) and record (the failing line's global input
+    number): to_bed reads, counts and checks record by record (impl/paf_to_bed.c:166-180), a record's query side before its target
+    side, so its failures sort by (global record, parse before query side before target side)."""
     e = info.error
     if not e.code:
         return None
+    if side is not None:
+        rec = e.record if record is None else record
+        return (rec, side + 1, 0), (e.code, e.stage, rec, e.aux)
     return ((fail[1], fail[2], 0) if fail else (e.stage, e.record, 0)), (e.code, e.stage, e.record, e.aux)
 
 
@@ -836,3 +842,254 @@ def chain_in_parts(workers, batches, first_record=0):
             src_off[1:] = torch.cumsum(k[:, 3], 0)
             w.scatter(w.emit(), src_off, offsets.contiguous(), out)
     return {"error": None, "out": out[:total], "total": total, "chain_ids": ids, "tail_keys": tails, "line_keys": keys}
+
+
+# ---- to_bed across ranks -----------------------------------------------------------------------
+#
+# `paffy to_bed` keeps two bytes per base of every sequence and all records that count on a sequence must meet in one place, so it is
+# sharded by SEQUENCE. Without -n that is tile's partition by query name. With -n (--includeInverted) a record also counts on its target
+# sequence, as the inverted record would (impl/paf_to_bed.c:170-177), and the two sequences may have different owners:
+#   1. side_names: the distinct names of the counted sides and the bytes of the lines that name them, merged over the ranks and dealt
+#      (merge_name_weights, owner_table);
+#   2. split_sides: a line goes to owner(query name) and, when that is another rank, to owner(target name) too; every copy carries a side
+#      mask (bit 0: count the query side here, bit 1: the target side) and its global input number. exchange_lines moves text and numbers,
+#      exchange_sides the masks;
+#   3. run_part: the rank counts the sides it was given and plans its BED lines: one block of lines per sequence, the blocks in the
+#      order its sequences first appeared in;
+#   4. an all-gather of (2 * global record of first appearance + side, block bytes) -- 32 bytes per sequence -- and bed_block_offsets give
+#      every block its place: one process writes the sequences in order of first appearance, a record's query side before its target side.
+# The -q tail of the command (sequences of a FASTA file that no record names, impl/paf_to_bed.c:187-190) is not part of this: the caller
+# appends it from the union of the names seen, as the command line does after its single run. The counters a rank holds afterwards
+# (Engine / paffy_hip_bed_counts) are those of its own sequences only.
+
+
+def bed_block_offsets(all_keys, owner, rank):
+    """all_keys: int64 [N, >= 2] = (2 * global record of first appearance + side, bytes of the block, ...) of ALL sequences, every
+    part's in its own output order; owner: the part of every row. The single-process order is ascending key. Returns (byte offset of
+    every block of `rank`, in that rank's own order; total bytes). A block of 0 bytes (every line excluded) keeps its place."""
+    import torch
+
+    order = torch.sort(all_keys[:, 0], stable=True).indices
+    sizes = all_keys[order, 1]
+    ends = torch.cumsum(sizes, 0)
+    offs = ends - sizes
+    mine = owner[order] == rank  # a part's records stand in global input order: its blocks keep their relative order
+    return offs[mine], int(ends[-1].item()) if ends.numel() else 0
+
+
+def exchange_sides(dist, send_sides, send_records, comm_device="cpu"):
+    """The side masks of exchange_lines' lines: uint8, one per line, grouped by destination like the global input numbers. Returns
+    (masks, lines received from every source rank): the second says how many lines each of exchange_lines' pieces holds."""
+    import torch
+
+    if dist is None or dist.get_world_size() == 1:
+        return send_sides[: int(sum(send_records))], [int(send_records[0])]
+    rank, world = dist.get_rank(), dist.get_world_size()
+    sizes = torch.tensor(list(send_records), dtype=torch.int64, device=comm_device)
+    got = torch.zeros_like(sizes)
+    dist.all_to_all_single(got, sizes)
+    recv_records = [int(x) for x in got.tolist()]
+    src = _comm(send_sides[: sum(send_records)], comm_device)
+    recv = torch.empty(sum(recv_records), dtype=torch.uint8, device=comm_device)
+    _pairwise_exchange(dist, rank, world, src, list(send_records), recv, recv_records, EXCHANGE_CHUNK)
+    return recv, recv_records
+
+
+BED_OPTS = ("binary", "exclude_unaligned", "exclude_aligned", "min_size", "include_inverted")
+
+
+class GpuBedWorker(GpuTileWorker):
+    """The device side of a rank in to_bed_sharded(): the partition by the names of both sides and the masked coverage run, through
+    the to_bed-in-parts calls of libpaffy_hip."""
+
+    def __init__(self, eng, batch_bytes=(1 << 30) + (1 << 29)):
+        super().__init__(eng, batch_bytes)
+        self.gidx = self.piece_lines = None
+
+    def release(self):
+        super().release()
+        self.gidx = self.piece_lines = None
+
+    def side_names(self, batches, include_inverted):
+        """-> ({name hash: bytes of the lines that count on it} over all batches, [per batch: {name hash: (bytes, lines)}])"""
+        self.release()
+        out, per_batch = {}, []
+        for buf, nbytes in batches:
+            names = self.eng.side_names_counts(buf, nbytes, include_inverted)
+            per_batch.append(names)
+            for h, (w, _) in names.items():
+                out[h] = out.get(h, 0) + w
+        return out, per_batch
+
+    def split_sides(self, batches, owner_of, world, first_record, include_inverted, consume=False):
+        """-> (send buffer grouped by destination, bytes per destination, global input index of every written line, its side mask,
+        lines per destination). A counting pass over every batch (paffy_hip_split_sides_count) gives the exact sizes first -- a line
+        whose two names share an owner is sent once --, so the send buffer, the index array and the mask array are allocated once at
+        their exact size, as split() does from the per-name counts."""
+        t = self.eng.torch
+        dev = self.eng.device
+        arrays = self.eng.owner_arrays(owner_of)
+        n_batches = len(batches)
+        need_b, need_r = [], []
+        for buf, n in batches:
+            pb, pr, _ = self.eng.split_sides_count(buf, n, include_inverted, world, arrays)
+            need_b.append(pb)
+            need_r.append(pr)
+        dest_bytes = [sum(need_b[b][d] for b in range(n_batches)) for d in range(world)]
+        dest_recs = [sum(need_r[b][d] for b in range(n_batches)) for d in range(world)]
+        total_r = sum(dest_recs)
+        pad = (lambda x: (x + 15) // 16 * 16) if world == 1 else (lambda x: x)  # one rank: every batch's lines are run where they are
+        total = sum(pad(need_b[b][d]) for b in range(n_batches) for d in range(world))
+        send = t.empty(big_buffer_bytes((total + 15) // 16 * 16 + 16), dtype=t.uint8, device=dev)
+        gidx = t.empty(max(1, total_r), dtype=t.int64, device=dev)
+        sides = t.empty(max(1, total_r), dtype=t.uint8, device=dev)
+        at_b, at_r = [0] * world, [0] * world
+        for d in range(1, world):
+            at_b[d] = at_b[d - 1] + dest_bytes[d - 1]
+            at_r[d] = at_r[d - 1] + dest_recs[d - 1]
+        base = first_record
+        pieces, piece_lines = [], []
+        for b in range(n_batches):
+            buf, n = batches[0] if consume else batches[b]
+            pb, pr, nrec = self.eng.split_sides_to(buf, n, include_inverted, world, arrays, send, at_b, gidx, sides, at_r, base)
+            if pb != need_b[b] or pr != need_r[b]:
+                raise RuntimeError("split_sides: a batch changed between its count and its split (bytes / lines per destination differ)")
+            if world == 1 and pb[0]:
+                pieces.append((at_b[0], pb[0]))
+                piece_lines.append(pr[0])
+                if pb[0] % 16:
+                    send[at_b[0] + pb[0]: at_b[0] + pad(pb[0])] = 0
+            for d in range(world):
+                at_b[d] += pad(pb[d])
+                at_r[d] += pr[d]
+            base += nrec
+            if consume:
+                self.eng.sync()  # the copy kernel reads the batch
+                del buf
+                batches.pop(0)
+        self.pieces, self.piece_lines = (pieces, piece_lines) if world == 1 else (None, None)
+        return send[:total], dest_bytes, gidx[:total_r], sides[:total_r], dest_recs
+
+    def run_part(self, recv_buf, recv_gidx, recv_sides, pieces=None, opts=None, piece_lines=None):
+        """to_bed over the lines this rank owns (recv_buf / pieces as for tile(); recv_gidx / recv_sides: the global input number and
+        the side mask of every line, in the order of the pieces; piece_lines: the lines of every piece, as the split counted them and
+        the exchange passed them on -- only a piece that has to be cut into several batches, or pieces without counts, are counted
+        by their newlines). Returns (keys, None) -- int64 [sequences, 4] per block of BED lines,
+        in output order: 2 * global record of first appearance + side, bytes, lines, local entry -- or (None, failure) with the
+        failure as part_failure gives it (the record a global input number)."""
+        t = self.eng.torch
+        opts = {k: v for k, v in (opts or {}).items() if k in BED_OPTS}
+        holder = recv_buf if isinstance(recv_buf, list) else [recv_buf]
+        recv = holder[0].to(self.eng.device)
+        self.keep, lines_of = [], []
+        if recv.numel() and piece_lines is not None and pieces is not None and len(piece_lines) == len(pieces):
+            for piece, lines in zip(pieces, piece_lines):
+                cut = self._cut(recv, [piece])
+                self.keep += cut  # one batch: its lines are the piece's; several: every line ends with a newline (the splitter's)
+                lines_of += [int(lines)] if len(cut) == 1 else [int((buf[:n] == 10).sum().item()) for buf, n in cut]
+        elif recv.numel():
+            self.keep = self._cut(recv, pieces)
+            lines_of = [int((buf[:n] == 10).sum().item()) for buf, n in self.keep]
+        if isinstance(recv_buf, list):
+            recv_buf.clear()
+        self._recv = recv
+        del holder
+        gidx = recv_gidx.to(device=self.eng.device, dtype=t.int64).contiguous()
+        sides = recv_sides.to(device=self.eng.device, dtype=t.uint8).contiguous()
+        self.gidx, per_batch, at = gidx, [], 0
+        for lines in lines_of:
+            per_batch.append(sides[at: at + lines])
+            at += lines
+        if at != gidx.numel() or at != sides.numel():
+            raise RuntimeError(f"run_part: {gidx.numel()} record numbers and {sides.numel()} side masks for {at} lines")
+        self.info = self.eng.bed_part(self.keep, per_batch, **opts)
+        if self.info.error.code:
+            return None, part_failure(self.info, side=self.eng.bed_failure_side(), record=int(gidx[self.info.error.record].item()))
+        k3 = self.eng.bed_sequence_keys()
+        if not k3.shape[0]:
+            return t.zeros(0, 4, dtype=t.int64, device=self.eng.device), None
+        return t.stack([2 * gidx[k3[:, 0] >> 1] + (k3[:, 0] & 1), k3[:, 1], k3[:, 2], k3[:, 0]], dim=1), None
+
+    def scatter(self, src, src_off, dst_off, dst):
+        """Blocks to their places. A part whose sequences all have 0-byte blocks (every line excluded by -e / -f / -m) has keys and
+        no bytes: there is nothing to place, and an empty tensor has no address to hand to the library."""
+        if src.numel():
+            super().scatter(src, src_off, dst_off, dst)
+
+
+def to_bed_sharded(worker, dist, rank, world, batches, first_record, opts, comm_device="cpu", consume=False):
+    """`paffy to_bed` over an input spread over the ranks (this rank holds `batches`, whose first record is global record
+    first_record; opts: binary, exclude_unaligned, exclude_aligned, min_size, include_inverted); one rank runs the same code with
+    world = 1 and dist = None. Returns {"error": None, "offsets": byte offset of every local block of BED lines (one per sequence, in
+    local output order) in the one-process output, "total": bytes of the whole output, "keys": the [n, 4] block keys (column 1: the
+    block sizes)}; worker.emit() then gives the local blocks back to back. When any record of any rank fails: {"error": {"code",
+    "stage", "record", "aux"}, "total": 0, ...} -- the failure one process reports, the same on every rank -- and nothing is to be
+    written. The -q tail of the command is the caller's (see above)."""
+    import torch
+
+    dev = worker.eng.device
+    inv = bool((opts or {}).get("include_inverted"))
+    empty = {"offsets": torch.zeros(0, dtype=torch.int64, device=comm_device), "total": 0, "keys": torch.zeros(0, 4, dtype=torch.int64, device=dev)}
+    local, _ = worker.side_names(batches, inv)
+    weights = merge_name_weights(dist, local, comm_device)
+    owner_of = owner_table(weights, world)
+    try:
+        send, send_bytes, send_gidx, send_sides, send_records = worker.split_sides(batches, owner_of, world, first_record, inv, consume)
+    except Exception:
+        worker.eng.drop_index()  # no kept index outlives a failed partition
+        raise
+    recv, recv_gidx, pieces = exchange_lines(dist, send, send_bytes, send_gidx, send_records, comm_device, getattr(worker, "pieces", None))
+    recv_sides, recv_records = exchange_sides(dist, send_sides, send_records, comm_device)
+    del send
+    holder = [recv]
+    del recv
+    # a piece per source rank that sent bytes (several ranks), or per batch as the splitter laid them out (one rank)
+    piece_lines = [n for n in recv_records if n] if world > 1 else getattr(worker, "piece_lines", None)
+    keys, fail = worker.run_part(holder, recv_gidx, recv_sides, pieces, opts, piece_lines)
+    err = first_failure(dist, fail, comm_device)
+    if err:
+        return dict(empty, error=err, owner_of=owner_of)
+    all_keys, owner = gather_tile_keys(dist, keys, comm_device)
+    offsets, total = bed_block_offsets(all_keys, owner, rank)
+    return {"error": None, "offsets": offsets, "total": total, "keys": keys, "owner_of": owner_of}
+
+
+def to_bed_in_parts(workers, batches, opts, first_record=0, owner_of=None):
+    """to_bed_sharded without ranks: one process, one GpuBedWorker (one context) per part on the same GPU, taken in turn -- the
+    partition with the real side_names / split_sides, the block keys exchanged in device memory, every part's blocks scattered into
+    one buffer. owner_of ({name hash: part}): a deal of the caller's instead of owner_table's. Returns {"error": None, "out": uint8
+    tensor with the ordered output, ...} or {"error": {...}, "out": None}."""
+    import torch
+
+    k_parts, w0 = len(workers), workers[0]
+    inv = bool((opts or {}).get("include_inverted"))
+    local, _ = w0.side_names(batches, inv)
+    if owner_of is None:
+        owner_of = owner_table(local, k_parts)
+    try:
+        send, send_bytes, send_gidx, send_sides, send_records = w0.split_sides(batches, owner_of, k_parts, first_record, inv)
+    except Exception:
+        w0.eng.drop_index()
+        raise
+    keys, failures, at_b, at_r = [], [], 0, 0
+    for w, nb, nr in zip(workers, send_bytes, send_records):  # a part's lines stand back to back in the send buffer
+        k, fail = w.run_part(send, send_gidx[at_r: at_r + nr], send_sides[at_r: at_r + nr], [(at_b, nb)] if k_parts > 1 else w0.pieces, opts,
+                             [nr] if k_parts > 1 else w0.piece_lines)
+        keys.append(k)
+        failures.append(fail)
+        at_b, at_r = at_b + nb, at_r + nr
+    err = least_failure([f for f in failures if f])
+    if err:
+        return {"error": err, "out": None, "total": 0, "owner_of": owner_of, "sides": send_sides}
+    all_keys = torch.cat(keys)
+    owner = torch.cat([torch.full((k.shape[0],), p, dtype=torch.int64, device=k.device) for p, k in enumerate(keys)])
+    out = total = None
+    for p, (w, k) in enumerate(zip(workers, keys)):
+        offsets, total = bed_block_offsets(all_keys, owner, p)
+        if out is None:
+            out = torch.zeros(max(16, (total + 15) // 16 * 16), dtype=torch.uint8, device=all_keys.device)
+        if k.shape[0]:
+            src_off = torch.zeros(k.shape[0] + 1, dtype=torch.int64, device=k.device)
+            src_off[1:] = torch.cumsum(k[:, 1], 0)
+            w.scatter(w.emit(), src_off, offsets.contiguous(), out)
+    return {"error": None, "out": out[:total], "total": total, "keys": keys, "owner_of": owner_of, "sides": send_sides}
