@@ -563,7 +563,14 @@ int paffy_to_bed_main(int argc, char *argv[]) {
         return 1;
     }
     int rc;
-    if (b.exclude_aligned && query_fasta) {
+    if (b.exclude_aligned && query_fasta && getenv("PAFFY_BED_PART") && getenv("PAFFY_BED_FDS")) {
+        /* one of the launcher's workers: the names are flagged batch by batch while the text is on the device, nothing is kept here */
+        fasta_text f;
+        memset(&f, 0, sizeof(f));
+        host_set_bed_tail(fasta_text_add(&f, query_fasta) == 0 ? &f : NULL); /* a file that cannot be opened adds nothing */
+        rc = host_to_bed(in, out, &b);
+        fasta_text_free(&f);
+    } else if (b.exclude_aligned && query_fasta) {
         /* the names the alignments use are needed afterwards: keep the text */
         size_t cap = 1 << 20, have = 0;
         char *buf = (char *)malloc(cap);

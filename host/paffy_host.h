@@ -58,8 +58,15 @@ void host_set_stats_lines(FILE *fh);
 
 /* `paffy tile`: reads all of `in`, one tile_plan + emit, writes `out`. */
 int host_tile(FILE *in, FILE *out);
-/* `paffy to_bed`: reads all of `in`, one bed_plan + emit, writes `out` */
+/* `paffy to_bed`: reads all of `in`, one bed_plan + emit, writes `out`. Under the N-GPU launcher (PAFFY_BED_PART=<file prefix of the
+ * part>, PAFFY_BED_FDS=<from_launcher>,<to_launcher>) `in` is one part of an input partitioned by sequence: every line has its global
+ * number in <part>.idx and its side mask in <part>.sides, the block keys go to <part>.bkeys, and a failure is reported up the pipe and
+ * printed only when the launcher says that it is the one the whole run ends with (host/paffy_stream.c, host/paffy_launch.c). */
 int host_to_bed(FILE *in, FILE *out, const paffy_bed_opts *opts);
+/* to_bed -f -q in part mode, before host_to_bed: the names of every batch are looked up in the records of t while the batch is on the
+   device (<part>.seen), and the worker the launcher asks writes <part>.tail. t NULL: the file could not be opened, no records. t must
+   stay valid until host_to_bed returns. */
+void host_set_bed_tail(const fasta_text *t);
 /* `paffy chain`: reads all of `in`, chains on the GPU, writes the records with their cn / s1 tags by descending score. Under the N-GPU
  * launcher (PAFFY_CHAIN_PART=<file prefix of the part>, PAFFY_CHAIN_FDS=<from_launcher>,<to_launcher>: two inherited pipe descriptors)
  * `in` is one part of an input partitioned by query name: the records carry the global numbers of <part>.idx, the chain keys go to

@@ -30,13 +30,31 @@
  *     1: you are the failure -- say so and end as the reference would, 2: end silently). A worker that dies before it reports shows as
  *     end-of-file on its pipe: the run ends with that worker's status and nothing is written; a worker that reads end-of-file instead
  *     of a verdict exits. Nothing is written before both phases have passed everywhere (impl/paf_chain.c:128-132 writes last).
+ *   to_bed: the counters are per SEQUENCE (impl/paf.c:675-712) and with -n a record counts on its query sequence and on its target
+ *     sequence (impl/paf_to_bed.c:170-177), so the partition is by the names of both sides (shard.GpuBedWorker.split_sides, restated
+ *     here): a name's weight is the bytes of the lines that count on it, names go heaviest first to the lightest worker, a line goes to
+ *     owner(query name) with side mask 1 (3 when owner(target name) is the same worker) and, with -n and another target owner, a second
+ *     time to that owner with mask 2; a line with fewer than six columns has a query side only. Worker r gets <r>.in, <r>.idx (one int64
+ *     global line number per line) and <r>.sides (one mask byte per line). Three things are global and are settled here from a few int64
+ *     per sequence or per part:
+ *       the failure that ends the run -- a failing worker reports (global record, kind: 0 the line does not parse, 1 its query side,
+ *         2 its target side: to_bed reads, counts and checks record by record, the query side first); the least speaks, of two workers
+ *         that hold the same unparsable line the lower rank;
+ *       the order of the sequence blocks -- <rank>.bkeys: (2 * global record of first appearance + side, block bytes, lines) per
+ *         sequence, in the order of the worker's <rank>.out; all blocks are sorted by that key and copied from the mapped outputs;
+ *       the -q tail (only under -f) -- <rank>.seen: one byte per FASTA record, whether a line of the part names it; the union goes
+ *         to <lowest started rank>.seen_all and that one worker writes <rank>.tail, which is appended behind the last block.
+ *     A bed worker is told its part by PAFFY_BED_PART=<spooldir>/<rank> and talks over PAFFY_BED_FDS=<from_launcher>,<to_launcher>,
+ *     chain's protocol under names of its own: after the run it writes <part>.bkeys (and <part>.seen), reports {1, failed, record, kind,
+ *     0, sequences, 0, 0} and reads a verdict; on "go on" it writes its output. Under -f -q it then reads a second verdict: 2 ends it
+ *     well, 0 makes it write <part>.tail from <part>.seen_all, report {2, 0, ...} and read a last verdict. An empty input, which under
+ *     -f -q still lists every FASTA record, is left to one plain worker.
  * Everything between the workers goes through files under PAFFY_TMPDIR (default /dev/shm, else TMPDIR, else /tmp): host-mediated, no
- * GPU-to-GPU traffic -- a CLI's input comes from the host and its output goes back there. Other commands run on one GPU (to_bed has its
- * sharded form in the library and in paffy_amd/shard.py, to_bed_sharded, but not yet behind this launcher).
+ * GPU-to-GPU traffic -- a CLI's input comes from the host and its output goes back there. Other commands run on one GPU.
  *
  * Environment: PAFFY_GPUS=N; PAFFY_ONE_DEVICE=1 (rehearsal: every worker uses device 0); PAFFY_WORKER=path (another worker binary:
  * the CPU tests put a stand-in there); PAFFY_TMPDIR. Set for the workers: PAFFY_RANK, PAFFY_WORLD, PAFFY_DEVICE, PAFFY_RANGE (stream),
- * PAFFY_ROWS_FILE (tile), PAFFY_CHAIN_PART and PAFFY_CHAIN_FDS (chain).
+ * PAFFY_ROWS_FILE (tile), PAFFY_CHAIN_PART and PAFFY_CHAIN_FDS (chain), PAFFY_BED_PART and PAFFY_BED_FDS (to_bed).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -61,9 +79,10 @@
 static char g_worker[PATH_MAX];
 static char g_tmpdir[PATH_MAX];  /* where the private spool directory is made */
 static char g_spooldir[PATH_MAX]; /* mkdtemp(<tmpdir>/paffy.XXXXXX), mode 0700: nobody else can plant a link under a name we open */
-enum { SP_IN, SP_OUT, SP_ROWS, SP_IDX, SP_TAILS, SP_IDS, SP_LKEYS, SPOOL_KINDS };
-static const char *const k_spool_ext[SPOOL_KINDS] = {"in", "out", "rows", "idx", "tails", "ids", "lkeys"};
-static char g_spool[MAX_RANKS][SPOOL_KINDS][PATH_MAX]; /* per rank: input, output, rows (tile), index, and chain's tail keys, chain ids, line keys */
+enum { SP_IN, SP_OUT, SP_ROWS, SP_IDX, SP_TAILS, SP_IDS, SP_LKEYS, SP_SIDES, SP_BKEYS, SP_SEEN, SP_SEEN_ALL, SP_TAIL, SPOOL_KINDS };
+static const char *const k_spool_ext[SPOOL_KINDS] = {"in", "out", "rows", "idx", "tails", "ids", "lkeys", "sides", "bkeys", "seen", "seen_all", "tail"};
+/* per rank: input, output, rows (tile), index, chain's tail keys, chain ids, line keys, and to_bed's side masks, block keys, seen flags, their union, the -q tail */
+static char g_spool[MAX_RANKS][SPOOL_KINDS][PATH_MAX];
 static char g_stdin_spool[PATH_MAX];
 static int g_n = 0;
 static volatile pid_t g_pids[MAX_RANKS]; /* workers that are running (0: none) */
@@ -130,7 +149,7 @@ static int is_stream_cmd(const char *c) {
 /*
  * The command line of a sharded command, parsed the way the worker will parse it: getopt_long with the subcommand's own option string
  * and long options (impl/paf_invert.c:41-76, paf_trim.c:45-100, paf_add_mismatches.c:40-85, paf_filter.c:50-115,
- * paf_tile.c:100-150, paf_dechunk.c:55-66, paf_upconvert.c:84-91, paf_chain.c:62-73) -- clustered short flags (`trim -fi in.paf`), abbreviated long
+ * paf_tile.c:100-150, paf_dechunk.c:55-66, paf_upconvert.c:84-91, paf_chain.c:62-73, paf_to_bed.c:84-135) -- clustered short flags (`trim -fi in.paf`), abbreviated long
  * options (`--input x`), an option's value that looks like an option (`-l -i`) all mean here what they mean there. The worker's command line is rebuilt from the parse: every
  * option but -i / -o as the worker would have seen it, then the positional arguments, then our own -i / -o. Anything getopt_long
  * rejects, and -h, leaves the command to a single worker (which prints what the reference prints).
@@ -163,6 +182,11 @@ static const struct option k_dechunk[] = {{"logLevel", required_argument, 0, 'l'
 static const struct option k_upconvert[] = {{"logLevel", required_argument, 0, 'l'}, {"inFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
                                             {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
 
+static const struct option k_to_bed[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
+                                         {"binary", no_argument, 0, 'b'}, {"excludeUnaligned", no_argument, 0, 'e'}, {"excludeAligned", no_argument, 0, 'f'},
+                                         {"minSize", required_argument, 0, 'm'}, {"includeInverted", no_argument, 0, 'n'},
+                                         {"queryFastaFile", required_argument, 0, 'q'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+
 static const struct option k_chain[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
                                         {"maxGapLength", required_argument, 0, 'g'}, {"trimFraction", required_argument, 0, 't'}, {"chainGapOpen", required_argument, 0, 'd'},
                                         {"chainGapExtend", required_argument, 0, 'e'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
@@ -178,6 +202,7 @@ static void parse_cmdline(int argc, char **argv, CmdLine *cl) {
     else if (!strcmp(cmd, "dechunk")) { optstring = "l:i:o:hqt"; lopts = k_dechunk; }
     else if (!strcmp(cmd, "upconvert")) { optstring = "l:o:hi:"; lopts = k_upconvert; }
     else if (!strcmp(cmd, "chain")) { optstring = "l:i:o:hg:t:d:e:"; lopts = k_chain; }
+    else if (!strcmp(cmd, "to_bed")) { optstring = "l:i:o:hbefm:nq:"; lopts = k_to_bed; }
     /* getopt_long permutes the array it is given: a copy of argv[1..] (argv[1], the subcommand, stands where the program name would) */
     char **v = (char **)calloc((size_t)argc + 1, sizeof(char *));
     for (int i = 1; i < argc; i++) v[i - 1] = argv[i];
@@ -243,11 +268,13 @@ static char **worker_argv(const char *cmd, const CmdLine *cl, const char *in_pat
     return v;
 }
 
-/* chain: the part's file prefix and the two pipe ends of this worker (every pipe end is close-on-exec: a worker holds its own two only,
-   so the death of a worker is end-of-file on its pipe whatever the others do) */
+/* chain, to_bed: the part's file prefix and the two pipe ends of this worker (every pipe end is close-on-exec: a worker holds its own two
+   only, so the death of a worker is end-of-file on its pipe whatever the others do). bed: the variables are to_bed's, so that a chain
+   worker and a bed worker can never take each other's part */
 typedef struct {
     const char *part;
     int from_launcher, to_launcher;
+    int bed;
 } ChainLink;
 
 static pid_t spawn(char **wargv, int rank, int world, int one_device, const char *range, const char *rows_path, const ChainLink *link) {
@@ -265,15 +292,16 @@ static pid_t spawn(char **wargv, int rank, int world, int one_device, const char
     else unsetenv("PAFFY_RANGE");
     if (rows_path) setenv("PAFFY_ROWS_FILE", rows_path, 1);
     else unsetenv("PAFFY_ROWS_FILE");
+    unsetenv("PAFFY_CHAIN_PART");
+    unsetenv("PAFFY_CHAIN_FDS");
+    unsetenv("PAFFY_BED_PART");
+    unsetenv("PAFFY_BED_FDS");
     if (link) {
         snprintf(b, sizeof(b), "%d,%d", link->from_launcher, link->to_launcher);
-        setenv("PAFFY_CHAIN_PART", link->part, 1);
-        setenv("PAFFY_CHAIN_FDS", b, 1);
+        setenv(link->bed ? "PAFFY_BED_PART" : "PAFFY_CHAIN_PART", link->part, 1);
+        setenv(link->bed ? "PAFFY_BED_FDS" : "PAFFY_CHAIN_FDS", b, 1);
         fcntl(link->from_launcher, F_SETFD, 0);
         fcntl(link->to_launcher, F_SETFD, 0);
-    } else {
-        unsetenv("PAFFY_CHAIN_PART");
-        unsetenv("PAFFY_CHAIN_FDS");
     }
     execv(wargv[0], wargv);
     fprintf(stderr, "paffy: cannot start the worker %s: %s\n", wargv[0], strerror(errno));
@@ -482,26 +510,51 @@ static const void *map_file(const char *path, size_t *len) {
     return p == MAP_FAILED ? NULL : p;
 }
 
+/* the first column of the line [p, le) (le: behind its newline, nl: the newline or NULL) */
+static size_t query_name_len(const char *p, const char *le, const char *nl) {
+    const char *t = (const char *)memchr(p, '\t', (size_t)(le - p));
+    return t ? (size_t)(t - p) : (size_t)((nl ? nl : le) - p);
+}
+
+/* the sixth column (the target name) of the line [p, e), e its newline or its end: 0 when the line has fewer than six columns */
+static int target_name(const char *p, const char *e, const char **name, size_t *len) {
+    for (int tabs = 0; tabs < 5; tabs++) {
+        const char *t = (const char *)memchr(p, '\t', (size_t)(e - p));
+        if (!t) return 0;
+        p = t + 1;
+    }
+    const char *t = (const char *)memchr(p, '\t', (size_t)(e - p));
+    *name = p;
+    *len = (size_t)((t ? t : e) - p);
+    return 1;
+}
+
 /*
- * The partition by query name that tile and chain share: two passes over the input (bytes of every query name; heaviest name to the
+ * The partition by name that tile, chain and to_bed share: two passes over the input (bytes of every name's lines; heaviest name to the
  * lightest worker, contig_partition of paffy_amd/shard.py), every line to <rank>.in and its global line number to <rank>.idx.
- * spooled[r]: the lines worker r got. 0, or 1 after a message.
+ * sides = PART_BY_QUERY (tile, chain): the names are the query names. PART_QUERY_SIDE / PART_BOTH_SIDES (to_bed without / with -n,
+ * shard.GpuBedWorker.split_sides): with both sides a target name (column 6) gets the line's bytes too, the line goes to the owner of its
+ * query name and, when the owner of its target name is another worker, to that one as well; <rank>.sides gets one mask byte per
+ * spooled line (bit 0: count the query side here, bit 1: the target side). spooled[r]: the lines worker r got. 0, or 1 after a message.
  */
-static int partition_by_query(const char *cmd, int n, const char *in_path, int64_t *spooled) {
+enum { PART_BY_QUERY, PART_QUERY_SIDE, PART_BOTH_SIDES };
+
+static int partition_lines(const char *cmd, int n, const char *in_path, int64_t *spooled, int sides) {
     size_t in_len = 0;
     const char *in = (const char *)map_file(in_path, &in_len);
     if (!in) {
         fprintf(stderr, "paffy %s: cannot open %s\n", cmd, in_path);
         return 1;
     }
-    /* pass 1: the bytes of every query name's lines */
+    /* pass 1: the bytes of every name's lines */
     NameTab tab = {NULL, 0, 0};
     for (const char *p = in, *end = in + in_len; p < end;) {
         const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
         const char *le = nl ? nl + 1 : end;
-        const char *t = (const char *)memchr(p, '\t', (size_t)(le - p));
-        const size_t nlen = t ? (size_t)(t - p) : (size_t)((nl ? nl : le) - p);
-        tab_find(&tab, name_hash(p, nlen), 1)->weight += (int64_t)(le - p);
+        tab_find(&tab, name_hash(p, query_name_len(p, le, nl)), 1)->weight += (int64_t)(le - p);
+        const char *tn = NULL;
+        size_t tlen = 0;
+        if (sides == PART_BOTH_SIDES && target_name(p, nl ? nl : le, &tn, &tlen)) tab_find(&tab, name_hash(tn, tlen), 1)->weight += (int64_t)(le - p);
         p = le;
     }
     /* heaviest name to the lightest worker */
@@ -521,13 +574,14 @@ static int partition_by_query(const char *cmd, int n, const char *in_path, int64
         }
         free(order);
     }
-    /* pass 2: every line to its worker's spool, with its global line number */
-    FILE *fin[MAX_RANKS], *fidx[MAX_RANKS];
+    /* pass 2: every line to its worker's spool, with its global line number (and its side mask) */
+    FILE *fin[MAX_RANKS], *fidx[MAX_RANKS], *fsides[MAX_RANKS];
     for (int r = 0; r < n; r++) {
         for (int k = 0; k < SPOOL_KINDS; k++) snprintf(g_spool[r][k], PATH_MAX, "%s/%d.%s", g_spooldir, r, k_spool_ext[k]);
         fin[r] = fopen(g_spool[r][SP_IN], "wx"); /* O_EXCL: inside our own 0700 directory nothing can be there */
         fidx[r] = fopen(g_spool[r][SP_IDX], "wx");
-        if (!fin[r] || !fidx[r]) {
+        fsides[r] = sides == PART_BY_QUERY ? NULL : fopen(g_spool[r][SP_SIDES], "wx");
+        if (!fin[r] || !fidx[r] || (sides != PART_BY_QUERY && !fsides[r])) {
             fprintf(stderr, "paffy %s: cannot write under %s\n", cmd, g_tmpdir);
             return 1;
         }
@@ -538,17 +592,29 @@ static int partition_by_query(const char *cmd, int n, const char *in_path, int64
     for (const char *p = in, *end = in + in_len; p < end; line_no++) {
         const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
         const char *le = nl ? nl + 1 : end;
-        const char *t = (const char *)memchr(p, '\t', (size_t)(le - p));
-        const size_t nlen = t ? (size_t)(t - p) : (size_t)((nl ? nl : le) - p);
-        const int r = tab_find(&tab, name_hash(p, nlen), 0)->owner;
-        fwrite(p, 1, (size_t)(le - p), fin[r]);
-        if (!nl) fputc('\n', fin[r]); /* a last line without its newline is a record all the same (impl/paf.c:213) */
-        fwrite(&line_no, sizeof(line_no), 1, fidx[r]);
-        spooled[r]++;
+        int to[2], mask[2], copies = 1;
+        to[0] = tab_find(&tab, name_hash(p, query_name_len(p, le, nl)), 0)->owner;
+        mask[0] = 1;
+        const char *tn = NULL;
+        size_t tlen = 0;
+        if (sides == PART_BOTH_SIDES && target_name(p, nl ? nl : le, &tn, &tlen)) {
+            to[1] = tab_find(&tab, name_hash(tn, tlen), 0)->owner;
+            mask[1] = 2;
+            if (to[1] == to[0]) mask[0] = 3; /* one copy, both sides counted where it lies */
+            else copies = 2;
+        }
+        for (int c = 0; c < copies; c++) {
+            const int r = to[c];
+            fwrite(p, 1, (size_t)(le - p), fin[r]);
+            if (!nl) fputc('\n', fin[r]); /* a last line without its newline is a record all the same (impl/paf.c:213) */
+            fwrite(&line_no, sizeof(line_no), 1, fidx[r]);
+            if (fsides[r]) fputc(mask[c], fsides[r]);
+            spooled[r]++;
+        }
         p = le;
     }
     int werr = 0;
-    for (int r = 0; r < n; r++) werr |= fclose(fin[r]) | fclose(fidx[r]);
+    for (int r = 0; r < n; r++) werr |= fclose(fin[r]) | fclose(fidx[r]) | (fsides[r] ? fclose(fsides[r]) : 0);
     if (in_len) munmap((void *)in, in_len);
     free(tab.slot);
     if (werr) {
@@ -557,6 +623,8 @@ static int partition_by_query(const char *cmd, int n, const char *in_path, int64
     }
     return 0;
 }
+
+static int partition_by_query(const char *cmd, int n, const char *in_path, int64_t *spooled) { return partition_lines(cmd, n, in_path, spooled, PART_BY_QUERY); }
 
 static int run_tile(const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path) {
     int64_t spooled[MAX_RANKS]; /* lines routed to each worker */
@@ -691,7 +759,7 @@ static void send_verdict(ChainWorker *w, int64_t verdict) {
 }
 
 /*
- * One phase's reports from every running worker, in rank order (each of them either reports or ends: nothing here can wait for ever on a
+ * One phase's reports from every running worker (chain or to_bed), in rank order (each of them either reports or ends: nothing here can wait for ever on a
  * dead peer). Returns -1 when all go on; else the rank whose failure ends the run -- a worker that ended without a report (the first
  * by rank) before any reported failure, among those the least sort key -- after that worker has been told to speak, every other one to
  * end, and all of them have been reaped. *st: the wait status to end with.
@@ -845,6 +913,47 @@ static double seconds_now(void) {
     return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
 }
 
+/* one worker per part that has lines (a worker without a line is not started), each with its two pipes; bed: a to_bed part. Returns the
+   number of workers started, or -1 after a message, with those already started told to end and reaped */
+static int start_part_workers(const char *cmd, const CmdLine *cl, int n, int one_device, const int64_t *spooled, ChainWorker *w, int bed) {
+    memset(w, 0, sizeof(ChainWorker) * MAX_RANKS);
+    int started = 0;
+    for (int r = 0; r < n; r++) w[r].to_fd = w[r].from_fd = -1;
+    for (int r = 0; r < n; r++) {
+        if (spooled[r] == 0) continue;
+        int down[2], up[2];
+        char part[PATH_MAX];
+        snprintf(part, sizeof(part), "%s/%d", g_spooldir, r);
+        if (pipe2(down, O_CLOEXEC) != 0) down[0] = down[1] = -1;
+        if (down[0] < 0 || pipe2(up, O_CLOEXEC) != 0) up[0] = up[1] = -1;
+        pid_t pid = -1;
+        if (up[0] >= 0) {
+            const ChainLink link = {part, down[0], up[1], bed};
+            char **wv = worker_argv(cmd, cl, g_spool[r][SP_IN], g_spool[r][SP_OUT]);
+            pid = spawn(wv, r, n, one_device, NULL, NULL, &link);
+            free(wv);
+        }
+        if (down[0] >= 0) close(down[0]);
+        if (up[0] >= 0) close(up[1]);
+        if (pid < 0) {
+            fprintf(stderr, "paffy: cannot start worker %d: %s\n", r, strerror(errno));
+            if (down[0] >= 0) close(down[1]);
+            if (up[0] >= 0) close(up[0]);
+            for (int q = 0; q < r; q++) {
+                send_verdict(&w[q], V_END);
+                hang_up(&w[q]);
+                reap(&w[q], q);
+            }
+            return -1;
+        }
+        w[r].pid = g_pids[r] = pid;
+        w[r].to_fd = down[1];
+        w[r].from_fd = up[0];
+        started++;
+    }
+    return started;
+}
+
 static int run_chain(const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path) {
     int info = 0; /* -l INFO / DEBUG: our own steps' times go to stderr */
     for (int i = 0; i + 1 < cl->n_opts; i++)
@@ -863,41 +972,8 @@ static int run_chain(const CmdLine *cl, int n, int one_device, const char *in_pa
     }
     const double t_partition = seconds_now() - t0;
     ChainWorker w[MAX_RANKS];
-    memset(w, 0, sizeof(w));
-    int started = 0;
-    for (int r = 0; r < n; r++) w[r].to_fd = w[r].from_fd = -1;
-    for (int r = 0; r < n; r++) { /* workers without a line are not started */
-        if (spooled[r] == 0) continue;
-        int down[2], up[2];
-        char part[PATH_MAX];
-        snprintf(part, sizeof(part), "%s/%d", g_spooldir, r);
-        if (pipe2(down, O_CLOEXEC) != 0) down[0] = down[1] = -1;
-        if (down[0] < 0 || pipe2(up, O_CLOEXEC) != 0) up[0] = up[1] = -1;
-        pid_t pid = -1;
-        if (up[0] >= 0) {
-            const ChainLink link = {part, down[0], up[1]};
-            char **wv = worker_argv("chain", cl, g_spool[r][SP_IN], g_spool[r][SP_OUT]);
-            pid = spawn(wv, r, n, one_device, NULL, NULL, &link);
-            free(wv);
-        }
-        if (down[0] >= 0) close(down[0]);
-        if (up[0] >= 0) close(up[1]);
-        if (pid < 0) {
-            fprintf(stderr, "paffy: cannot start worker %d: %s\n", r, strerror(errno));
-            if (down[0] >= 0) close(down[1]);
-            if (up[0] >= 0) close(up[0]);
-            for (int q = 0; q < r; q++) {
-                send_verdict(&w[q], V_END);
-                hang_up(&w[q]);
-                reap(&w[q], q);
-            }
-            return 1;
-        }
-        w[r].pid = g_pids[r] = pid;
-        w[r].to_fd = down[1];
-        w[r].from_fd = up[0];
-        started++;
-    }
+    const int started = start_part_workers("chain", cl, n, one_device, spooled, w, 0);
+    if (started < 0) return 1;
     int st = 0;
     for (int64_t phase = 1; phase <= 2; phase++) {
         const int loser = chain_phase(w, n, phase, &st);
@@ -948,19 +1024,211 @@ static int run_chain(const CmdLine *cl, int n, int one_device, const char *in_pa
     return rc;
 }
 
+/* ---------------- to_bed ---------------- */
+
+/* whether the parsed command line has the flag -<key>; takes_value: the options of this command that are followed by their value */
+static int has_flag(const CmdLine *cl, char key, const char *takes_value) {
+    int found = 0;
+    for (int i = 0; i < cl->n_opts; i++) {
+        const char k = cl->opts[i][1];
+        if (k == key) found = 1;
+        if (strchr(takes_value, k)) i++;
+    }
+    return found;
+}
+
+static void end_all(ChainWorker *w, int n) {
+    for (int r = 0; r < n; r++) {
+        send_verdict(&w[r], V_END);
+        hang_up(&w[r]);
+        reap(&w[r], r);
+    }
+}
+
+/* the union of the started workers' <rank>.seen (one byte per FASTA record, the same count everywhere) -> <first>.seen_all */
+static int unite_seen(const ChainWorker *w, int n, int first) {
+    uint8_t *all = NULL;
+    size_t n_rec = 0;
+    int rc = 0;
+    for (int r = 0; r < n && !rc; r++) {
+        if (w[r].pid <= 0) continue;
+        size_t len = 0;
+        const uint8_t *seen = (const uint8_t *)map_file(g_spool[r][SP_SEEN], &len);
+        if (!seen || (all && len != n_rec)) {
+            fprintf(stderr, "paffy to_bed: worker %d left no sequence flags\n", r);
+            rc = 1;
+        } else {
+            if (!all) all = (uint8_t *)calloc((n_rec = len) + 1, 1);
+            for (size_t k = 0; k < len; k++) all[k] |= seen[k];
+        }
+        if (seen && len) munmap((void *)seen, len);
+    }
+    if (!rc) {
+        FILE *f = fopen(g_spool[first][SP_SEEN_ALL], "wx");
+        if (!f || fwrite(all, 1, n_rec, f) != n_rec || fclose(f) != 0) {
+            fprintf(stderr, "paffy to_bed: cannot write under %s\n", g_tmpdir);
+            rc = 1;
+        }
+    }
+    free(all);
+    return rc;
+}
+
+typedef struct {
+    int64_t key, bytes, from; /* 2 * global record of first appearance + side; the block's bytes; where they start in its worker's output */
+    int32_t part;
+} BedBlock;
+
+static int by_block_key(const void *a, const void *b) {
+    const BedBlock *x = (const BedBlock *)a, *y = (const BedBlock *)b;
+    if (x->key != y->key) return x->key < y->key ? -1 : 1;
+    return x->part < y->part ? -1 : (x->part > y->part ? 1 : 0);
+}
+
+/* the blocks of all workers in the order one process writes them: ascending key of first appearance (shard.bed_block_offsets). A worker's
+   blocks lie back to back in its output in the order of its keys; a block of no bytes is legal (-e on an uncovered sequence) */
+static int merge_bed_blocks(const ChainWorker *w, int n, FILE *out) {
+    int64_t total = 0;
+    for (int r = 0; r < n; r++) total += w[r].rep[5];
+    BedBlock *all = (BedBlock *)malloc(sizeof(BedBlock) * (size_t)(total + 1));
+    const char *text[MAX_RANKS];
+    memset(text, 0, sizeof(text));
+    int64_t m = 0;
+    int rc = !all;
+    for (int r = 0; r < n && !rc; r++) {
+        if (w[r].rep[5] <= 0) continue; /* no worker, or no sequence */
+        size_t out_len = 0, key_len = 0;
+        text[r] = (const char *)map_file(g_spool[r][SP_OUT], &out_len);
+        const int64_t *keys = (const int64_t *)map_file(g_spool[r][SP_BKEYS], &key_len);
+        int64_t bytes = 0;
+        int ok = text[r] && keys && key_len == (size_t)w[r].rep[5] * 24;
+        for (int64_t k = 0; ok && k < w[r].rep[5]; k++, m++) {
+            const int64_t len = keys[3 * k + 1];
+            if (len < 0 || len > (int64_t)out_len - bytes) ok = 0;
+            const BedBlock e = {keys[3 * k], len, bytes, r};
+            all[m] = e;
+            bytes += len;
+        }
+        if (!ok || bytes != (int64_t)out_len) {
+            fprintf(stderr, "paffy to_bed: the output of worker %d is not what its block keys say\n", r);
+            rc = 1;
+        }
+        if (keys && key_len) munmap((void *)keys, key_len);
+    }
+    if (!rc) {
+        qsort(all, (size_t)m, sizeof(BedBlock), by_block_key);
+        for (int64_t k = 0; k < m && !rc; k++)
+            if (all[k].bytes && fwrite(text[all[k].part] + all[k].from, 1, (size_t)all[k].bytes, out) != (size_t)all[k].bytes) rc = 1;
+    }
+    free(all);
+    return rc;
+}
+
+static int run_to_bed(const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path) {
+    int log_info = 0; /* -l INFO / DEBUG: our own steps' times go to stderr */
+    for (int i = 0; i < cl->n_opts; i++) {
+        const char k = cl->opts[i][1];
+        if (k == 'l' && i + 1 < cl->n_opts) log_info = !strcasecmp(cl->opts[i + 1], "INFO") || !strcasecmp(cl->opts[i + 1], "DEBUG");
+        if (strchr("lmq", k)) i++;
+    }
+    const int with_target = has_flag(cl, 'n', "lmq");
+    const int tail = has_flag(cl, 'f', "lmq") && has_flag(cl, 'q', "lmq"); /* impl/paf_to_bed.c:187-190: -q counts under -f only */
+    double t0 = seconds_now();
+    int64_t spooled[MAX_RANKS];
+    if (partition_lines("to_bed", n, in_path, spooled, with_target ? PART_BOTH_SIDES : PART_QUERY_SIDE) != 0) return 1;
+    /* where one worker opens it (impl/paf_to_bed.c:163): a run that fails leaves the same empty file */
+    FILE *out = out_path ? fopen(out_path, "w") : stdout;
+    if (!out) {
+        fprintf(stderr, "paffy to_bed: cannot open %s\n", out_path);
+        return 1;
+    }
+    const double t_partition = seconds_now() - t0;
+    ChainWorker w[MAX_RANKS];
+    const int started = start_part_workers("to_bed", cl, n, one_device, spooled, w, 1);
+    if (started < 0) return 1;
+    int first = -1; /* the lowest started rank: it writes the -q tail */
+    for (int r = n - 1; r >= 0; r--)
+        if (w[r].pid > 0) first = r;
+    int st = 0;
+    int loser = chain_phase(w, n, 1, &st);
+    if (loser < 0 && tail && unite_seen(w, n, first) != 0) {
+        end_all(w, n);
+        return 1;
+    }
+    if (loser < 0) {
+        for (int r = 0; r < n; r++) /* every worker writes its blocks; under -f -q the next verdict waits in its pipe until it has */
+            if (w[r].pid > 0) {
+                send_verdict(&w[r], V_GO_ON);
+                if (tail) send_verdict(&w[r], r == first ? V_GO_ON : V_END);
+            }
+        int any_bad = 0;
+        for (int r = 0; r < n; r++) {
+            if (w[r].pid <= 0) {
+                w[r].rep[5] = 0;
+                continue;
+            }
+            if (tail && r == first) continue;
+            hang_up(&w[r]);
+            reap(&w[r], r);
+            if (!any_bad && (WIFSIGNALED(w[r].st) || WEXITSTATUS(w[r].st) != 0)) {
+                any_bad = 1;
+                st = w[r].st;
+            }
+        }
+        if (any_bad) {
+            end_all(w, n);
+            return status_of(st);
+        }
+        if (tail) { /* the one worker that is left writes the tail and says so */
+            const int64_t sequences = w[first].rep[5];
+            loser = chain_phase(w, n, 2, &st);
+            if (loser < 0) {
+                w[first].rep[5] = sequences;
+                send_verdict(&w[first], V_GO_ON);
+                hang_up(&w[first]);
+                reap(&w[first], first);
+                if (WIFSIGNALED(w[first].st) || WEXITSTATUS(w[first].st) != 0) return status_of(w[first].st);
+            }
+        }
+    }
+    if (loser >= 0) { /* nothing is written; we end the way that worker ended */
+        if (!WIFSIGNALED(st) && WEXITSTATUS(st) == 0) {
+            fprintf(stderr, "paffy to_bed: worker %d ended without a result\n", loser);
+            return 1;
+        }
+        return status_of(st);
+    }
+    t0 = seconds_now();
+    setvbuf(out, NULL, _IOFBF, 1 << 22);
+    int rc = merge_bed_blocks(w, n, out);
+    if (!rc && tail) {
+        size_t len = 0;
+        const char *t = (const char *)map_file(g_spool[first][SP_TAIL], &len);
+        if (!t || (len && fwrite(t, 1, len, out) != len)) {
+            fprintf(stderr, "paffy to_bed: worker %d left no list of the sequences without alignments\n", first);
+            rc = 1;
+        }
+    }
+    rc |= fflush(out) != 0;
+    if (out != stdout) rc |= fclose(out) != 0;
+    if (log_info) fprintf(stderr, "paffy to_bed: %d workers; launcher: partition %.3f s, merge %.3f s\n", started, t_partition, seconds_now() - t0);
+    return rc;
+}
+
 int main(int argc, char **argv) {
     find_worker();
     const char *g = getenv("PAFFY_GPUS");
     int n = g ? atoi(g) : 1;
     if (n > MAX_RANKS) n = MAX_RANKS;
     const int is_chain = argc >= 2 && !strcmp(argv[1], "chain");
-    int shard = n > 1 && argc >= 2 && (is_stream_cmd(argv[1]) || !strcmp(argv[1], "tile") || is_chain);
+    const int is_bed = argc >= 2 && !strcmp(argv[1], "to_bed");
+    int shard = n > 1 && argc >= 2 && (is_stream_cmd(argv[1]) || !strcmp(argv[1], "tile") || is_chain || is_bed);
     CmdLine cl;
     memset(&cl, 0, sizeof(cl));
     if (shard) {
         parse_cmdline(argc, argv, &cl);
         shard = cl.ok; /* -h, or something getopt_long would reject: the one worker says what the reference says */
-        if (shard && is_chain && cl.in_path) { /* and so it does for an input that cannot be opened */
+        if (shard && (is_chain || is_bed) && cl.in_path) { /* and so it does for an input that cannot be opened */
             const int fd = open(cl.in_path, O_RDONLY);
             if (fd < 0) shard = 0;
             else close(fd);
@@ -1000,8 +1268,20 @@ int main(int argc, char **argv) {
         close(fd);
         in_path = g_stdin_spool;
     }
+    if (is_bed) { /* an input without a line: under -f -q one worker still lists every FASTA record, so it is that worker's (stdin is at its end) */
+        struct stat sb;
+        if (stat(in_path, &sb) == 0 && sb.st_size == 0) {
+            cleanup();
+            free(cl.copy);
+            argv[0] = g_worker;
+            execv(g_worker, argv);
+            fprintf(stderr, "paffy: cannot start %s: %s\n", g_worker, strerror(errno));
+            return 127;
+        }
+    }
     const int rc = !strcmp(argv[1], "tile") ? run_tile(&cl, n, one_device, in_path, out_path)
-                   : (is_chain ? run_chain(&cl, n, one_device, in_path, out_path) : run_stream(argv[1], &cl, n, one_device, in_path, out_path));
+                   : (is_chain ? run_chain(&cl, n, one_device, in_path, out_path)
+                               : (is_bed ? run_to_bed(&cl, n, one_device, in_path, out_path) : run_stream(argv[1], &cl, n, one_device, in_path, out_path)));
     free(cl.copy);
     return rc;
 }

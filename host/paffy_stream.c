@@ -709,26 +709,37 @@ static int chain_part_keys(paffy_hip_ctx *ctx, const chain_part *p, const char *
     return rc;
 }
 
-/* the report of a phase, then the launcher's verdict: returns on "go on", ends the process otherwise */
-static void chain_part_report(const chain_part *p, int64_t phase, const paffy_error *e, const int64_t key[3], int64_t count) {
-    const int64_t rep[8] = {phase, e->code != 0, key[0], key[1], key[2], count, 0, 0};
+/* a verdict from the launcher; end-of-file in its place ends the process */
+static int64_t part_verdict(int from_fd) {
     int64_t verdict = -1;
-    size_t at = 0;
-    while (at < sizeof(rep)) {
-        const ssize_t k = write(p->to_fd, (const char *)rep + at, sizeof(rep) - at);
-        if (k < 0 && errno == EINTR) continue;
-        if (k <= 0) exit(1); /* the launcher is gone */
-        at += (size_t)k;
-    }
-    for (at = 0; at < sizeof(verdict);) {
-        const ssize_t k = read(p->from_fd, (char *)&verdict + at, sizeof(verdict) - at);
+    for (size_t at = 0; at < sizeof(verdict);) {
+        const ssize_t k = read(from_fd, (char *)&verdict + at, sizeof(verdict) - at);
         if (k < 0 && errno == EINTR) continue;
         if (k <= 0) exit(1); /* end-of-file in place of a verdict */
         at += (size_t)k;
     }
+    return verdict;
+}
+
+/* a report of eight int64 up the pipe, then the launcher's verdict: returns on "go on", ends the process otherwise (chain and to_bed) */
+static void part_settle(int to_fd, int from_fd, const int64_t rep[8], const paffy_error *e) {
+    size_t at = 0;
+    while (at < 8 * sizeof(int64_t)) {
+        const ssize_t k = write(to_fd, (const char *)rep + at, 8 * sizeof(int64_t) - at);
+        if (k < 0 && errno == EINTR) continue;
+        if (k <= 0) exit(1); /* the launcher is gone */
+        at += (size_t)k;
+    }
+    const int64_t verdict = part_verdict(from_fd);
     if (verdict == 0 && !e->code) return;
     if (verdict == 1 && e->code) die_like_reference(e, 0);
     exit(verdict == 2 ? 0 : 1);
+}
+
+/* the report of a phase, then the launcher's verdict: returns on "go on", ends the process otherwise */
+static void chain_part_report(const chain_part *p, int64_t phase, const paffy_error *e, const int64_t key[3], int64_t count) {
+    const int64_t rep[8] = {phase, e->code != 0, key[0], key[1], key[2], count, 0, 0};
+    part_settle(p->to_fd, p->from_fd, rep, e);
 }
 
 /* paffy_hip_chain_run in two phases with the launcher between them; 0 with the lines planned, or the failing call's code */
@@ -778,6 +789,194 @@ static int chain_part_run(paffy_hip_ctx *ctx, const paffy_chain_opts *opts, chai
     return 0;
 }
 
+/*
+ * ---- `paffy to_bed` as one of N workers of the launcher (host/paffy_launch.c): the part mode ----
+ * PAFFY_BED_PART=<prefix> names the part's files -- <prefix>.idx (read: the global record number of every input line, one int64 each),
+ * <prefix>.sides (read: one side mask byte per input line, paffy_hip_bed_add_sides), <prefix>.bkeys (written: three int64 per sequence in
+ * output order: 2 * global record of first appearance + side, the bytes of its block of BED lines, its lines), and under -f -q <prefix>.seen
+ * (written: one byte per record of the FASTA file, whether a line of the part names it), <prefix>.seen_all (read by the one worker that
+ * is asked for the tail: the union over all parts) and <prefix>.tail (written by that worker: the "name 0 length\t0" lines) -- and
+ * PAFFY_BED_FDS=<from_launcher>,<to_launcher> two inherited pipe descriptors with chain's protocol: after the run eight int64
+ * {1, failed, global record, kind, 0, sequences, 0, 0} (kind: 0 the line does not parse, 1 its query side fails, 2 its target side,
+ * shard.part_failure) and one int64 back: 0 go on (write the blocks), 1 this worker's failure is the one the user sees, anything else or
+ * end-of-file: end silently. Under -f -q a second verdict follows once the blocks are written: 2 end well, 0 write the tail, report
+ * {2, 0, ...} and read a last verdict.
+ */
+typedef struct {
+    const char *prefix;
+    int from_fd, to_fd;
+    int64_t *idx;           /* the global record number of every line of the part */
+    int64_t n_lines, added; /* lines of the part; lines of the batches added so far */
+    FILE *sides;
+    int with_target;
+    /* -f -q: the FASTA records (indexed in a context of their own) and whether a line of the part names them */
+    int tail;
+    const fasta_text *fasta;
+    paffy_hip_ctx *fctx;
+    int64_t n_fasta;
+    uint8_t *seen, *seen_batch;
+} bed_part;
+
+static int g_bed_tail = 0;
+static const fasta_text *g_bed_fasta = NULL;
+void host_set_bed_tail(const fasta_text *t) {
+    g_bed_tail = 1;
+    g_bed_fasta = t;
+}
+
+static int bed_part_open(bed_part *p, const paffy_bed_opts *opts) { /* 1: part mode; 0: not under the launcher; -1 after a message */
+    const char *prefix = getenv("PAFFY_BED_PART"), *fds = getenv("PAFFY_BED_FDS");
+    if (!prefix || !*prefix || !fds) return 0;
+    char path[4096];
+    p->prefix = prefix;
+    p->with_target = opts->include_inverted != 0;
+    snprintf(path, sizeof(path), "%s.idx", prefix);
+    FILE *fi = fopen(path, "r");
+    snprintf(path, sizeof(path), "%s.sides", prefix);
+    p->sides = fopen(path, "r");
+    int ok = sscanf(fds, "%d,%d", &p->from_fd, &p->to_fd) == 2 && fi && p->sides && fseek(fi, 0, SEEK_END) == 0;
+    if (ok) {
+        p->n_lines = (int64_t)(ftell(fi) / (long)sizeof(int64_t));
+        rewind(fi);
+        p->idx = (int64_t *)malloc(sizeof(int64_t) * (size_t)(p->n_lines + 1));
+        ok = p->idx && fread(p->idx, sizeof(int64_t), (size_t)p->n_lines, fi) == (size_t)p->n_lines;
+    }
+    if (fi) fclose(fi);
+    if (!ok) {
+        fprintf(stderr, "paffy to_bed: cannot use the part %s (PAFFY_BED_FDS=%s)\n", prefix, fds);
+        return -1;
+    }
+    p->tail = g_bed_tail;
+    p->fasta = g_bed_fasta;
+    if (p->tail && p->fasta) { /* a file that cannot be opened adds nothing: no record, no flag */
+        void *d_text = NULL;
+        int rc = paffy_hip_create(&p->fctx, host_device()) != 0;
+        if (!rc) rc = fasta_text_to_device(p->fasta, &d_text);
+        if (!rc) rc = paffy_hip_fasta_index_headers(p->fctx, d_text, p->fasta->len, p->fasta->starts, p->fasta->n_files, &p->n_fasta);
+        if (d_text) paffy_hip_free(d_text); /* the index keeps the table and the headers on the host */
+        if (!rc) {
+            p->seen = (uint8_t *)calloc((size_t)p->n_fasta + 1, 1);
+            p->seen_batch = (uint8_t *)calloc((size_t)p->n_fasta + 1, 1);
+        }
+        if (rc || !p->seen || !p->seen_batch) {
+            fprintf(stderr, "paffy to_bed: could not index the FASTA file on the GPU: %s\n", p->fctx ? paffy_hip_last_error(p->fctx) : "no context");
+            return -1;
+        }
+    }
+    return 1;
+}
+
+/* a batch of the part: its lines' side masks go to the device with it; under -f -q the names it uses are flagged while it is there */
+static int bed_part_add(paffy_hip_ctx *ctx, bed_part *p, const void *d, const char *buf, size_t use) {
+    size_t lines = use > 0 && buf[use - 1] != '\n';
+    for (const char *q = buf, *e = buf + use; q < e && (q = (const char *)memchr(q, '\n', (size_t)(e - q))) != NULL; q++) lines++;
+    uint8_t *m = (uint8_t *)malloc(lines + 1);
+    void *d_m = NULL;
+    int rc = -1;
+    if (m && p->added + (int64_t)lines <= p->n_lines && fread(m, 1, lines, p->sides) == lines && paffy_hip_malloc(&d_m, (int64_t)lines + 64) == 0 &&
+        paffy_hip_memcpy_h2d(d_m, m, (int64_t)lines) == 0)
+        rc = paffy_hip_bed_add_sides(ctx, d, (int64_t)use, d_m);
+    if (d_m) paffy_hip_free(d_m); /* read before the call returned */
+    free(m);
+    p->added += (int64_t)lines;
+    if (!rc && p->fctx && p->n_fasta > 0) {
+        rc = paffy_hip_fasta_seen(p->fctx, d, (int64_t)use, p->with_target, p->seen_batch);
+        for (int64_t k = 0; !rc && k < p->n_fasta; k++) p->seen[k] |= p->seen_batch[k];
+    }
+    return rc;
+}
+
+static int bed_part_file(const bed_part *p, const char *ext, const void *data, size_t bytes) {
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.%s", p->prefix, ext);
+    FILE *f = fopen(path, "w");
+    int rc = !f || fwrite(data, 1, bytes, f) != bytes;
+    if (f && fclose(f) != 0) rc = 1;
+    if (rc) fprintf(stderr, "paffy to_bed: cannot write %s\n", path);
+    return rc;
+}
+
+/* paffy_hip_bed_run, then the launcher: 0 with the blocks planned and "go on" received, or the failing call's code */
+static int bed_part_run(paffy_hip_ctx *ctx, const paffy_bed_opts *opts, bed_part *p, paffy_plan_info *info) {
+    int rc = paffy_hip_bed_run(ctx, opts, info);
+    if (rc) return rc;
+    if (p->added != p->n_lines) {
+        fprintf(stderr, "paffy to_bed: %lld record numbers for %lld lines\n", (long long)p->n_lines, (long long)p->added);
+        return PAFFY_E_STATE;
+    }
+    int64_t rep[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+    if (info->error.code) { /* the failing line's global number, and which of its sides failed: what the launcher compares */
+        if (info->error.record < 0 || info->error.record >= p->n_lines) return PAFFY_E_STATE;
+        info->error.record = p->idx[info->error.record];
+        rep[1] = 1;
+        rep[2] = info->error.record;
+        rep[3] = paffy_hip_bed_failure_side(ctx) + 1;
+    } else {
+        const int64_t cap = paffy_hip_bed_sequences(ctx) > 0 ? paffy_hip_bed_sequences(ctx) : 1;
+        void *d_keys = NULL;
+        int64_t *keys = (int64_t *)malloc((size_t)cap * 24);
+        int64_t n_seq = PAFFY_E_HIP;
+        if (keys && paffy_hip_malloc(&d_keys, cap * 24 + 64) == 0) n_seq = paffy_hip_bed_sequence_keys(ctx, cap, d_keys);
+        if (n_seq > 0 && (paffy_hip_sync(ctx) != 0 || paffy_hip_memcpy_d2h(keys, d_keys, n_seq * 24) != 0)) n_seq = PAFFY_E_HIP;
+        for (int64_t s = 0; s < n_seq; s++) { /* the local entry of first appearance (2 * line + side) -> the global one */
+            const int64_t line = keys[3 * s] >> 1;
+            if (line < 0 || line >= p->n_lines) n_seq = PAFFY_E_STATE;
+            else keys[3 * s] = 2 * p->idx[line] + (keys[3 * s] & 1);
+        }
+        if (n_seq >= 0 && bed_part_file(p, "bkeys", keys, (size_t)n_seq * 24) != 0) n_seq = PAFFY_E_HIP;
+        if (n_seq >= 0 && p->tail && bed_part_file(p, "seen", p->seen ? p->seen : (const uint8_t *)"", (size_t)p->n_fasta) != 0) n_seq = PAFFY_E_HIP;
+        if (d_keys) paffy_hip_free(d_keys);
+        free(keys);
+        if (n_seq < 0) return (int)n_seq;
+        rep[5] = n_seq;
+    }
+    part_settle(p->to_fd, p->from_fd, rep, &info->error);
+    return 0;
+}
+
+/* under -f -q, once the blocks are written: the launcher either ends this worker or asks it for the tail -- the records of the FASTA
+   file that no line of ANY part names (<prefix>.seen_all), in file order: the loop of paffy_to_bed_main */
+static int bed_part_tail(bed_part *p) {
+    if (!p->tail) return 0;
+    if (part_verdict(p->from_fd) != 0) exit(0);
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.tail", p->prefix);
+    FILE *tf = fopen(path, "w");
+    int rc = !tf;
+    if (!rc && p->n_fasta > 0) {
+        paffy_fasta_record *recs = (paffy_fasta_record *)malloc(sizeof(paffy_fasta_record) * (size_t)p->n_fasta);
+        uint8_t *all = (uint8_t *)malloc((size_t)p->n_fasta);
+        snprintf(path, sizeof(path), "%s.seen_all", p->prefix);
+        FILE *sf = fopen(path, "r");
+        rc = !recs || !all || !sf || fread(all, 1, (size_t)p->n_fasta, sf) != (size_t)p->n_fasta || paffy_hip_fasta_records(p->fctx, 0, p->n_fasta, recs) != p->n_fasta;
+        for (int64_t k = 0; k < p->n_fasta && !rc; k++)
+            if (!all[k]) { /* the name is the header up to a NUL byte */
+                const char *h = p->fasta->data + recs[k].hdr_off;
+                fprintf(tf, "%.*s 0 %" PRIi64 "\t0\n", (int)strnlen(h, (size_t)recs[k].hdr_len), h, recs[k].seq_len);
+            }
+        if (sf) fclose(sf);
+        free(recs);
+        free(all);
+    }
+    if (tf && fclose(tf) != 0) rc = 1;
+    if (rc) {
+        fprintf(stderr, "paffy to_bed: cannot write the sequences without alignments of the part %s\n", p->prefix);
+        return 1;
+    }
+    const int64_t rep[8] = {2, 0, 0, 0, 0, 0, 0, 0};
+    const paffy_error none = {0};
+    part_settle(p->to_fd, p->from_fd, rep, &none);
+    return 0;
+}
+
+static void bed_part_close(bed_part *p) {
+    if (p->sides) fclose(p->sides);
+    if (p->fctx) paffy_hip_destroy(p->fctx);
+    free(p->idx);
+    free(p->seen);
+    free(p->seen_batch);
+}
+
 static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paffy_chain_opts *chain);
 int host_tile(FILE *in, FILE *out) { return whole_file(in, out, NULL, NULL); }
 /* paffy to_bed: every record counts before anything is written, like tile */
@@ -801,6 +1000,10 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
     memset(&part, 0, sizeof(part));
     const int in_part = chain ? chain_part_open(&part) : 0;
     if (in_part < 0) return 1;
+    bed_part bpart; /* to_bed under the N-GPU launcher */
+    memset(&bpart, 0, sizeof(bpart));
+    const int in_bed_part = bed ? bed_part_open(&bpart, bed) : 0;
+    if (in_bed_part < 0) return 1;
     const size_t cap = chunk_bytes();
     size_t buf_cap = cap + (1 << 20), have = 0;
     char *buf = (char *)malloc(buf_cap);
@@ -842,7 +1045,7 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
         }
         void *d = NULL;
         if (paffy_hip_malloc(&d, (int64_t)use + 64) != 0 || paffy_hip_memcpy_h2d(d, buf, (int64_t)use) != 0 ||
-            (bed ? paffy_hip_bed_add(ctx, d, (int64_t)use) : (chain ? (in_part ? chain_part_add(ctx, &part, d, buf, use) : paffy_hip_chain_add(ctx, d, (int64_t)use)) : paffy_hip_tile_add(ctx, d, (int64_t)use))) != 0) {
+            (bed ? (in_bed_part ? bed_part_add(ctx, &bpart, d, buf, use) : paffy_hip_bed_add(ctx, d, (int64_t)use)) : (chain ? (in_part ? chain_part_add(ctx, &part, d, buf, use) : paffy_hip_chain_add(ctx, d, (int64_t)use)) : paffy_hip_tile_add(ctx, d, (int64_t)use))) != 0) {
             fprintf(stderr, "paffy %s: GPU call failed: %s (the input must fit the GPU's memory)\n", what, paffy_hip_last_error(ctx));
             if (d) paffy_hip_free(d);
             rc = 1;
@@ -856,7 +1059,7 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
     free(buf);
     paffy_plan_info info;
     memset(&info, 0, sizeof(info));
-    if (!rc && (bed ? paffy_hip_bed_run(ctx, bed, &info) : (chain ? (in_part ? chain_part_run(ctx, chain, &part, &info) : paffy_hip_chain_run(ctx, chain, &info)) : paffy_hip_tile_run(ctx, &info))) != 0) {
+    if (!rc && (bed ? (in_bed_part ? bed_part_run(ctx, bed, &bpart, &info) : paffy_hip_bed_run(ctx, bed, &info)) : (chain ? (in_part ? chain_part_run(ctx, chain, &part, &info) : paffy_hip_chain_run(ctx, chain, &info)) : paffy_hip_tile_run(ctx, &info))) != 0) {
         fprintf(stderr, "paffy %s: GPU call failed: %s\n", what, paffy_hip_last_error(ctx));
         rc = 1;
     }
@@ -919,6 +1122,11 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
     for (size_t i = 0; i < n_batches; i++) paffy_hip_free(d_batches[i]);
     free(d_batches);
     if (part.idx) fclose(part.idx);
+    if (in_bed_part) {
+        fflush(out);
+        if (!rc) rc = bed_part_tail(&bpart);
+        bed_part_close(&bpart);
+    }
     paffy_hip_destroy(ctx);
     fflush(out);
     return rc;
