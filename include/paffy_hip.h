@@ -234,6 +234,52 @@ int paffy_hip_dedupe_reset(paffy_hip_ctx *ctx);
 #define PAFFY_DEDUPE_KEEP_ALL 2
 
 /*
+ * Dedupe in parts: `paffy dedupe [-a]` sharded by KEY OWNER. "First seen wins" is a decision per class of records -- a class
+ * is a key (the 128-bit hash of paffy_hip_dedupe_plan), with check_inverse a key and its swapped key, named by the smaller of the two --
+ * so it needs a class's records in one place, not the input. A part is a context that holds any share of the records, each with a global
+ * input number (rec_base + its index in the part's batch). Per ROUND (one batch per part) a part sends one 32-byte entry per record to
+ * the part that owns the record's class, the owner answers one byte per entry, and the text never leaves the part that read it. The
+ * concatenation of the parts' outputs in part order, round by round, is what one context writes for the same records in the order of
+ * their global numbers, when the parts' shares are consecutive stretches of it.
+ *   entry:       four 64-bit words -- class key hi, class key lo, global number (int64), flags: bit 0 the record's own key is its class
+ *                key (its orientation), bit 1 its coordinates fail paf_check (impl/paf.c:427-438).
+ *   owner:       a pure function of the class key and n_parts (shard.dedupe_owner mirrors it):
+ *                    x = hi ^ lo;  x ^= x >> 33;  x *= 0xff51afd7ed558ccd;  x ^= x >> 33;  x *= 0xc4ceb9fe1a85ec53;  x ^= x >> 33;
+ *                    owner = (x * n_parts) >> 64
+ *                (64-bit arithmetic, the last product 128 bits wide).
+ *   part_keys:   source side. Indexes and parses the batch as paffy_hip_dedupe_plan does and keeps that state for part_plan. Writes the
+ *                entries of the records that parsed to d_entries (device, 16-byte aligned, cap_entries entries), grouped by owner:
+ *                owner p's segment has part_counts[p] entries (host, n_parts values) and follows owner p - 1's; the order inside a segment
+ *                is not defined (the entry carries its number). A record that does not parse has no entry: it is a failure of this
+ *                part at its global number. *n_records = the batch's records. n_parts >= 1 as for paffy_hip_split_to. More entries than
+ *                cap_entries: PAFFY_E_CAPACITY, found before anything is written; the round is then not begun.
+ *   part_decide: owner side, once per round. n_entries entries of any parts, in any order, in device memory; d_verdicts gets one byte per
+ *                entry, in the same order: bit 0 the record is written -- it has the lowest global number of its class in this round and
+ *                the class is not in the owner's memory --, bit 1 the record fails: check_inverse, its own key was not found among the
+ *                records written before it, and flag bit 1. The memory holds the classes this context declared written since the last
+ *                paffy_hip_dedupe_reset, each with its head's orientation; "own key found" is: the class's written record (memory, or
+ *                this round's head when it is another record) has the record's orientation. A record that is its own swap has own key =
+ *                swapped key, as has every record of its class. The memory is separate from that of paffy_hip_dedupe_plan; reset clears
+ *                both. A context may be source and owner at once: part_decide does not touch the round's source state.
+ *   part_verdicts: source side. The verdict bytes of this part's entries in the order part_keys wrote them (the owners' answers, segment
+ *                by segment; device memory, n_entries = the sum of part_counts). *first_bad_global = the lowest global number of this
+ *                part that fails -- a record that did not parse or a verdict with bit 1 -- or -1.
+ *   part_plan:   source side. first_bad_global: the minimum over all parts (-1: none). Plans the lines of this part's records with verdict
+ *                bit 0 and a global number below first_bad_global, in input order, with the verbatim writer of paffy_hip_dedupe_plan;
+ *                paffy_hip_emit, _emit_lines and _plan_rows (records: indices into the part's batch) work as after a dedupe plan. The
+ *                part that holds the failing record reports it in info->error, error.record being the global number. With
+ *                first_bad_global >= 0 the run is over in every part: until paffy_hip_dedupe_reset all four calls return PAFFY_E_STATE.
+ * Order: part_keys, part_verdicts, part_plan per round; part_verdicts or part_plan out of turn: PAFFY_E_STATE. The round's state lies in
+ * the context's index buffers: any other plan, and any call that indexes another batch (query_names, the split calls), ends the round.
+ * With n_parts = 1 and one context the four calls write what paffy_hip_dedupe_plan writes.
+ */
+int paffy_hip_dedupe_part_keys(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len, int check_inverse, int64_t rec_base, int32_t n_parts, void *d_entries,
+                               int64_t cap_entries, int64_t *part_counts, int64_t *n_records);
+int paffy_hip_dedupe_part_decide(paffy_hip_ctx *ctx, const void *d_entries, int64_t n_entries, int check_inverse, void *d_verdicts);
+int paffy_hip_dedupe_part_verdicts(paffy_hip_ctx *ctx, const void *d_verdicts, int64_t n_entries, int64_t *first_bad_global);
+int paffy_hip_dedupe_part_plan(paffy_hip_ctx *ctx, int64_t first_bad_global, paffy_plan_info *info);
+
+/*
  * bed_plan: `paffy to_bed` (impl/paf_to_bed.c:33-55, 166-190) over the whole batch: per-base coverage counters of every query
  * sequence (with include_inverted also of every target sequence, as the inverted record would count), written as maximal runs
  * "name start end value\n"; binary / exclude_unaligned / exclude_aligned / min_size are the reference's -b -e -f -m. Sequences come

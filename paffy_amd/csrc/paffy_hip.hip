@@ -1072,6 +1072,12 @@ struct paffy_hip_ctx {
     paffy_filter filter = {-1, -1, -1.0, -1.0, -1, 0};
     DevBuf dedupe_keys;
     struct DedupeState *dedupe = nullptr; /* dedupe_host.h: keys of the records written so far (sorted, on the device) and scratch */
+    /* dedupe in parts (dedupe_parts_kernel.h): how far the round of this context's batch has come -- 0 none, 1 keys sent, 2 verdicts in; any
+       planner and anything that indexes another batch puts it back to 0 (the round's state lies in the index buffers) -- and whether a
+       round reported a failure since the last paffy_hip_dedupe_reset */
+    int dd_part_stage = 0;
+    bool dd_part_failed = false;
+    struct DedupeParts *dd_parts = nullptr; /* the round's entry map and verdicts; the owner's memory */
     DevBuf scan_part, emit_order, order_cnt, tile_keys, tile_order, tile_rank, tile_coff, tile_cbase, tile_cov, tile_level, tile_len, tile_items, tile_slots, tile_parts;
     bool keep_raw = false;    /* paffy_hip_keep_raw_sequences: seq_raw holds the bases as loaded (paf_pretty_print shows their case) */
     bool plan_seq_lookup = false; /* rec_qseq / rec_tseq belong to the current plan */
@@ -1295,6 +1301,7 @@ int paffy_hip_create(paffy_hip_ctx **out, int device) {
 static void stream_detach(struct paffy_hip_stream *s);
 static void cov_free(paffy_hip_ctx *c); /* coverage_host.h state */
 static void dedupe_free(paffy_hip_ctx *c); /* dedupe_host.h state */
+static void dedupe_parts_free(paffy_hip_ctx *c); /* dedupe_parts_kernel.h state */
 static void index_drop(paffy_hip_ctx *c, const void *d_in);
 static void index_drop_all(paffy_hip_ctx *c);
 static void chain_free(paffy_hip_ctx *c);
@@ -1325,6 +1332,7 @@ void paffy_hip_destroy(paffy_hip_ctx *c) {
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     dedupe_free(c);
+    dedupe_parts_free(c);
     (void)paffy_hip_stream_trim(c);
     delete c->bed_params;
     if (c->h_info) (void)hipHostFree(c->h_info);
@@ -1352,6 +1360,7 @@ static int fetch_info(paffy_hip_ctx *c) {
 static void plan_begin(paffy_hip_ctx *c, PlanKind kind, int64_t in_bytes, paffy_plan_info *info) {
     c->planned = false;
     c->plan_kind = kind;
+    c->dd_part_stage = 0;
     memset(info, 0, sizeof(*info));
     info->in_bytes = in_bytes;
     memset(&c->plan, 0, sizeof(c->plan));
@@ -1368,6 +1377,7 @@ static void plan_begin(paffy_hip_ctx *c, PlanKind kind, int64_t in_bytes, paffy_
 static void index_drop(paffy_hip_ctx *c, const void *d_in);
 static int index_and_parse(paffy_hip_ctx *c, const uint8_t *in, uint32_t len, uint32_t *n_lines_out, uint32_t lvl0_max = PAFFY_OPS_CAP, bool flat = false) {
     index_drop(c, in); /* a kept index of this buffer describes what it held before */
+    c->dd_part_stage = 0;
     const uint32_t n_tiles = (len + SEP_TILE - 1) / SEP_TILE;
     c->indexed_in = nullptr; /* the index buffers are about to describe another batch */
 
@@ -2313,6 +2323,7 @@ static int index_restore(paffy_hip_ctx *c, const void *d_in, int64_t in_len, uin
         paffy_hip_ctx::KeptIndex &k = c->kept_index[i];
         if (k.in != d_in || k.len != in_len) continue;
         const size_t mb = sizeof(RecMeta) * (size_t)k.n, sb = sizeof(uint32_t) * ((size_t)k.n_seps + 1), nb = sizeof(uint32_t) * ((size_t)k.n + 1);
+        c->dd_part_stage = 0;
         if (ensure(c, c->meta, mb) || ensure(c, c->sep_pos, sb) || ensure(c, c->nl_idx, nb)) return 1;
         if (hipMemcpyAsync(c->meta.p, k.meta.p, mb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
             hipMemcpyAsync(c->sep_pos.p, k.sep_pos.p, sb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
@@ -2804,9 +2815,47 @@ int paffy_hip_set_intervals(paffy_hip_ctx *c, const char *const *headers, const 
     return 0;
 }
 
+static void dedupe_parts_reset(paffy_hip_ctx *c); /* dedupe_parts_kernel.h */
 int paffy_hip_dedupe_reset(paffy_hip_ctx *c) {
     if (!c) return PAFFY_E_ARG;
     if (c->dedupe) c->dedupe->seen_n = 0;
+    dedupe_parts_reset(c);
+    return 0;
+}
+
+/* the tail of a dedupe plan: the nk records listed in tile_order (input order) become the plan's lines -- sizes, offsets, the table emit
+   reads. The verbatim writer of tile: header + the cigar text as it was read. Shared with the plan of a part (dedupe_parts_kernel.h). */
+static int dedupe_plan_lines(paffy_hip_ctx *c, const uint8_t *in, uint32_t nk, paffy_plan_info *info) {
+    int64_t total = 0;
+    if (nk > 0) {
+        int64_t *lens = static_cast<int64_t *>(c->tile_len.p);
+        LAUNCH(c, "k_line_size", k_line_size, dim3((nk + 1 + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, static_cast<const RecMeta *>(c->meta.p),
+               static_cast<const uint32_t *>(c->tile_order.p), static_cast<const int64_t *>(c->tile_level.p), (uint64_t)nk, reinterpret_cast<uint64_t *>(lens));
+        { /* offsets of the lines: exclusive scan of nk + 1 lengths (the last one zero, k_line_size), so that entry nk is the total */
+            if (ensure(c, c->out_off, sizeof(int64_t) * ((size_t)nk + 1))) return PAFFY_E_HIP;
+            DedupeState &D = *c->dedupe;
+            size_t bytes = 0;
+            RPCHK(c, rocprim::exclusive_scan(nullptr, bytes, lens, static_cast<int64_t *>(c->out_off.p), (int64_t)0, (size_t)nk + 1, rocprim::plus<int64_t>(), c->stream));
+            if (ensure(c, D.tmp, bytes + 16)) return PAFFY_E_HIP;
+            RPCHK(c, rocprim::exclusive_scan(D.tmp.p, bytes, lens, static_cast<int64_t *>(c->out_off.p), (int64_t)0, (size_t)nk + 1, rocprim::plus<int64_t>(), c->stream));
+        }
+        HIPCHK(c, hipMemcpyAsync(&total, static_cast<int64_t *>(c->out_off.p) + nk, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (ensure(c, c->one_batch, sizeof(void *))) return PAFFY_E_HIP;
+        HIPCHK(c, hipMemcpyAsync(c->one_batch.p, &in, sizeof(void *), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (c->profile) prof_collect(c);
+    c->plan.out_bytes = total;
+    c->plan.n_rows = nk;
+    c->line_batches = static_cast<const uint8_t *const *>(c->one_batch.p);
+    c->line_meta = static_cast<const RecMeta *>(c->meta.p);
+    c->line_names2 = nullptr;
+    c->line_order = static_cast<const uint32_t *>(c->tile_order.p);
+    c->line_level = static_cast<const int64_t *>(c->tile_level.p);
+    c->line_off = static_cast<const uint64_t *>(c->out_off.p);
+    c->line_n = total ? nk : 0;
+    *info = c->plan;
+    c->planned = true;
     return 0;
 }
 
@@ -2859,38 +2908,10 @@ int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, in
             c->plan.error.stage = 0;
         }
     }
-    int64_t total = 0;
-    if (nk > 0) {
-        int64_t *lens = static_cast<int64_t *>(c->tile_len.p);
-        LAUNCH(c, "k_line_size", k_line_size, dim3((nk + 1 + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, static_cast<const RecMeta *>(c->meta.p),
-               static_cast<const uint32_t *>(c->tile_order.p), static_cast<const int64_t *>(c->tile_level.p), (uint64_t)nk, reinterpret_cast<uint64_t *>(lens));
-        { /* offsets of the lines: exclusive scan of nk + 1 lengths (the last one zero, k_line_size), so that entry nk is the total */
-            if (ensure(c, c->out_off, sizeof(int64_t) * ((size_t)nk + 1))) return PAFFY_E_HIP;
-            DedupeState &D = *c->dedupe;
-            size_t bytes = 0;
-            RPCHK(c, rocprim::exclusive_scan(nullptr, bytes, lens, static_cast<int64_t *>(c->out_off.p), (int64_t)0, (size_t)nk + 1, rocprim::plus<int64_t>(), c->stream));
-            if (ensure(c, D.tmp, bytes + 16)) return PAFFY_E_HIP;
-            RPCHK(c, rocprim::exclusive_scan(D.tmp.p, bytes, lens, static_cast<int64_t *>(c->out_off.p), (int64_t)0, (size_t)nk + 1, rocprim::plus<int64_t>(), c->stream));
-        }
-        HIPCHK(c, hipMemcpyAsync(&total, static_cast<int64_t *>(c->out_off.p) + nk, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (ensure(c, c->one_batch, sizeof(void *))) return PAFFY_E_HIP;
-        HIPCHK(c, hipMemcpyAsync(c->one_batch.p, &in, sizeof(void *), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (c->profile) prof_collect(c);
-    c->plan.out_bytes = total;
-    c->plan.n_rows = nk;
-    c->line_batches = static_cast<const uint8_t *const *>(c->one_batch.p);
-    c->line_meta = static_cast<const RecMeta *>(c->meta.p);
-    c->line_names2 = nullptr;
-    c->line_order = static_cast<const uint32_t *>(c->tile_order.p);
-    c->line_level = static_cast<const int64_t *>(c->tile_level.p);
-    c->line_off = static_cast<const uint64_t *>(c->out_off.p);
-    c->line_n = total ? nk : 0;
-    *info = c->plan;
-    c->planned = true;
-    return 0;
+    return dedupe_plan_lines(c, in, nk, info);
 }
+
+#include "dedupe_parts_kernel.h"
 
 int64_t paffy_hip_plan_rows(paffy_hip_ctx *c, int64_t cap, uint32_t *record, int64_t *out_off) {
     if (!c || !record || !out_off) return PAFFY_E_ARG;

@@ -161,6 +161,10 @@ def lib():
         L.paffy_hip_sync.argtypes = [vp]
         L.paffy_hip_dedupe_plan.argtypes = [vp, vp, i64, C.c_int, C.POINTER(PlanInfo)]
         L.paffy_hip_dedupe_reset.argtypes = [vp]
+        L.paffy_hip_dedupe_part_keys.argtypes = [vp, vp, i64, C.c_int, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+        L.paffy_hip_dedupe_part_decide.argtypes = [vp, vp, i64, C.c_int, vp]
+        L.paffy_hip_dedupe_part_verdicts.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.paffy_hip_dedupe_part_plan.argtypes = [vp, i64, C.POINTER(PlanInfo)]
         L.paffy_hip_set_sequences.argtypes = [vp, i64, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(i64)]
         L.paffy_hip_set_filter.argtypes = [vp, C.POINTER(Filter)]
         L.paffy_hip_set_intervals.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(i64), i64]
@@ -566,6 +570,47 @@ class Engine:
             raise PafError(f"record {info.error.record}: {L.paffy_hip_error_string(info.error.code).decode()}", info,
                            L.paffy_hip_error_exit_status(info.error.code))
         return out, info
+
+    # ---- dedupe in parts: `paffy dedupe` sharded by key owner (include/paffy_hip.h; shard.dedupe_sharded drives these) ----
+    def dedupe_reset(self):
+        self._check(lib().paffy_hip_dedupe_reset(self._ctx), "paffy_hip_dedupe_reset")
+
+    def dedupe_part_keys(self, d_in, in_len, check_inverse, rec_base, n_parts, entries=None):
+        """The round's entries of a device batch, grouped by owner: (int64 device tensor [n, 4] -- class hi, class lo, global number,
+        flags --, entries per owner, records of the batch). entries: a tensor to write into (its rows are the capacity); by default one
+        row per line end of the batch, plus one. The batch must stay alive until the round's lines have been written."""
+        t = self.torch
+        if entries is None:
+            entries = t.empty((int((d_in[:in_len] == 10).sum().item()) + 1 if in_len else 1, 4), dtype=t.int64, device=self.device)
+        counts, n_rec = (C.c_int64 * n_parts)(), C.c_int64()
+        self._check(lib().paffy_hip_dedupe_part_keys(self._ctx, C.c_void_p(d_in.data_ptr()) if in_len else None, in_len, 1 if check_inverse else 0, rec_base, n_parts,
+                                                     C.c_void_p(entries.data_ptr()), entries.shape[0], counts, C.byref(n_rec)), "paffy_hip_dedupe_part_keys")
+        counts = list(counts)
+        return entries[: sum(counts)], counts, n_rec.value
+
+    def dedupe_part_decide(self, entries, check_inverse):
+        """Owner side: one verdict byte per entry (uint8 device tensor; bit 0 written, bit 1 fails), in the entries' order."""
+        t = self.torch
+        e = entries.to(device=self.device, dtype=t.int64).contiguous()
+        n = e.shape[0] if e.dim() == 2 else e.numel() // 4
+        v = t.zeros(max(16, n), dtype=t.uint8, device=self.device)
+        self._check(lib().paffy_hip_dedupe_part_decide(self._ctx, C.c_void_p(e.data_ptr()) if n else None, n, 1 if check_inverse else 0, C.c_void_p(v.data_ptr())),
+                    "paffy_hip_dedupe_part_decide")
+        return v[:n]
+
+    def dedupe_part_verdicts(self, verdicts):
+        """Source side: the verdict bytes of this part's entries, in the order dedupe_part_keys wrote them. Returns the lowest failing
+        global record of this part, or -1."""
+        v = verdicts.to(device=self.device, dtype=self.torch.uint8).contiguous()
+        bad = C.c_int64(-1)
+        self._check(lib().paffy_hip_dedupe_part_verdicts(self._ctx, C.c_void_p(v.data_ptr()) if v.numel() else None, v.numel(), C.byref(bad)), "paffy_hip_dedupe_part_verdicts")
+        return bad.value
+
+    def dedupe_part_plan(self, first_bad_global=-1):
+        """Source side: plans this part's lines in front of first_bad_global (-1: no failure anywhere). Returns the PlanInfo; emit follows."""
+        info = PlanInfo()
+        self._check(lib().paffy_hip_dedupe_part_plan(self._ctx, first_bad_global, C.byref(info)), "paffy_hip_dedupe_part_plan")
+        return info
 
     def emit(self, d_out):
         rc = lib().paffy_hip_emit(self._ctx, C.c_void_p(d_out.data_ptr()), d_out.numel())

@@ -1093,3 +1093,179 @@ def to_bed_in_parts(workers, batches, opts, first_record=0, owner_of=None):
             src_off[1:] = torch.cumsum(k[:, 1], 0)
             w.scatter(w.emit(), src_off, offsets.contiguous(), out)
     return {"error": None, "out": out[:total], "total": total, "keys": keys, "owner_of": owner_of, "sides": send_sides}
+
+
+# ---- dedupe across ranks -----------------------------------------------------------------------
+#
+# `paffy dedupe [-a]` writes the first record of every class -- a class is a key (names, strand, four coordinates; the device compares
+# 128-bit hashes of them), with -a a key and its swapped key -- and ends at the first record that fails (impl/paf_dedupe.c:117-143). The
+# decision needs a class's records in one place, not the input, so it is sharded by the OWNER of the class key: every rank holds a
+# consecutive share of the records and per round (one batch per rank)
+#   1. keys: one 32-byte entry per record (class key, global input number, flags), grouped by owner -- a pure function of the class key;
+#   2. the entries travel to their owners (_pairwise_exchange: 32 bytes per record);
+#   3. decide: the owner sorts what it got by (class, number), finds every class's first record and looks the class up in its memory of
+#      the classes written in earlier rounds: one verdict byte per entry (bit 0 written, bit 1 fails);
+#   4. the bytes travel back the way the entries came (the counts transposed: 1 byte per record);
+#   5. verdicts: every rank finds its lowest failing record, an all-reduce (min) finds the run's;
+#   6. plan / emit: every rank writes its records with bit 0 in front of that record, in input order.
+# The text never moves; the ordered output is the ranks' outputs in rank order, round by round (gather_batch_sizes, gather_to_writer).
+
+DEDUPE_ENTRY_BYTES, DEDUPE_VERDICT_BYTES = 32, 1
+
+
+def dedupe_owner(class_hi, class_lo, n_parts):
+    """The part that owns a class key: what dd_owner computes on the device (paffy_amd/csrc/dedupe_parts_kernel.h) -- the 64-bit
+    finalizer of hi ^ lo, mapped to [0, n_parts) by the high half of the 128-bit product."""
+    mask = (1 << 64) - 1
+    x = (class_hi ^ class_lo) & mask
+    x ^= x >> 33
+    x = (x * 0xff51afd7ed558ccd) & mask
+    x ^= x >> 33
+    x = (x * 0xc4ceb9fe1a85ec53) & mask
+    x ^= x >> 33
+    return (x * n_parts) >> 64
+
+
+class GpuDedupeWorker:
+    """The device side of a part in dedupe_sharded() / dedupe_in_parts(): one Engine (one context), source and owner at once."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.info = None
+
+    def reset(self):
+        self.eng.dedupe_reset()
+
+    def count_records(self, batch):
+        """lines of a device batch (uint8 tensor, bytes): a last line without a newline is a record"""
+        buf, n = batch
+        return 0 if n == 0 else int((buf[:n] == 10).sum().item()) + (0 if int(buf[n - 1].item()) == 10 else 1)
+
+    def keys(self, batch, check_inverse, rec_base, n_parts):
+        buf, n = batch
+        self.batch = batch  # the lines are written from it
+        return self.eng.dedupe_part_keys(buf, n, check_inverse, rec_base, n_parts)
+
+    def decide(self, entries, check_inverse):
+        return self.eng.dedupe_part_decide(entries, check_inverse)
+
+    def verdicts(self, v):
+        return self.eng.dedupe_part_verdicts(v)
+
+    def plan(self, first_bad_global):
+        self.info = self.eng.dedupe_part_plan(first_bad_global)
+        return self.info
+
+    def emit(self):
+        out = self.eng.alloc_out(self.info.out_bytes)
+        if self.info.out_bytes:
+            self.eng.emit(out)
+            self.eng.sync()
+        return out[: self.info.out_bytes]
+
+
+def _dedupe_failure(info):
+    e = info.error
+    return ((e.record, 0, 0), (e.code, e.stage, e.record, e.aux)) if e.code else None
+
+
+def dedupe_in_parts(workers, rounds, check_inverse, first_record=0):
+    """dedupe_sharded without ranks: one process, one worker (one context) per part on the same GPU, the parts taken in turn. rounds: a
+    list of rounds, each a list with one device batch (uint8 tensor, bytes) per part; the records count on from first_record, part by
+    part, round by round. Returns {"error": None or the failure one process reports ({"code", "stage", "record", "aux"}), "out": uint8
+    tensor -- the parts' outputs in part order, round by round: everything in front of the failing record --, "total": its bytes,
+    "records": records read, "exchanged": bytes that would have travelled between the parts}."""
+    import torch
+
+    k = len(workers)
+    for w in workers:
+        w.reset()
+    outs, base, error, exchanged = [], first_record, None, 0
+    for rnd in rounds:
+        if len(rnd) != k:
+            raise ValueError("a round has one batch per part")
+        sent = []
+        for w, batch in zip(workers, rnd):
+            entries, counts, n_rec = w.keys(batch, check_inverse, base, k)
+            sent.append((entries, [0] + [sum(counts[: p + 1]) for p in range(k)]))
+            base += n_rec
+        answers = [[None] * k for _ in range(k)]  # [source][owner]
+        for p, w in enumerate(workers):
+            segs = [e[at[p]: at[p + 1]] for e, at in sent]
+            v, a = w.decide(torch.cat(segs), check_inverse), 0
+            for s, seg in enumerate(segs):
+                answers[s][p] = v[a: a + seg.shape[0]]
+                a += seg.shape[0]
+                if s != p:
+                    exchanged += seg.shape[0] * (DEDUPE_ENTRY_BYTES + DEDUPE_VERDICT_BYTES)
+        bads = [w.verdicts(torch.cat(answers[s])) for s, w in enumerate(workers)]
+        first_bad = min([b for b in bads if b >= 0], default=-1)
+        failures = []
+        for w in workers:
+            failures.append(_dedupe_failure(w.plan(first_bad)))
+            outs.append(w.emit())
+        if first_bad >= 0:
+            error = least_failure([f for f in failures if f])
+            break
+    out = torch.cat(outs) if outs else torch.zeros(0, dtype=torch.uint8)
+    return {"error": error, "out": out, "total": int(out.numel()), "records": base - first_record, "exchanged": exchanged}
+
+
+def dedupe_sharded(worker, dist, rank, world, rounds, check_inverse, first_record=0, comm_device="cpu", write=None, writer=0):
+    """`paffy dedupe [-a]` over an input spread over the ranks: this rank holds `rounds`, one device batch (uint8 tensor, bytes) per round
+    -- every rank the same number of rounds, an empty batch where it has nothing --, and within a round the ranks' batches follow each
+    other in rank order. One rank runs the same code with world = 1 and dist = None. No text is exchanged: 33 bytes per record.
+    Returns {"error": None or the failure one process reports, the same on every rank, "total": bytes of the whole output (everything in
+    front of a failing record), "sizes": bytes per (round, rank), "local": {round * world + rank: uint8 tensor} this rank's outputs};
+    with `write` the outputs travel to rank `writer`, which calls write(index, tensor) in output order (gather_to_writer)."""
+    import torch
+
+    worker.reset()
+    dev = getattr(getattr(worker, "eng", None), "device", "cpu")
+    local, base, error, none = {}, first_record, None, (1 << 63) - 1
+    for r, batch in enumerate(rounds):
+        n_mine = worker.count_records(batch)
+        shares = torch.tensor([n_mine], dtype=torch.int64, device=comm_device)
+        if dist is not None:
+            everyone = torch.zeros(world, dtype=torch.int64, device=comm_device)
+            dist.all_gather_into_tensor(everyone, shares)
+            shares = everyone
+        shares = [int(x) for x in shares.tolist()]
+        entries, send_counts, n_rec = worker.keys(batch, check_inverse, base + sum(shares[:rank]), world)
+        if n_rec != n_mine:
+            raise RuntimeError(f"dedupe_sharded: {n_rec} records in a batch of {n_mine} lines")
+        base += sum(shares)
+        if world == 1:
+            back = worker.decide(entries, check_inverse)
+        else:
+            sent = torch.tensor(send_counts, dtype=torch.int64, device=comm_device)
+            got = torch.zeros_like(sent)
+            dist.all_to_all_single(got, sent)  # 8 bytes per peer
+            recv_counts = [int(x) for x in got.tolist()]
+            mine = torch.empty(4 * sum(recv_counts), dtype=torch.int64, device=comm_device)
+            _pairwise_exchange(dist, rank, world, _comm(entries.reshape(-1), comm_device), [4 * c for c in send_counts], mine, [4 * c for c in recv_counts], EXCHANGE_CHUNK // 8)
+            v = worker.decide(mine.reshape(-1, 4).to(dev), check_inverse)
+            back = torch.empty(sum(send_counts), dtype=torch.uint8, device=comm_device)
+            _pairwise_exchange(dist, rank, world, _comm(v, comm_device), recv_counts, back, send_counts, EXCHANGE_CHUNK)
+        bad = worker.verdicts(back.to(dev))
+        first = torch.tensor([bad if bad >= 0 else none], dtype=torch.int64, device=comm_device)
+        if dist is not None:
+            dist.all_reduce(first, op=dist.ReduceOp.MIN)
+        first_bad = int(first.item())
+        first_bad = -1 if first_bad == none else first_bad
+        info = worker.plan(first_bad)
+        local[r * world + rank] = worker.emit()
+        if first_bad >= 0:
+            error = first_failure(dist, _dedupe_failure(info), comm_device)
+            break
+    n_batches = len(rounds) * world
+    sizes = {b: int(t.numel()) for b, t in local.items()}
+    sizes = gather_batch_sizes(dist, sizes, n_batches, comm_device) if dist is not None else [sizes.get(b, 0) for b in range(n_batches)]
+    if write is not None:
+        if dist is None:
+            for b in sorted(local):
+                if sizes[b]:
+                    write(b, local[b])
+        else:
+            gather_to_writer(dist, rank, world, {b: _comm(t, comm_device) for b, t in local.items()}, sizes, write, comm_device, writer)
+    return {"error": error, "total": sum(sizes), "sizes": sizes, "local": local}
