@@ -192,6 +192,10 @@ int paffy_dedupe_main(int argc, char *argv[]) {
                 return key == 'h' ? 0 : 1;
         }
     }
+    if (host_dedupe_in_part()) { /* one of the N workers of the launcher: rounds of shares, decided by the owners of the keys */
+        host_set_log_level(o.log_level);
+        return host_dedupe_part(o.in_path, o.out_path, check_inverse);
+    }
     host_set_dedupe(check_inverse);
     return run_stream_cmd(&o, NULL, 0, "dedupe");
 }

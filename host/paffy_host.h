@@ -49,6 +49,14 @@ int host_stream(const paffy_stage *stages, int n_stages, FILE *in, FILE *out);
 void host_set_filter(const paffy_filter *f);
 /* paffy dedupe: host_stream runs paffy_hip_dedupe_plan per chunk on one context (which remembers the records written). */
 void host_set_dedupe(int check_inverse);
+/* paffy dedupe under the N-GPU launcher (PAFFY_DEDUPE_PART=<spooldir>/<rank>, PAFFY_DEDUPE_FDS=<from_launcher>,<to_launcher>, PAFFY_RANK,
+ * PAFFY_WORLD, PAFFY_DEDUPE_SHARE_BYTES): the worker reads share k * world + rank of the input in round k -- shares are cut at the first
+ * line end at or after a multiple of the share size --, exchanges entries and verdict bytes with the other workers through files next
+ * to <spooldir>/<rank> (paffy_hip_dedupe_part_keys / _decide / _verdicts / _plan), appends its lines to out_path and reports up the pipe
+ * after each of a round's four phases (host/paffy_stream.c, host/paffy_launch.c). A failure is printed only by the worker the launcher
+ * tells to, with the record number of the one-worker run. */
+int host_dedupe_in_part(void);
+int host_dedupe_part(const char *in_path, const char *out_path, int check_inverse);
 
 /* paffy view -s -t: host_stream adds up the PAFFY_STATS sums of the chunks instead of writing lines */
 void host_set_stats(int on);

@@ -49,12 +49,33 @@
  *     0, sequences, 0, 0} and reads a verdict; on "go on" it writes its output. Under -f -q it then reads a second verdict: 2 ends it
  *     well, 0 makes it write <part>.tail from <part>.seen_all, report {2, 0, ...} and read a last verdict. An empty input, which under
  *     -f -q still lists every FASTA record, is left to one plain worker.
+ *   dedupe: "first seen wins" is a decision per class of records (a key, with -a a key and its swapped key), so it is cut by the OWNER of
+ *     the class key (include/paffy_hip.h, "Dedupe in parts"), in rounds. The cut is not the stream commands': with worker r on the r-th
+ *     N-th of the file, a record of worker 0's second round stands earlier in the input than its twin in worker 1's first round, and the
+ *     twin would be written. With C the share size (PAFFY_CHUNK_MB), cut(j) = the first line end at or after j * C (cut(0) = 0, the last
+ *     cut the file's size), share j = [cut(j), cut(j + 1)), round k = shares kN .. kN + N - 1, and worker r takes share kN + r: a round's
+ *     shares are consecutive stretches of the input. Every worker reads the one input (-i, or the spooled stdin) itself and computes its
+ *     cuts; we pass the path, N and C and count the rounds from the file's size, as they do. A record's number is cut(j) + its index in
+ *     the share (unique, rising with the input order); the true number is needed for the message only and is summed here from the
+ *     workers' record counts. Every worker is started, whatever its shares hold: it owns keys. A dedupe worker is told
+ *     PAFFY_DEDUPE_PART=<spooldir>/<rank>, PAFFY_DEDUPE_FDS=<from_launcher>,<to_launcher> and PAFFY_DEDUPE_SHARE_BYTES=C and reports four
+ *     times per round, eight int64 {phase, 0, a, 0, 0, count, 0, 0}; the answer is one int64, the verdict in its two low bits, a number
+ *     above them:
+ *       1 keys      <rank>.ent (its entries grouped by owner) and <rank>.cnt (N int64) are written; count = the share's records
+ *       2 decide    it has decided the entries addressed to it (its stretch of every <s>.ent) and written <rank>.ver, a byte per entry
+ *       3 verdicts  a = its lowest failing number or -1; the answer's number is the minimum over the workers + 1 (0: none)
+ *       4 write     count = the bytes it appended to <rank>.out, a = 1 when it holds the failing record. The round's segments are copied
+ *                   to the output in rank order. After a failure the holder is told to speak, the number being the records in front of
+ *                   its share, every other worker to end, and the holder's status is ours: everything before the record is written.
+ *     A worker that dies shows as end-of-file on its pipe: the run ends with its status, and what earlier rounds wrote stays. An empty
+ *     input is left to one plain worker. PAFFY_DEDUPE_SHARE_BYTES in our own environment (at least 1) replaces C: a knob for rehearsals.
  * Everything between the workers goes through files under PAFFY_TMPDIR (default /dev/shm, else TMPDIR, else /tmp): host-mediated, no
  * GPU-to-GPU traffic -- a CLI's input comes from the host and its output goes back there. Other commands run on one GPU.
  *
  * Environment: PAFFY_GPUS=N; PAFFY_ONE_DEVICE=1 (rehearsal: every worker uses device 0); PAFFY_WORKER=path (another worker binary:
  * the CPU tests put a stand-in there); PAFFY_TMPDIR. Set for the workers: PAFFY_RANK, PAFFY_WORLD, PAFFY_DEVICE, PAFFY_RANGE (stream),
- * PAFFY_ROWS_FILE (tile), PAFFY_CHAIN_PART and PAFFY_CHAIN_FDS (chain), PAFFY_BED_PART and PAFFY_BED_FDS (to_bed).
+ * PAFFY_ROWS_FILE (tile), PAFFY_CHAIN_PART and PAFFY_CHAIN_FDS (chain), PAFFY_BED_PART and PAFFY_BED_FDS (to_bed), PAFFY_DEDUPE_PART,
+ * PAFFY_DEDUPE_FDS and PAFFY_DEDUPE_SHARE_BYTES (dedupe).
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -79,9 +100,10 @@
 static char g_worker[PATH_MAX];
 static char g_tmpdir[PATH_MAX];  /* where the private spool directory is made */
 static char g_spooldir[PATH_MAX]; /* mkdtemp(<tmpdir>/paffy.XXXXXX), mode 0700: nobody else can plant a link under a name we open */
-enum { SP_IN, SP_OUT, SP_ROWS, SP_IDX, SP_TAILS, SP_IDS, SP_LKEYS, SP_SIDES, SP_BKEYS, SP_SEEN, SP_SEEN_ALL, SP_TAIL, SPOOL_KINDS };
-static const char *const k_spool_ext[SPOOL_KINDS] = {"in", "out", "rows", "idx", "tails", "ids", "lkeys", "sides", "bkeys", "seen", "seen_all", "tail"};
-/* per rank: input, output, rows (tile), index, chain's tail keys, chain ids, line keys, and to_bed's side masks, block keys, seen flags, their union, the -q tail */
+enum { SP_IN, SP_OUT, SP_ROWS, SP_IDX, SP_TAILS, SP_IDS, SP_LKEYS, SP_SIDES, SP_BKEYS, SP_SEEN, SP_SEEN_ALL, SP_TAIL, SP_ENT, SP_CNT, SP_VER, SPOOL_KINDS };
+static const char *const k_spool_ext[SPOOL_KINDS] = {"in", "out", "rows", "idx", "tails", "ids", "lkeys", "sides", "bkeys", "seen", "seen_all", "tail", "ent", "cnt", "ver"};
+/* per rank: input, output, rows (tile), index, chain's tail keys, chain ids, line keys, to_bed's side masks, block keys, seen flags, their union, the -q tail,
+   and dedupe's entries, entry counts and verdict bytes */
 static char g_spool[MAX_RANKS][SPOOL_KINDS][PATH_MAX];
 static char g_stdin_spool[PATH_MAX];
 static int g_n = 0;
@@ -149,7 +171,8 @@ static int is_stream_cmd(const char *c) {
 /*
  * The command line of a sharded command, parsed the way the worker will parse it: getopt_long with the subcommand's own option string
  * and long options (impl/paf_invert.c:41-76, paf_trim.c:45-100, paf_add_mismatches.c:40-85, paf_filter.c:50-115,
- * paf_tile.c:100-150, paf_dechunk.c:55-66, paf_upconvert.c:84-91, paf_chain.c:62-73, paf_to_bed.c:84-135) -- clustered short flags (`trim -fi in.paf`), abbreviated long
+ * paf_tile.c:100-150, paf_dechunk.c:55-66, paf_upconvert.c:84-91, paf_chain.c:62-73, paf_to_bed.c:84-135, paf_dedupe.c:63-97; --checkInverse
+ * takes no value, as in host/paffy_cmds.c) -- clustered short flags (`trim -fi in.paf`), abbreviated long
  * options (`--input x`), an option's value that looks like an option (`-l -i`) all mean here what they mean there. The worker's command line is rebuilt from the parse: every
  * option but -i / -o as the worker would have seen it, then the positional arguments, then our own -i / -o. Anything getopt_long
  * rejects, and -h, leaves the command to a single worker (which prints what the reference prints).
@@ -187,6 +210,9 @@ static const struct option k_to_bed[] = {{"logLevel", required_argument, 0, 'l'}
                                          {"minSize", required_argument, 0, 'm'}, {"includeInverted", no_argument, 0, 'n'},
                                          {"queryFastaFile", required_argument, 0, 'q'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
 
+static const struct option k_dedupe[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
+                                         {"checkInverse", no_argument, 0, 'a'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+
 static const struct option k_chain[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
                                         {"maxGapLength", required_argument, 0, 'g'}, {"trimFraction", required_argument, 0, 't'}, {"chainGapOpen", required_argument, 0, 'd'},
                                         {"chainGapExtend", required_argument, 0, 'e'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
@@ -203,6 +229,7 @@ static void parse_cmdline(int argc, char **argv, CmdLine *cl) {
     else if (!strcmp(cmd, "upconvert")) { optstring = "l:o:hi:"; lopts = k_upconvert; }
     else if (!strcmp(cmd, "chain")) { optstring = "l:i:o:hg:t:d:e:"; lopts = k_chain; }
     else if (!strcmp(cmd, "to_bed")) { optstring = "l:i:o:hbefm:nq:"; lopts = k_to_bed; }
+    else if (!strcmp(cmd, "dedupe")) { optstring = "l:i:o:ha"; lopts = k_dedupe; }
     /* getopt_long permutes the array it is given: a copy of argv[1..] (argv[1], the subcommand, stands where the program name would) */
     char **v = (char **)calloc((size_t)argc + 1, sizeof(char *));
     for (int i = 1; i < argc; i++) v[i - 1] = argv[i];
@@ -268,13 +295,16 @@ static char **worker_argv(const char *cmd, const CmdLine *cl, const char *in_pat
     return v;
 }
 
-/* chain, to_bed: the part's file prefix and the two pipe ends of this worker (every pipe end is close-on-exec: a worker holds its own two
-   only, so the death of a worker is end-of-file on its pipe whatever the others do). bed: the variables are to_bed's, so that a chain
-   worker and a bed worker can never take each other's part */
+/* chain, to_bed, dedupe: the part's file prefix and the two pipe ends of this worker (every pipe end is close-on-exec: a worker holds its
+   own two only, so the death of a worker is end-of-file on its pipe whatever the others do). kind: every command has variables of its own,
+   so that a worker of one command can never take the part of another */
+enum { LINK_CHAIN, LINK_BED, LINK_DEDUPE };
+static const char *const k_link_part[] = {"PAFFY_CHAIN_PART", "PAFFY_BED_PART", "PAFFY_DEDUPE_PART"};
+static const char *const k_link_fds[] = {"PAFFY_CHAIN_FDS", "PAFFY_BED_FDS", "PAFFY_DEDUPE_FDS"};
 typedef struct {
     const char *part;
     int from_launcher, to_launcher;
-    int bed;
+    int kind;
 } ChainLink;
 
 static pid_t spawn(char **wargv, int rank, int world, int one_device, const char *range, const char *rows_path, const ChainLink *link) {
@@ -292,14 +322,14 @@ static pid_t spawn(char **wargv, int rank, int world, int one_device, const char
     else unsetenv("PAFFY_RANGE");
     if (rows_path) setenv("PAFFY_ROWS_FILE", rows_path, 1);
     else unsetenv("PAFFY_ROWS_FILE");
-    unsetenv("PAFFY_CHAIN_PART");
-    unsetenv("PAFFY_CHAIN_FDS");
-    unsetenv("PAFFY_BED_PART");
-    unsetenv("PAFFY_BED_FDS");
+    for (int k = LINK_CHAIN; k <= LINK_DEDUPE; k++) {
+        unsetenv(k_link_part[k]);
+        unsetenv(k_link_fds[k]);
+    }
     if (link) {
         snprintf(b, sizeof(b), "%d,%d", link->from_launcher, link->to_launcher);
-        setenv(link->bed ? "PAFFY_BED_PART" : "PAFFY_CHAIN_PART", link->part, 1);
-        setenv(link->bed ? "PAFFY_BED_FDS" : "PAFFY_CHAIN_FDS", b, 1);
+        setenv(k_link_part[link->kind], link->part, 1);
+        setenv(k_link_fds[link->kind], b, 1);
         fcntl(link->from_launcher, F_SETFD, 0);
         fcntl(link->to_launcher, F_SETFD, 0);
     }
@@ -759,7 +789,7 @@ static void send_verdict(ChainWorker *w, int64_t verdict) {
 }
 
 /*
- * One phase's reports from every running worker (chain or to_bed), in rank order (each of them either reports or ends: nothing here can wait for ever on a
+ * One phase's reports from every running worker (chain, to_bed or dedupe), in rank order (each of them either reports or ends: nothing here can wait for ever on a
  * dead peer). Returns -1 when all go on; else the rank whose failure ends the run -- a worker that ended without a report (the first
  * by rank) before any reported failure, among those the least sort key -- after that worker has been told to speak, every other one to
  * end, and all of them have been reaped. *st: the wait status to end with.
@@ -913,9 +943,10 @@ static double seconds_now(void) {
     return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
 }
 
-/* one worker per part that has lines (a worker without a line is not started), each with its two pipes; bed: a to_bed part. Returns the
-   number of workers started, or -1 after a message, with those already started told to end and reaped */
-static int start_part_workers(const char *cmd, const CmdLine *cl, int n, int one_device, const int64_t *spooled, ChainWorker *w, int bed) {
+/* one worker per part that has lines (a worker without a line is not started), each with its two pipes; kind: LINK_CHAIN, LINK_BED or
+   LINK_DEDUPE; in_path: the input every worker reads (dedupe), or NULL: worker r reads its own <r>.in. Returns the number of workers
+   started, or -1 after a message, with those already started told to end and reaped */
+static int start_part_workers(const char *cmd, const CmdLine *cl, int n, int one_device, const int64_t *spooled, ChainWorker *w, int kind, const char *in_path) {
     memset(w, 0, sizeof(ChainWorker) * MAX_RANKS);
     int started = 0;
     for (int r = 0; r < n; r++) w[r].to_fd = w[r].from_fd = -1;
@@ -928,8 +959,8 @@ static int start_part_workers(const char *cmd, const CmdLine *cl, int n, int one
         if (down[0] < 0 || pipe2(up, O_CLOEXEC) != 0) up[0] = up[1] = -1;
         pid_t pid = -1;
         if (up[0] >= 0) {
-            const ChainLink link = {part, down[0], up[1], bed};
-            char **wv = worker_argv(cmd, cl, g_spool[r][SP_IN], g_spool[r][SP_OUT]);
+            const ChainLink link = {part, down[0], up[1], kind};
+            char **wv = worker_argv(cmd, cl, in_path ? in_path : g_spool[r][SP_IN], g_spool[r][SP_OUT]);
             pid = spawn(wv, r, n, one_device, NULL, NULL, &link);
             free(wv);
         }
@@ -972,7 +1003,7 @@ static int run_chain(const CmdLine *cl, int n, int one_device, const char *in_pa
     }
     const double t_partition = seconds_now() - t0;
     ChainWorker w[MAX_RANKS];
-    const int started = start_part_workers("chain", cl, n, one_device, spooled, w, 0);
+    const int started = start_part_workers("chain", cl, n, one_device, spooled, w, LINK_CHAIN, NULL);
     if (started < 0) return 1;
     int st = 0;
     for (int64_t phase = 1; phase <= 2; phase++) {
@@ -1144,7 +1175,7 @@ static int run_to_bed(const CmdLine *cl, int n, int one_device, const char *in_p
     }
     const double t_partition = seconds_now() - t0;
     ChainWorker w[MAX_RANKS];
-    const int started = start_part_workers("to_bed", cl, n, one_device, spooled, w, 1);
+    const int started = start_part_workers("to_bed", cl, n, one_device, spooled, w, LINK_BED, NULL);
     if (started < 0) return 1;
     int first = -1; /* the lowest started rank: it writes the -q tail */
     for (int r = n - 1; r >= 0; r--)
@@ -1215,6 +1246,157 @@ static int run_to_bed(const CmdLine *cl, int n, int one_device, const char *in_p
     return rc;
 }
 
+/* ---------------- dedupe ---------------- */
+
+/* the share size C: PAFFY_DEDUPE_SHARE_BYTES (the rehearsal knob, at least 1), else PAFFY_CHUNK_MB as the worker's chunk_bytes() reads it */
+static int64_t dedupe_share_bytes(void) {
+    const char *e = getenv("PAFFY_DEDUPE_SHARE_BYTES");
+    if (e && *e) {
+        const long long v = atoll(e);
+        return v < 1 ? 1 : (int64_t)v;
+    }
+    e = getenv("PAFFY_CHUNK_MB");
+    long mb = e ? atol(e) : 256;
+    if (mb < 1) mb = 1;
+    if (mb > 1900) mb = 1900;
+    return (int64_t)mb << 20;
+}
+
+/* `n` bytes of `from`, from byte `at` on, to `to` */
+static int copy_range(int from, int64_t at, int64_t n, int to) {
+    static char buf[1 << 22];
+    while (n > 0) {
+        const ssize_t got = pread(from, buf, n < (int64_t)sizeof(buf) ? (size_t)n : sizeof(buf), (off_t)at);
+        if (got < 0 && errno == EINTR) continue;
+        if (got <= 0) return -1;
+        for (ssize_t o = 0; o < got;) {
+            const ssize_t k = write(to, buf + o, (size_t)(got - o));
+            if (k < 0 && errno == EINTR) continue;
+            if (k < 0) return -1;
+            o += k;
+        }
+        at += got;
+        n -= got;
+    }
+    return 0;
+}
+
+/* A verdict to a dedupe worker: the code in the two low bits, a number above them */
+static int64_t dedupe_verdict(int64_t code, int64_t number) { return (int64_t)(((uint64_t)number << 2) | (uint64_t)code); }
+
+static int run_dedupe(const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path) {
+    struct stat sb;
+    if (stat(in_path, &sb) != 0) {
+        fprintf(stderr, "paffy dedupe: cannot open %s\n", in_path);
+        return 1;
+    }
+    int info = 0; /* -l INFO / DEBUG: our own steps' times go to stderr */
+    for (int i = 0; i + 1 < cl->n_opts; i++)
+        if (!strcmp(cl->opts[i], "-l")) {
+            info = !strcasecmp(cl->opts[i + 1], "INFO") || !strcasecmp(cl->opts[i + 1], "DEBUG");
+            i++;
+        }
+    const double t_start = seconds_now();
+    double t_copy = 0.0;
+    const int64_t size = (int64_t)sb.st_size, share = dedupe_share_bytes();
+    const int64_t shares = size / share + (size % share != 0), rounds = (shares + n - 1) / n;
+    {
+        char b[32];
+        snprintf(b, sizeof(b), "%lld", (long long)share);
+        setenv("PAFFY_DEDUPE_SHARE_BYTES", b, 1); /* every worker cuts with the share size we count the rounds with */
+    }
+    /* where one worker opens it (host/paffy_cmds.c, run_stream_cmd): after the input, before the first record */
+    const int out_fd = out_path ? open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666) : 1;
+    if (out_fd < 0) {
+        fprintf(stderr, "paffy dedupe: cannot open %s\n", out_path);
+        return 1;
+    }
+    int64_t spooled[MAX_RANKS];
+    for (int r = 0; r < n; r++) { /* every worker is an owner in every round, whatever its shares hold */
+        for (int k = 0; k < SPOOL_KINDS; k++) snprintf(g_spool[r][k], PATH_MAX, "%s/%d.%s", g_spooldir, r, k_spool_ext[k]);
+        spooled[r] = 1;
+    }
+    ChainWorker w[MAX_RANKS];
+    if (start_part_workers("dedupe", cl, n, one_device, spooled, w, LINK_DEDUPE, in_path) < 0) return 1;
+    int src[MAX_RANKS], st = 0, dead = -1;
+    int64_t at[MAX_RANKS], before[MAX_RANKS], records = 0;
+    for (int r = 0; r < n; r++) {
+        src[r] = -1;
+        at[r] = 0;
+    }
+    for (int64_t round = 0; round < rounds; round++) {
+        int64_t first_bad = -1;
+        for (int64_t phase = 1; phase <= 4; phase++) {
+            if ((dead = chain_phase(w, n, phase, &st)) >= 0) break; /* a worker is gone: what earlier rounds wrote stays */
+            int64_t number = 0;
+            if (phase == 1)
+                for (int r = 0; r < n; r++) { /* the true record number of a share's first record: for the message only */
+                    before[r] = records;
+                    records += w[r].rep[5] > 0 ? w[r].rep[5] : 0;
+                }
+            if (phase == 3) { /* the run's first failing record, as its pseudo number: cut + index, which rises with the input order */
+                for (int r = 0; r < n; r++)
+                    if (w[r].rep[2] >= 0 && (first_bad < 0 || w[r].rep[2] < first_bad)) first_bad = w[r].rep[2];
+                number = first_bad + 1;
+            }
+            if (phase == 4) { /* the round's output: the workers' new bytes in rank order */
+                int bad = 0;
+                const double t0 = seconds_now();
+                for (int r = 0; r < n && !bad; r++) {
+                    if (w[r].rep[5] <= 0) continue;
+                    if (src[r] < 0) src[r] = open(g_spool[r][SP_OUT], O_RDONLY | O_NOFOLLOW);
+                    if (src[r] < 0 || copy_range(src[r], at[r], w[r].rep[5], out_fd) != 0) bad = 1;
+                    at[r] += w[r].rep[5];
+                }
+                t_copy += seconds_now() - t0;
+                int holder = -1;
+                for (int r = n - 1; r >= 0; r--)
+                    if (w[r].rep[2]) holder = r;
+                if (bad || (first_bad >= 0 && holder < 0)) {
+                    fprintf(stderr, bad ? "paffy dedupe: cannot copy the output of a worker\n" : "paffy dedupe: no worker holds the failing record\n");
+                    end_all(w, n);
+                    return 1;
+                }
+                if (first_bad >= 0) { /* the worker that holds the record speaks, with the records in front of its share; the run ends here */
+                    for (int r = 0; r < n; r++) send_verdict(&w[r], r == holder ? dedupe_verdict(V_YOU_FAILED, before[holder]) : dedupe_verdict(V_END, 0));
+                    for (int r = 0; r < n; r++) {
+                        hang_up(&w[r]);
+                        reap(&w[r], r);
+                    }
+                    if (!WIFSIGNALED(w[holder].st) && WEXITSTATUS(w[holder].st) == 0) {
+                        fprintf(stderr, "paffy dedupe: worker %d ended without a result\n", holder);
+                        return 1;
+                    }
+                    return status_of(w[holder].st);
+                }
+            }
+            for (int r = 0; r < n; r++) send_verdict(&w[r], dedupe_verdict(V_GO_ON, number));
+        }
+        if (dead >= 0) break;
+    }
+    if (dead >= 0) {
+        if (!WIFSIGNALED(st) && WEXITSTATUS(st) == 0) {
+            fprintf(stderr, "paffy dedupe: worker %d ended without a result\n", dead);
+            return 1;
+        }
+        return status_of(st);
+    }
+    int any_bad = 0;
+    for (int r = 0; r < n; r++) {
+        hang_up(&w[r]);
+        reap(&w[r], r);
+        if (!any_bad && (WIFSIGNALED(w[r].st) || WEXITSTATUS(w[r].st) != 0)) {
+            any_bad = 1;
+            st = w[r].st;
+        }
+        if (src[r] >= 0) close(src[r]);
+    }
+    if (out_fd != 1 && close(out_fd) != 0) return 1;
+    if (info)
+        fprintf(stderr, "paffy dedupe: %d workers, %lld rounds; launcher: copy %.3f s of %.3f s\n", n, (long long)rounds, t_copy, seconds_now() - t_start);
+    return any_bad ? status_of(st) : 0;
+}
+
 int main(int argc, char **argv) {
     find_worker();
     const char *g = getenv("PAFFY_GPUS");
@@ -1222,13 +1404,14 @@ int main(int argc, char **argv) {
     if (n > MAX_RANKS) n = MAX_RANKS;
     const int is_chain = argc >= 2 && !strcmp(argv[1], "chain");
     const int is_bed = argc >= 2 && !strcmp(argv[1], "to_bed");
-    int shard = n > 1 && argc >= 2 && (is_stream_cmd(argv[1]) || !strcmp(argv[1], "tile") || is_chain || is_bed);
+    const int is_dedupe = argc >= 2 && !strcmp(argv[1], "dedupe");
+    int shard = n > 1 && argc >= 2 && (is_stream_cmd(argv[1]) || !strcmp(argv[1], "tile") || is_chain || is_bed || is_dedupe);
     CmdLine cl;
     memset(&cl, 0, sizeof(cl));
     if (shard) {
         parse_cmdline(argc, argv, &cl);
         shard = cl.ok; /* -h, or something getopt_long would reject: the one worker says what the reference says */
-        if (shard && (is_chain || is_bed) && cl.in_path) { /* and so it does for an input that cannot be opened */
+        if (shard && (is_chain || is_bed || is_dedupe) && cl.in_path) { /* and so it does for an input that cannot be opened */
             const int fd = open(cl.in_path, O_RDONLY);
             if (fd < 0) shard = 0;
             else close(fd);
@@ -1268,7 +1451,8 @@ int main(int argc, char **argv) {
         close(fd);
         in_path = g_stdin_spool;
     }
-    if (is_bed) { /* an input without a line: under -f -q one worker still lists every FASTA record, so it is that worker's (stdin is at its end) */
+    if (is_bed || is_dedupe) { /* an input without a line: under to_bed -f -q one worker still lists every FASTA record, and dedupe has no round to run, so it is
+                                  one plain worker's (stdin is at its end) */
         struct stat sb;
         if (stat(in_path, &sb) == 0 && sb.st_size == 0) {
             cleanup();
@@ -1281,7 +1465,8 @@ int main(int argc, char **argv) {
     }
     const int rc = !strcmp(argv[1], "tile") ? run_tile(&cl, n, one_device, in_path, out_path)
                    : (is_chain ? run_chain(&cl, n, one_device, in_path, out_path)
-                               : (is_bed ? run_to_bed(&cl, n, one_device, in_path, out_path) : run_stream(argv[1], &cl, n, one_device, in_path, out_path)));
+                               : (is_bed ? run_to_bed(&cl, n, one_device, in_path, out_path)
+                                         : (is_dedupe ? run_dedupe(&cl, n, one_device, in_path, out_path) : run_stream(argv[1], &cl, n, one_device, in_path, out_path))));
     free(cl.copy);
     return rc;
 }

@@ -10,6 +10,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -1130,4 +1131,250 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
     paffy_hip_destroy(ctx);
     fflush(out);
     return rc;
+}
+
+/*
+ * ---- `paffy dedupe` as one of N workers of the launcher (host/paffy_launch.c): the part mode ----
+ * PAFFY_DEDUPE_PART=<spooldir>/<rank>, PAFFY_DEDUPE_FDS=<from_launcher>,<to_launcher> (two inherited pipe descriptors), PAFFY_RANK,
+ * PAFFY_WORLD = N and PAFFY_DEDUPE_SHARE_BYTES = C. Every worker reads the one input itself. cut(j) is the first line end at or after
+ * j * C (cut(0) = 0, the last cut the file's size), share j is [cut(j), cut(j + 1)), round k is shares kN .. kN + N - 1 and this worker
+ * takes share kN + rank: within a round the workers' shares are consecutive stretches of the input, which is what the part calls of
+ * include/paffy_hip.h ask for, and every worker knows the number of rounds from the file's size. A record's number is cut(j) + its index
+ * in the share -- a share has no more lines than bytes, so the numbers are unique and rise with the input order; nobody has to count the
+ * lines in front of a share before the keys are made. A worker whose share is empty skips the source-side calls and still decides.
+ * A round has four phases; after each the worker writes eight int64 {phase, 0, a, 0, 0, count, 0, 0} and reads one int64, code in the two
+ * low bits (0 go on, 1 speak, 2 end), a number above them. The files, reused from round to round, lie next to each other:
+ *   1 keys      <rank>.ent: the entries of part_keys, grouped by owner; <rank>.cnt: N int64, the entries per owner. count = the records
+ *   2 decide    owner p reads its stretch of every <s>.ent (the counts say where) into one buffer; <p>.ver: part_decide's verdict bytes
+ *   3 verdicts  the worker reads its stretch of every <p>.ver; a = its lowest failing number or -1; the answer's number is the run's + 1
+ *   4 write     part_plan(the run's), the lines appended to the output spool; count = their bytes, a = 1: the failing record is here.
+ *               That worker is told to speak, the number being the records in front of its share: the message is the one-worker run's.
+ * End-of-file in place of an answer ends the worker.
+ */
+typedef struct {
+    char dir[4096];
+    int from_fd, to_fd, fd;
+    int rank, world;
+    int64_t size, share;
+    double t_files, t_wait; /* seconds in the exchange files and between a report and its answer (-l INFO) */
+} dedupe_part;
+
+static double dedupe_now(void) {
+    struct timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+}
+
+static int64_t dedupe_cut(const dedupe_part *p, int64_t j) {
+    if (j <= 0) return 0;
+    if (j >= p->size / p->share + (p->size % p->share != 0)) return p->size;
+    char blk[65536];
+    for (int64_t at = j * p->share; at < p->size;) {
+        const ssize_t got = pread(p->fd, blk, sizeof(blk), (off_t)at);
+        if (got < 0 && errno == EINTR) continue;
+        if (got <= 0) break;
+        const char *nl = (const char *)memchr(blk, '\n', (size_t)got);
+        if (nl) return at + (nl - blk) + 1;
+        at += got;
+    }
+    return p->size;
+}
+
+static int dedupe_file_put(dedupe_part *p, int rank, const char *ext, const void *data, size_t bytes) {
+    char path[4200];
+    const double t0 = dedupe_now();
+    snprintf(path, sizeof(path), "%s/%d.%s", p->dir, rank, ext);
+    FILE *f = fopen(path, "w");
+    int rc = !f || (bytes && fwrite(data, 1, bytes, f) != bytes);
+    if (f && fclose(f) != 0) rc = 1;
+    p->t_files += dedupe_now() - t0;
+    if (rc) fprintf(stderr, "paffy dedupe: cannot write %s\n", path);
+    return rc;
+}
+
+static int fd_get(int fd, int64_t at, void *buf, size_t bytes) {
+    for (size_t have = 0; have < bytes;) {
+        const ssize_t got = pread(fd, (char *)buf + have, bytes - have, (off_t)(at + (int64_t)have));
+        if (got < 0 && errno == EINTR) continue;
+        if (got <= 0) return 1;
+        have += (size_t)got;
+    }
+    return 0;
+}
+
+static int dedupe_file_get(dedupe_part *p, int rank, const char *ext, int64_t at, void *buf, size_t bytes) {
+    if (!bytes) return 0;
+    char path[4200];
+    const double t0 = dedupe_now();
+    snprintf(path, sizeof(path), "%s/%d.%s", p->dir, rank, ext);
+    const int fd = open(path, O_RDONLY);
+    const int rc = fd < 0 || fd_get(fd, at, buf, bytes);
+    if (fd >= 0) close(fd);
+    p->t_files += dedupe_now() - t0;
+    if (rc) fprintf(stderr, "paffy dedupe: cannot read %s\n", path);
+    return rc;
+}
+
+/* a report up the pipe, the launcher's answer back; "end" ends the process here */
+static int64_t dedupe_settle(dedupe_part *p, int64_t phase, int64_t a, int64_t count) {
+    const int64_t rep[8] = {phase, 0, a, 0, 0, count, 0, 0};
+    const double t0 = dedupe_now();
+    for (size_t at = 0; at < sizeof(rep);) {
+        const ssize_t k = write(p->to_fd, (const char *)rep + at, sizeof(rep) - at);
+        if (k < 0 && errno == EINTR) continue;
+        if (k <= 0) exit(1); /* the launcher is gone */
+        at += (size_t)k;
+    }
+    const int64_t verdict = part_verdict(p->from_fd);
+    p->t_wait += dedupe_now() - t0;
+    if ((verdict & 3) == 2) exit(0);
+    if ((verdict & 3) == 3 || ((verdict & 3) == 1 && phase != 4)) exit(1);
+    return verdict;
+}
+
+int host_dedupe_in_part(void) { return getenv("PAFFY_DEDUPE_PART") && *getenv("PAFFY_DEDUPE_PART") && getenv("PAFFY_DEDUPE_FDS"); }
+
+int host_dedupe_part(const char *in_path, const char *out_path, int check_inverse) {
+    dedupe_part P;
+    memset(&P, 0, sizeof(P));
+    const char *prefix = getenv("PAFFY_DEDUPE_PART"), *fds = getenv("PAFFY_DEDUPE_FDS"), *share = getenv("PAFFY_DEDUPE_SHARE_BYTES");
+    const char *rank = getenv("PAFFY_RANK"), *world = getenv("PAFFY_WORLD");
+    const char *slash = prefix ? strrchr(prefix, '/') : NULL;
+    if (!slash || !fds || sscanf(fds, "%d,%d", &P.from_fd, &P.to_fd) != 2 || !rank || !world || !in_path || !out_path || (size_t)(slash - prefix) >= sizeof(P.dir)) {
+        fprintf(stderr, "paffy dedupe: cannot use the part %s (PAFFY_DEDUPE_FDS=%s)\n", prefix ? prefix : "", fds ? fds : "");
+        return 1;
+    }
+    memcpy(P.dir, prefix, (size_t)(slash - prefix));
+    P.rank = atoi(rank);
+    P.world = atoi(world);
+    P.share = share && atoll(share) >= 1 ? (int64_t)atoll(share) : (int64_t)chunk_bytes();
+    P.fd = open(in_path, O_RDONLY);
+    const off_t size = P.fd < 0 ? -1 : lseek(P.fd, 0, SEEK_END);
+    if (size < 0 || P.world < 1 || P.rank < 0 || P.rank >= P.world) {
+        fprintf(stderr, "paffy dedupe: cannot open %s\n", in_path);
+        return 1;
+    }
+    P.size = (int64_t)size;
+    FILE *out = fopen(out_path, "w");
+    if (!out) {
+        fprintf(stderr, "paffy dedupe: cannot open %s\n", out_path);
+        return 1;
+    }
+    const double t_start = dedupe_now();
+    paffy_hip_ctx *ctx = open_ctx();
+    if (!ctx) return 1;
+    const int N = P.world, me = P.rank;
+    int64_t *cnt = (int64_t *)calloc((size_t)N * (size_t)N, sizeof(int64_t)); /* cnt[s * N + p]: entries of source s for owner p */
+    const int64_t shares = P.size / P.share + (P.size % P.share != 0), rounds = (shares + N - 1) / N;
+    int rc = !cnt;
+    for (int64_t k = 0; k < rounds && !rc; k++) {
+        const int64_t a = dedupe_cut(&P, k * N + me), len = dedupe_cut(&P, k * N + me + 1) - a;
+        if (len >= ((int64_t)1 << 31) - 64) {
+            fprintf(stderr, "paffy dedupe: a share of 2 GiB or more\n");
+            return 1;
+        }
+        void *d_in = NULL, *d_ent = NULL, *d_own = NULL, *d_ver = NULL, *d_out = NULL;
+        char *h_in = NULL, *h_ent = NULL, *h_own = NULL, *h_ver = NULL, *h_out = NULL;
+        int64_t *mine = cnt + (size_t)me * (size_t)N, n_rec = 0, n_ent = 0;
+        memset(mine, 0, sizeof(int64_t) * (size_t)N);
+        /* 1: the keys of this share */
+        if (len > 0) {
+            h_in = (char *)malloc((size_t)len);
+            rc = !h_in || fd_get(P.fd, a, h_in, (size_t)len);
+            int64_t lines = !rc && h_in[len - 1] != '\n';
+            for (const char *q = h_in, *e = h_in + len; !rc && q < e && (q = (const char *)memchr(q, '\n', (size_t)(e - q))) != NULL; q++) lines++;
+            if (!rc) rc = paffy_hip_malloc(&d_in, len + 64) || paffy_hip_memcpy_h2d(d_in, h_in, len) || paffy_hip_malloc(&d_ent, lines * 32 + 64);
+            if (!rc) rc = paffy_hip_dedupe_part_keys(ctx, d_in, len, check_inverse, a, N, d_ent, lines, mine, &n_rec);
+            for (int p = 0; p < N; p++) n_ent += mine[p];
+            if (!rc && n_ent > 0) {
+                h_ent = (char *)malloc((size_t)n_ent * 32);
+                rc = !h_ent || paffy_hip_sync(ctx) || paffy_hip_memcpy_d2h(h_ent, d_ent, n_ent * 32);
+            }
+            free(h_in);
+        }
+        if (rc) break;
+        if (dedupe_file_put(&P, me, "ent", h_ent, (size_t)n_ent * 32) || dedupe_file_put(&P, me, "cnt", mine, sizeof(int64_t) * (size_t)N)) return 1;
+        free(h_ent);
+        dedupe_settle(&P, 1, 0, n_rec);
+        /* 2: the entries every worker addressed to this one, decided in one call */
+        int64_t total = 0;
+        for (int s = 0; s < N; s++) {
+            if (dedupe_file_get(&P, s, "cnt", 0, cnt + (size_t)s * (size_t)N, sizeof(int64_t) * (size_t)N)) return 1;
+            total += cnt[(size_t)s * (size_t)N + (size_t)me];
+        }
+        if (total > 0) {
+            h_own = (char *)malloc((size_t)total * 32);
+            h_ver = (char *)malloc((size_t)total);
+            if (!h_own || !h_ver) return 1;
+            int64_t at = 0;
+            for (int s = 0; s < N; s++) {
+                int64_t skip = 0;
+                for (int p = 0; p < me; p++) skip += cnt[(size_t)s * (size_t)N + (size_t)p];
+                const int64_t c = cnt[(size_t)s * (size_t)N + (size_t)me];
+                if (dedupe_file_get(&P, s, "ent", skip * 32, h_own + at * 32, (size_t)c * 32)) return 1;
+                at += c;
+            }
+            rc = paffy_hip_malloc(&d_own, total * 32 + 64) || paffy_hip_memcpy_h2d(d_own, h_own, total * 32) || paffy_hip_malloc(&d_ver, total + 64);
+            if (!rc) rc = paffy_hip_dedupe_part_decide(ctx, d_own, total, check_inverse, d_ver);
+            if (!rc) rc = paffy_hip_sync(ctx) || paffy_hip_memcpy_d2h(h_ver, d_ver, total);
+            if (d_own) paffy_hip_free(d_own);
+            if (d_ver) paffy_hip_free(d_ver);
+            free(h_own);
+            if (rc) break;
+        }
+        if (dedupe_file_put(&P, me, "ver", h_ver, (size_t)total)) return 1;
+        free(h_ver);
+        dedupe_settle(&P, 2, 0, total);
+        /* 3: the owners' answers about this share */
+        int64_t first_bad = -1;
+        if (len > 0) {
+            h_ver = (char *)malloc((size_t)n_ent + 1);
+            if (!h_ver) return 1;
+            int64_t at = 0;
+            for (int p = 0; p < N; p++) {
+                int64_t skip = 0;
+                for (int s = 0; s < me; s++) skip += cnt[(size_t)s * (size_t)N + (size_t)p];
+                if (dedupe_file_get(&P, p, "ver", skip, h_ver + at, (size_t)mine[p])) return 1;
+                at += mine[p];
+            }
+            rc = paffy_hip_malloc(&d_ver, n_ent + 64) || (n_ent && paffy_hip_memcpy_h2d(d_ver, h_ver, n_ent));
+            if (!rc) rc = paffy_hip_dedupe_part_verdicts(ctx, d_ver, n_ent, &first_bad);
+            if (!rc) rc = paffy_hip_sync(ctx);
+            if (d_ver) paffy_hip_free(d_ver);
+            free(h_ver);
+            if (rc) break;
+        }
+        const int64_t run_bad = (dedupe_settle(&P, 3, first_bad, 0) >> 2) - 1;
+        /* 4: the lines of this share in front of the run's failing record */
+        paffy_plan_info info;
+        memset(&info, 0, sizeof(info));
+        if (len > 0) {
+            rc = paffy_hip_dedupe_part_plan(ctx, run_bad, &info);
+            if (!rc && info.out_bytes > 0) {
+                h_out = (char *)malloc((size_t)info.out_bytes);
+                rc = !h_out || paffy_hip_malloc(&d_out, info.out_bytes + 64) || paffy_hip_emit(ctx, d_out, info.out_bytes + 64) || paffy_hip_sync(ctx) ||
+                     paffy_hip_memcpy_d2h(h_out, d_out, info.out_bytes);
+                if (!rc) rc = fwrite(h_out, 1, (size_t)info.out_bytes, out) != (size_t)info.out_bytes;
+                if (d_out) paffy_hip_free(d_out);
+                free(h_out);
+            }
+            if (!rc) rc = fflush(out) != 0; /* complete before the report that mentions the bytes */
+            paffy_hip_free(d_in);
+            paffy_hip_free(d_ent);
+            if (rc) break;
+        }
+        const int64_t verdict = dedupe_settle(&P, 4, info.error.code != 0, info.out_bytes > 0 ? info.out_bytes : 0);
+        if ((verdict & 3) == 1) { /* the failing record is this share's: its index here, the records in front of the share from the launcher */
+            if (!info.error.code) exit(1);
+            info.error.record -= a;
+            die_like_reference(&info.error, verdict >> 2);
+        }
+    }
+    if (rc) fprintf(stderr, "paffy: GPU call failed (%d): %s\n", rc, paffy_hip_last_error(ctx));
+    host_log_info("paffy dedupe: part %d of %d, %lld rounds: exchange files %.3f s, waiting for the others %.3f s of %.3f s\n", me, N, (long long)rounds, P.t_files, P.t_wait,
+                  dedupe_now() - t_start);
+    free(cnt);
+    close(P.fd);
+    paffy_hip_destroy(ctx);
+    return (fclose(out) != 0 || rc) ? 1 : 0;
 }

@@ -150,14 +150,6 @@ __global__ __launch_bounds__(PAFFY_NT) void k_dd_unpack(const DdEntry *entries, 
     kg[i] = g.x;
     idx[i] = i;
 }
-__global__ __launch_bounds__(PAFFY_NT) void k_dd_iota(uint32_t *idx, uint32_t n) {
-    const uint32_t i = blockIdx.x * PAFFY_NT + threadIdx.x;
-    if (i < n) idx[i] = i;
-}
-__global__ __launch_bounds__(PAFFY_NT) void k_dd_gather_u32_by(const uint32_t *src, const uint32_t *order, uint32_t n, uint32_t *dst) {
-    const uint32_t p = blockIdx.x * PAFFY_NT + threadIdx.x;
-    if (p < n) dst[p] = src[order[p]];
-}
 /* position p of the order by (class, number): head[p] = p where a class begins, else 0 (a running maximum gives every position its head) */
 __global__ __launch_bounds__(PAFFY_NT) void k_dd_heads(const DdEntry *entries, const uint32_t *order, uint32_t n, uint32_t *head) {
     const uint32_t p = blockIdx.x * PAFFY_NT + threadIdx.x;
@@ -204,6 +196,27 @@ __global__ __launch_bounds__(PAFFY_NT) void k_dd_remember(const DdEntry *entries
     mem_hi[q] = k.x;
     mem_lo[q] = k.y;
     mem_or[q] = (uint32_t)(g.y & 1u);
+}
+/* The memory's n_a classes [0, n_a) and the round's n_b new ones [n_a, n_a + n_b) of hi / lo / orient, each run sorted by (hi, lo) and
+   the two disjoint (a new class is one the memory does not hold: no tie rule), merged into hi2 / lo2 / or2: element i of a run goes to
+   i + the number of elements of the OTHER run that are less than it -- one binary search, and the orientation word moves with its key. */
+__global__ __launch_bounds__(PAFFY_NT) void k_dd_merge(const uint64_t *hi, const uint64_t *lo, const uint32_t *orient, uint32_t n_a, uint32_t n_b, uint64_t *hi2, uint64_t *lo2,
+                                                     uint32_t *or2) {
+    const uint32_t t = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (t >= n_a + n_b) return;
+    const bool mine_a = t < n_a;
+    const uint64_t kh = hi[t], kl = lo[t];
+    const uint32_t first = mine_a ? n_a : 0u; /* the other run is [first, first + len) */
+    uint32_t b = 0, e = mine_a ? n_b : n_a;
+    while (b < e) {
+        const uint32_t m = b + ((e - b) >> 1);
+        if (dd_less(hi[first + m], lo[first + m], kh, kl)) b = m + 1;
+        else e = m;
+    }
+    const uint32_t q = (mine_a ? t : t - n_a) + b; /* < n_a + n_b: the place in its own run plus at most the other run's length */
+    hi2[q] = kh;
+    lo2[q] = kl;
+    or2[q] = orient[t];
 }
 
 /* ---- source side, after the owners answered ---- */
@@ -388,7 +401,7 @@ int paffy_hip_dedupe_part_decide(paffy_hip_ctx *c, const void *d_entries, int64_
     HIPCHK(c, hipMemcpyAsync(&last_flag, wflag + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint32_t nw = last_pos + last_flag;
-    if (nw > 0) { /* the new classes behind the memory's, then the memory sorted again by (hi, lo) */
+    if (nw > 0) { /* the new classes behind the memory's, then the two runs merged by (hi, lo) */
         const size_t m = P.mem_n + nw;
         if (m >= (1ull << 31)) {
             c->last_error = "dedupe in parts: more than 2^31 classes in one owner's memory";
@@ -403,20 +416,11 @@ int paffy_hip_dedupe_part_decide(paffy_hip_ctx *c, const void *d_entries, int64_
         uint32_t *mo = static_cast<uint32_t *>(P.mem_or.p);
         LAUNCH(c, "k_dd_remember", k_dd_remember, dim3(grid), dim3(PAFFY_NT), 0, entries, order, static_cast<const uint32_t *>(wflag), static_cast<const uint32_t *>(wpos), n, mh + used,
                ml + used, mo + used);
-        if (dd_parts_scratch(c, P, m)) return PAFFY_E_HIP; /* may move the buffers `order` lay in: it is not read below */
-        k64a = static_cast<uint64_t *>(P.k64a.p), k64b = static_cast<uint64_t *>(P.k64b.p);
-        idx = static_cast<uint32_t *>(P.idx.p), va = static_cast<uint32_t *>(P.va.p), vb = static_cast<uint32_t *>(P.vb.p);
+        /* both runs are sorted -- the memory by construction, the new classes because wpos is a scan over entries in (hi, lo, number)
+           order -- and disjoint: one merge in place of a sort of all m */
         const uint32_t gm = (uint32_t)((m + PAFFY_NT - 1) / PAFFY_NT);
-        LAUNCH(c, "k_dd_iota", k_dd_iota, dim3(gm), dim3(PAFFY_NT), 0, idx, (uint32_t)m);
-        if (dd_parts_sort(c, P, ml, k64a, idx, va, m)) return PAFFY_E_HIP;
-        LAUNCH(c, "k_gather_u64_by", k_gather_u64_by, dim3(gm), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(mh), static_cast<const uint32_t *>(va), (uint32_t)m, k64b);
-        if (dd_parts_sort(c, P, k64b, k64a, va, vb, m)) return PAFFY_E_HIP;
-        LAUNCH(c, "k_gather_u64_by", k_gather_u64_by, dim3(gm), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(mh), static_cast<const uint32_t *>(vb), (uint32_t)m,
-               static_cast<uint64_t *>(P.mem_hi2.p));
-        LAUNCH(c, "k_gather_u64_by", k_gather_u64_by, dim3(gm), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(ml), static_cast<const uint32_t *>(vb), (uint32_t)m,
-               static_cast<uint64_t *>(P.mem_lo2.p));
-        LAUNCH(c, "k_dd_gather_u32_by", k_dd_gather_u32_by, dim3(gm), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(mo), static_cast<const uint32_t *>(vb), (uint32_t)m,
-               static_cast<uint32_t *>(P.mem_or2.p));
+        LAUNCH(c, "k_dd_merge", k_dd_merge, dim3(gm), dim3(PAFFY_NT), 0, static_cast<const uint64_t *>(mh), static_cast<const uint64_t *>(ml), static_cast<const uint32_t *>(mo),
+               (uint32_t)used, nw, static_cast<uint64_t *>(P.mem_hi2.p), static_cast<uint64_t *>(P.mem_lo2.p), static_cast<uint32_t *>(P.mem_or2.p));
         std::swap(P.mem_hi, P.mem_hi2);
         std::swap(P.mem_lo, P.mem_lo2);
         std::swap(P.mem_or, P.mem_or2);

@@ -8,7 +8,12 @@ records (a batch stays below 2 GiB); a round is cut into k consecutive shares of
 
 One JSON line per figure: HIP events on the stream around the whole step (every round, plan and emit), one warm-up, the smallest and
 the median of --reps runs. --tree DIR: import paffy_amd (with its built library) from another checkout, for example the parent
-commit's, so that one copy of this script times both; on a tree without the parts it prints the one-context line only."""
+commit's, so that one copy of this script times both; on a tree without the parts it prints the one-context line only.
+
+--decide-until M: times paffy_hip_dedupe_part_decide alone, the owner's step whose cost grows with its memory: rounds of --decide-round
+fresh classes (random 128-bit class keys, no text) into one context until its memory holds at least M classes, the whole series --reps
+times from a reset. One JSON line per round: the classes held before it, the milliseconds of every repeat, their smallest, median and
+spread (largest - smallest). Run it on two builds (--tree, or PAFFY_HIP_LIB) to compare how they keep the memory sorted."""
 import argparse
 import json
 import os
@@ -19,6 +24,40 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, MEAN_OPS = 0x5EED0003, 2048
 
 
+def decide_series(a, torch, paffy_amd, eng):
+    import ctypes as C
+
+    L, n = paffy_amd.engine.lib(), a.decide_round
+    n_rounds = -(-a.decide_until // n)
+    gen = torch.Generator(device="cpu").manual_seed(SEED)
+    rounds = []
+    for r in range(n_rounds):  # entries: class hi, class lo, global number, flags (bit 0: the own key is the class key)
+        e = torch.randint(-(1 << 63), (1 << 63) - 1, (n, 4), dtype=torch.int64, generator=gen)
+        e[:, 2] = torch.arange(r * n, (r + 1) * n)
+        e[:, 3] = 1
+        rounds.append(e.to(eng.device))
+    verdicts = torch.zeros(n + 64, dtype=torch.uint8, device=eng.device)
+    ms = [[] for _ in range(n_rounds)]
+    for rep in range(a.reps + 1):  # the first series warms up (buffers, code objects) and is not kept
+        eng.dedupe_reset()
+        for r, e in enumerate(rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            rc = L.paffy_hip_dedupe_part_decide(eng._ctx, C.c_void_p(e.data_ptr()), n, 1, C.c_void_p(verdicts.data_ptr()))
+            e1.record()
+            torch.cuda.synchronize()
+            assert rc == 0, rc
+            if rep == 0:
+                assert int((verdicts[:n] & 1).sum().item()) == n  # every class is new: all of them enter the memory
+            else:
+                ms[r].append(e0.elapsed_time(e1))
+    for r in range(n_rounds):
+        print(json.dumps({"label": a.label, "cmd": "part_decide", "round": r, "entries": n, "memory_before": r * n, "memory_after": (r + 1) * n, "ms": round(min(ms[r]), 3),
+                          "ms_median": round(statistics.median(ms[r]), 3), "ms_spread": round(max(ms[r]) - min(ms[r]), 3), "ms_all": [round(t, 3) for t in ms[r]]}), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=200000)
@@ -27,6 +66,8 @@ def main():
     ap.add_argument("--parts", type=int, nargs="*", default=[1, 2, 4, 8])
     ap.add_argument("--label", default="")
     ap.add_argument("--tree", default=ROOT, help="the checkout whose paffy_amd is timed (default: this one)")
+    ap.add_argument("--decide-until", type=int, default=0, help="time part_decide alone until the memory holds this many classes")
+    ap.add_argument("--decide-round", type=int, default=131072, help="fresh classes per round of --decide-until")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
     import torch
@@ -35,6 +76,8 @@ def main():
     from paffy_amd import shard
 
     eng = paffy_amd.Engine()
+    if a.decide_until > 0:
+        return decide_series(a, torch, paffy_amd, eng)
     per_round = a.records // a.rounds
     fresh, dup = per_round * 3 // 4, per_round - per_round * 3 // 4
 
