@@ -22,6 +22,10 @@
  * characters outside MID=X, a failing check, rows whose digit counts change inside the record, pieces longer than the writers' LDS
  * staging, sums beyond 31 bits, any error at all -- it leaves to the record kernels (flat_done[rec] = 0), which run afterwards over
  * exactly those records; errors are reported there, by the code that has always reported them.
+ *
+ * The two mismatch commands, each as a pipe of its own, use k_flat_parse and the pieces with kernels of their own in place of the sizing
+ * kernels: `add_mismatches` the encoder on the pieces (flat_add_kernel.h), `add_mismatches -a` the merge of the M/=/X runs across the
+ * pieces (flat_remove_kernel.h; = and X ops are its normal input, so FLAT_F_NONPLAIN does not send a record away there).
  */
 #ifndef PAFFY_FLAT_KERNEL_H_
 #define PAFFY_FLAT_KERNEL_H_

@@ -29,6 +29,7 @@
 #include "record_groups.h"
 #include "flat_kernel.h"
 #include "flat_add_kernel.h"
+#include "flat_remove_kernel.h"
 #include "coverage_kernel.h"
 #include "bed_kernel.h"
 #include "fasta_kernel.h"
@@ -1468,7 +1469,8 @@ static int upconvert_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bo
 enum FlatMode {
     FLAT_MODE_NONE, /* the record kernels size every record */
     FLAT_MODE_PASS, /* the flat pass (flat_kernel.h); what it leaves goes to the record kernels */
-    FLAT_MODE_ADD   /* `paffy add_mismatches` alone: the flat parse and the encoder on its pieces (flat_add_kernel.h) */
+    FLAT_MODE_ADD,  /* `paffy add_mismatches` alone: the flat parse and the encoder on its pieces (flat_add_kernel.h) */
+    FLAT_MODE_REMOVE /* `paffy add_mismatches -a` alone: the flat parse and the merge of the M/=/X runs on its pieces (flat_remove_kernel.h) */
 };
 struct StageClass {
     paffy_stage stages[PAFFY_MAX_STAGES]; /* kinds without the PAFFY_NO_CHECK flag; a leading dechunk is its paf_check */
@@ -1539,6 +1541,8 @@ static int classify_stages(paffy_hip_ctx *c, const paffy_stage *stages, int32_t 
     static const bool flat_off = getenv("PAFFY_NO_FLAT") != nullptr;
     /* `paffy add_mismatches` alone (BASELINE cfg4): the same parse, the encoder on the pieces (flat_add_kernel.h) */
     if (n_stages == 1 && norm[0].kind == PAFFY_ADD_MISMATCHES && s.nocheck_mask == 0 && !flat_off && c->n_seqs > 0) s.flat = FLAT_MODE_ADD;
+    /* `paffy add_mismatches -a` alone, with its paf_check: the same parse, the runs merged across the pieces (flat_remove_kernel.h) */
+    else if (n_stages == 1 && norm[0].kind == PAFFY_REMOVE_MISMATCHES && s.nocheck_mask == 0 && !flat_off) s.flat = FLAT_MODE_REMOVE;
     else if (lean_or_filter && s.nocheck_mask == 0 && !flat_off) s.flat = FLAT_MODE_PASS;
     /* the first instantiation that knows every stage kind: the lean kinds; them and add_mismatches (the encoder wants the registers); them
        with filter / trim -f / stats / check; no stage of the kinds that came with the encoder; all */
@@ -1714,6 +1718,66 @@ static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records)
         HIPCHK(c, hipMemcpyAsync(c->info.p, &z, sizeof(z), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    *need_records = c->h_info->flat_legacy > 0;
+    c->flat_left = c->h_info->flat_legacy;
+    kp.flat_done = static_cast<const uint8_t *>(c->flat_done.p);
+    return 0;
+}
+
+/* `paffy add_mismatches -a` alone: the flat parse, then the merge of the M/=/X runs on its pieces. One pass: the new cigar never has more
+   ops than the old one and an op takes two bytes of text at least, so len / 2 words always hold the new ops of a batch.
+   *need_records: records were left to the record kernels. */
+static int plan_flat_remove(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records) {
+    KParams &kp = c->kp;
+    const uint32_t len = kp.in_len;
+    const FlatParams fp = flat_params(c, 0u);
+    LAUNCH(c, "k_flat_parse", k_flat_parse<0u>, dim3(2048), dim3(64 * FLAT_PARSE_WAVES), 0, fp);
+    const uint32_t n_slots = c->flat_piece_slots, n_sblocks = (n_slots + SCAN32_BLOCK - 1) / SCAN32_BLOCK;
+    static_assert(sizeof(RmEdge) == sizeof(uint64_t), "the edges take the encoder's scratch offsets");
+    if (ensure(c, c->add_pieces, sizeof(AddPiece) * (size_t)n_slots) || ensure(c, c->add_scr_cnt, sizeof(uint32_t) * (size_t)n_slots) ||
+        ensure(c, c->add_scr_off, sizeof(RmEdge) * (size_t)n_slots) || ensure(c, c->add_new_cnt, sizeof(uint32_t) * (size_t)n_slots) ||
+        ensure(c, c->add_new_off, sizeof(uint64_t) * (size_t)n_slots) || ensure(c, c->add_text, sizeof(uint32_t) * (size_t)n_slots) ||
+        ensure(c, c->add_bad, sizeof(uint32_t) * (size_t)(n_lines + 1)) || ensure(c, c->add_part, sizeof(uint64_t) * (size_t)(n_sblocks + 1)) ||
+        ensure(c, c->add_new_ops, 4 * ((size_t)len / 2 + 1024)))
+        return PAFFY_E_HIP;
+    /* segments of the lines of more than PAFFY_ROWS_MAX_OPS new ops. As in plan_flat_add two neighbouring segments hold more than
+       ADD_SEG_OPS (16 384) new ops, so a line of T new ops has at most T / 8192 + 1 segments. Here the bounds are hard: all lines
+       together have at most len / 2 new ops (len >> 14 segments), and a line with segments has more than 32 768 ops, 64 KiB of text,
+       so at most len >> 16 lines add their "+ 1". The list cannot run out; n_items is clamped all the same. */
+    const size_t items_cap = ((size_t)len >> 14) + ((size_t)len >> 16) + 16;
+    if (ensure(c, c->flat_items, sizeof(EmitItem) * items_cap)) return PAFFY_E_HIP;
+    kp.items = static_cast<EmitItem *>(c->flat_items.p);
+    kp.items_cap = (uint32_t)items_cap;
+    RmParams rp;
+    memset(&rp, 0, sizeof(rp));
+    AddParams &ap = rp.A;
+    ap.P = kp;
+    ap.sums = fp.sums;
+    ap.pieces = static_cast<AddPiece *>(c->add_pieces.p);
+    ap.n_piece_slots = n_slots;
+    ap.new_cnt = static_cast<uint32_t *>(c->add_new_cnt.p);
+    ap.new_off = static_cast<const uint64_t *>(c->add_new_off.p);
+    ap.new_ops = static_cast<uint32_t *>(c->add_new_ops.p);
+    ap.new_cap = c->add_new_ops.cap / 4;
+    ap.text_cnt = static_cast<uint32_t *>(c->add_text.p);
+    ap.rec_bad = static_cast<uint32_t *>(c->add_bad.p);
+    ap.flat_done = static_cast<uint8_t *>(c->flat_done.p);
+    rp.edges = static_cast<RmEdge *>(c->add_scr_off.p);
+    rp.carry = static_cast<uint32_t *>(c->add_scr_cnt.p);
+    HIPCHK(c, hipMemsetAsync(c->add_pieces.p, 0xff, sizeof(AddPiece) * (size_t)n_slots, c->stream)); /* rec = FLAT_NO_CHUNK */
+    HIPCHK(c, hipMemsetAsync(c->add_new_cnt.p, 0, sizeof(uint32_t) * (size_t)n_slots, c->stream));
+    LAUNCH(c, "k_rm_prep", k_rm_prep, dim3((n_lines + 255) / 256), dim3(256), 0, rp);
+    LAUNCH(c, "k_rm_edges", k_rm_edges, dim3(2048), dim3(64 * ADD_WAVES), 0, rp);
+    LAUNCH(c, "k_rm_carry", k_rm_carry, dim3((n_lines + 255) / 256), dim3(256), 0, rp);
+    LAUNCH(c, "k_scan32_part", k_scan32_part, dim3(n_sblocks), dim3(256), 0, ap.new_cnt, n_slots, static_cast<uint64_t *>(c->add_new_off.p), static_cast<uint64_t *>(c->add_part.p));
+    LAUNCH(c, "k_scan32_fix", k_scan32_fix, dim3(n_sblocks), dim3(256), 0, n_slots, n_sblocks, static_cast<uint64_t *>(c->add_new_off.p), static_cast<const uint64_t *>(c->add_part.p),
+           static_cast<uint64_t *>(nullptr));
+    LAUNCH(c, "k_rm_fill", k_rm_fill, dim3(2048), dim3(64 * ADD_WAVES), 0, rp);
+    LAUNCH(c, "k_add_final", k_add_final, dim3((n_lines + 255) / 256), dim3(256), 0, ap);
+    kp.new_ops = ap.new_ops;
+    if (post_scans(c, n_lines)) return PAFFY_E_HIP;
+    if (fetch_info(c)) return PAFFY_E_HIP;
+    kp.n_items = std::min(c->h_info->n_items, kp.items_cap);
     *need_records = c->h_info->flat_legacy > 0;
     c->flat_left = c->h_info->flat_legacy;
     kp.flat_done = static_cast<const uint8_t *>(c->flat_done.p);
@@ -1905,6 +1969,7 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
         bool need_records = true;
         uint32_t flat_g_count = 0;
         if (s.flat == FLAT_MODE_ADD) rc = plan_flat_add(c, n_lines, &need_records);
+        else if (s.flat == FLAT_MODE_REMOVE) rc = plan_flat_remove(c, n_lines, &need_records);
         else if (s.flat == FLAT_MODE_PASS) rc = plan_flat(c, s, n_lines, &need_records, &flat_g_count);
         if (!rc && need_records) rc = plan_records(c, s, n_lines, lvl0_long, flat_g_count);
     }

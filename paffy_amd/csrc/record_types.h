@@ -71,7 +71,7 @@ struct RecPlan {
                        bit17 the 4-byte ops live in the arena block arena_off[rec] (rebuilt by add_mismatches), not in the mirror,
                        bit18 the mirror holds 2-byte words (every length below 8192),
                        bit19 a long shatter record written as EmitItem segments by k_emit_rows,
-                       bit20 the 4-byte ops are words of new_ops[] (flat add_mismatches), bit21 the row pieces are in row_pieces[],
+                       bit20 the 4-byte ops are words of new_ops[] (flat add_mismatches and flat add_mismatches -a: flat_add_kernel.h, flat_remove_kernel.h), bit21 the row pieces are in row_pieces[],
                        bit22 the line's cigar is a stretch of the input's text: k_emit_copy (wq[0] = first byte from cg_off, wt[0] = bytes;
                        wq[1] / wt[1] = new length of a first / last op a fixed trim shortened, wq[2] / wt[2] = bytes of that op's text) */
     uint32_t chunk; /* ops per lane in the sizing sweep: wave w owns view ops [64*w*chunk, 64*(w+1)*chunk) */
@@ -129,7 +129,7 @@ struct KParams {
     int64_t *rec_stats;         /* PAFFY_STATS: six sums per record (the order of paf_stats_calc's arguments), or NULL */
     uint32_t nocheck_mask;      /* bit i: stage i runs without the paf_check the command loops append (PAFFY_NO_CHECK) */
     uint32_t wave_max_bytes;    /* records with at most this many cigar bytes are sized by the one-wave kernel (0: none): the four-wave kernel skips them */
-    const uint32_t *new_ops;    /* flat_add_kernel.h: the rebuilt cigars of all records, 4-byte ops back to back (RecPlan flag bit 20: arena_off counts words of it) */
+    const uint32_t *new_ops;    /* flat_add_kernel.h, flat_remove_kernel.h: the rebuilt cigars of all records, 4-byte ops back to back (RecPlan flag bit 20: arena_off counts words of it) */
     EmitItem *items;            /* segments of long records, written by the flat sizing pass, emitted by k_emit_rows in front of the records */
     uint32_t n_items, items_cap;
     uint8_t *row_pieces;        /* flat sizing pass: the three constant pieces of a record's rows, 3 x 48 zero filled bytes per record (RecPlan flag bit 21; NULL: none) */

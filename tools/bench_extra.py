@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Side measurements for DESIGN.md (not the driver's bench contract): `tile` and single commands
-on the synthetic stream, records/s with inputs resident in HBM. dechunk / pass / upconvert: the cfg3 stream, chunk-named for the first two."""
+on the synthetic stream, records/s with inputs resident in HBM. dechunk / pass / upconvert: the cfg3 stream, chunk-named for the first two.
+remove_eqx: `add_mismatches -a` on the cfg4 stream as `add_mismatches` wrote it (= and X runs: the command's real input; `remove` times
+the plain M/I/D stream, where almost nothing merges)."""
 import argparse
 import json
 import os
@@ -30,7 +32,7 @@ def main():
     ap.add_argument("--records", type=int, default=200000)
     ap.add_argument("--mean-ops", type=int, default=2048)
     ap.add_argument("--contigs", type=int, default=24, help="contigs of the synthetic stream (chain: fewer contigs = larger groups)")
-    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "filter", "add", "dedupe", "bed", "stats", "chain",
+    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "dedupe", "bed", "stats", "chain",
                                                     "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload"])
     ap.add_argument("--genome-gb", type=float, default=3.1, help="faffy_*: bases of the synthetic genome (24 contigs)")
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
@@ -48,7 +50,7 @@ def main():
     import paffy_amd
 
     eng = paffy_amd.Engine()
-    if a.cmd == "add":
+    if a.cmd in ("add", "remove_eqx"):
         # cfg4: 24 + 24 contigs of 50-250 Mb generated on the device, records on homologous bases (2 % substitutions)
         t0 = time.perf_counter()
         if os.environ.get("PAFFY_X_SMALL_GENOME"):  # experiment: genomes small enough to stay in the caches
@@ -57,6 +59,13 @@ def main():
             eng.synth4_setup(0x5EED0004, a.mean_ops)
         print(f"cfg4 genomes resident in HBM ({time.perf_counter() - t0:.1f} s to generate)", file=sys.stderr)
         buf, nbytes = eng.synth4(0, a.records)
+        if a.cmd == "remove_eqx":  # encoded once on the device, outside the timed region: the = / X text is the input
+            info = eng.plan([paffy_amd.stage(paffy_amd.ADD_MISMATCHES)], buf, nbytes)
+            assert info.error.code == 0
+            enc = eng.alloc_out(info.out_bytes)
+            eng.emit(enc)
+            eng.sync()
+            buf, nbytes = enc, int(info.out_bytes)
     elif a.cmd in ("dechunk", "upconvert", "pass"):
         # the cfg3 stream; dechunk and pass read it chunk-named (rewritten on the host once, outside the timed region), upconvert plain
         # with one interval per contig (every side renamed) and a thousand that match nothing
@@ -80,6 +89,7 @@ def main():
     kinds = {"invert": paffy_amd.INVERT, "trim": paffy_amd.TRIM_IDENTITY, "shatter": paffy_amd.SHATTER, "remove": paffy_amd.REMOVE_MISMATCHES, "filter": paffy_amd.FILTER}
     eng.set_filter(min_identity=0.9)
     kinds["add"] = paffy_amd.ADD_MISMATCHES
+    kinds["remove_eqx"] = paffy_amd.REMOVE_MISMATCHES
     kinds["stats"] = paffy_amd.STATS
     kinds["pass"] = paffy_amd.PASS
     kinds["upconvert"] = paffy_amd.UPCONVERT
@@ -112,9 +122,9 @@ def main():
         res.append(dt)
     dt = min(res)
     prof = {k: round(v[0] / max(1, v[1]), 3) for k, v in eng.profile_read().items()}
-    extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass") else {}
+    extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx") else {}
     print(json.dumps({**extra, "cmd": a.cmd, "records": a.records, "mean_ops": a.mean_ops, "in_bytes": nbytes, "out_bytes": int(info.out_bytes),
-                      "seconds": round(dt, 4), "records_per_s": round(a.records / dt, 1),
+                      "seconds": round(dt, 4), "repeats": [round(x, 4) for x in res], "records_per_s": round(a.records / dt, 1),
                       "GBps": round((nbytes + info.out_bytes) / dt / 1e9, 1), "kernel_ms": prof}))
 
 
