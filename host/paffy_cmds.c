@@ -483,7 +483,10 @@ int paffy_view_main(int argc, char *argv[]) {
     if (read_fasta_args("view", argv + optind, argc - optind, &f)) return 1;
     host_keep_raw_sequences(include_alignment); /* the rows show the bases in the case of the files */
     host_set_sequences(&f, 0);
+    /* without rows to print all that is read of a plan are its sums: the count walk alone (paffy_hip_stats_only) */
+    host_set_stats_only(!(include_alignment && per_alignment));
     if (host_load_fasta()) return 1;
+    host_set_stats_only(0);
     fasta_text_free(&f);
     host_set_alignment_rows(include_alignment && per_alignment); /* impl/paf_view.c:158-160: paf_pretty_print runs unless -t */
     const paffy_stage st[2] = {{PAFFY_ADD_MISMATCHES, 0.05f, 1.0f}, {PAFFY_STATS, 0.0f, 0.0f}};

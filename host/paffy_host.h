@@ -99,5 +99,8 @@ int host_fasta_seen(const fasta_text *t, const char *paf, int64_t paf_len, int w
 /* paffy view -a: keep the bases as loaded beside the upper-cased store (before host_stream), and print the rows under each stats line */
 void host_keep_raw_sequences(int on);
 void host_set_alignment_rows(int on);
+/* paffy view without rows (every form but `-a` without `-t`): the context host_load_fasta creates next plans for the sums only
+   (paffy_hip_stats_only) */
+void host_set_stats_only(int on);
 
 #endif

@@ -72,6 +72,8 @@ void host_set_sequences(const fasta_text *t, int log_count) {
 
 static int g_keep_raw = 0;
 void host_keep_raw_sequences(int on) { g_keep_raw = on; }
+static int g_stats_only = 0; /* paffy view without rows: the plans are asked for their sums only (paffy_hip_stats_only) */
+void host_set_stats_only(int on) { g_stats_only = on; }
 
 void host_set_log_level(const char *s) {
     g_log_level = 0;
@@ -394,6 +396,7 @@ static paffy_hip_ctx *open_ctx(void) {
 int host_load_fasta(void) {
     if (!(g_ctx = open_ctx())) return 1;
     if (g_keep_raw) paffy_hip_keep_raw_sequences(g_ctx, 1);
+    if (g_stats_only) paffy_hip_stats_only(g_ctx, 1);
     int64_t n_fasta = 0;
     if (g_seq_text) {
         if (load_fasta(g_ctx, g_seq_text, 0, &n_fasta) != 0) {

@@ -460,6 +460,17 @@ int paffy_hip_flat_stats(paffy_hip_ctx *ctx, int64_t *left, int64_t reasons[16])
  * `paffy view` (paf_pretty_print, impl/paf.c:269-281). Returns n_records or a negative error. */
 int64_t paffy_hip_plan_record_stats(paffy_hip_ctx *ctx, int64_t cap_records, int64_t *sums);
 /*
+ * Sums only: the caller declares that all it will ask of a plan is paffy_hip_plan_stats and paffy_hip_plan_record_stats (`paffy view`
+ * when it prints no base-level rows). Sticky, like paffy_hip_keep_raw_sequences. It takes effect for the stage list that is exactly
+ * [PAFFY_ADD_MISMATCHES, PAFFY_STATS], both with their paf_check, with sequences loaded and PAFFY_NO_FLAT unset: the plan then counts
+ * the matching columns of every M op on the pieces of the flat pass (paffy_amd/csrc/flat_view_kernel.h) and builds neither the = / X ops
+ * nor a line: info.n_records and info.error are as ever, info.out_bytes and info.n_rows are 0, the sums are those of the default plan,
+ * and paffy_hip_emit, paffy_hip_emit_lines, paffy_hip_plan_rows, paffy_hip_plan_record_layout, paffy_hip_plan_alignment_sizes and
+ * paffy_hip_plan_alignment_rows return PAFFY_E_STATE (paffy_hip_last_error names this setting). paffy_hip_flat_stats tells how many
+ * records went through the record kernels all the same. Every other stage list plans exactly as without the setting.
+ */
+int paffy_hip_stats_only(paffy_hip_ctx *ctx, int on);
+/*
  * Diagnostics of the last paffy_hip_plan, read only: for records [first, first + count) of the planned batch, flags[i] = the record's
  * RecPlan.flags (paffy_amd/csrc/record_types.h: bit 0 reversed view, bit 1 I / D exchanged, bit 2 query / target exchanged, bit 3 has a
  * cigar, bit 17 4-byte ops in an arena block, bit 18 2-byte words in the mirror, bit 20 the arena block is the flat add pass's) and

@@ -89,8 +89,10 @@ __global__ __launch_bounds__(256) void k_scan32_fix(uint32_t n, uint32_t n_block
     if (blockIdx.x == 0 && threadIdx.x == 0 && total) *total = (uint64_t)v[1];
 }
 
-/* one lane per record: is the record this pass's, where do its pieces stand */
-__global__ __launch_bounds__(256) void k_add_prep(AddParams A) {
+/* one lane per record: is the record this pass's, where do its pieces stand. SCR: the words of scratch a piece takes are written too
+   (the encoder; the sums-only pass of flat_view_kernel.h keeps the same records and needs none) */
+template <bool SCR>
+__device__ __forceinline__ void add_prep_lane(const AddParams &A) {
     const KParams &P = A.P;
     const uint32_t rec = blockIdx.x * 256u + threadIdx.x;
     if (rec >= P.n_rec) return;
@@ -126,13 +128,14 @@ __global__ __launch_bounds__(256) void k_add_prep(AddParams A) {
         AddPiece ap;
         ap.op_base = nb; ap.q_base = qb; ap.t_base = tb; ap.rec = rec;
         A.pieces[slot0 + p] = ap;
-        A.scr_cnt[slot0 + p] = s.extra + (cnt - s.rows); /* items + ops other than M */
+        if (SCR) A.scr_cnt[slot0 + p] = s.extra + (cnt - s.rows); /* items + ops other than M */
         nb += cnt;
         qb += s.m + s.x - s.del;
         tb += s.m + s.x - s.ins;
     }
     A.flat_done[rec] = 2; /* in progress: k_add_final decides */
 }
+__global__ __launch_bounds__(256) void k_add_prep(AddParams A) { add_prep_lane<true>(A); }
 
 #define ADD_WAVES 4u
 #define ADD_SEG_OPS (PAFFY_ROWS_MAX_OPS / 2u) /* new ops of a segment of a long line (closed at the next piece boundary) */

@@ -30,6 +30,7 @@
 #include "flat_kernel.h"
 #include "flat_add_kernel.h"
 #include "flat_remove_kernel.h"
+#include "flat_view_kernel.h"
 #include "coverage_kernel.h"
 #include "bed_kernel.h"
 #include "fasta_kernel.h"
@@ -1130,6 +1131,9 @@ struct paffy_hip_ctx {
     /* profiling */
     bool profile = false;
     int64_t flat_left = -1, flat_reasons[16] = {0}; /* paffy_hip_flat_stats */
+    bool stats_only = false;      /* paffy_hip_stats_only: the caller will only ask a plan for its sums */
+    bool plan_stats_only = false; /* the last plan took FLAT_MODE_VIEW: it has sums, no ops and no line plan */
+    DevBuf view_sums;             /* flat_view_kernel.h: six sums per piece slot */
     uint32_t flat_chunk_slots = 0;
     bool lvl0_long_ok = false, lvl0_long_off = false; /* the longer first store level: shown safe by the batch before / overflowed once */
     /* device buffers of the two slots of a closed stream (paffy_hip_stream_close), taken again by the next paffy_hip_stream_open: a
@@ -1327,7 +1331,7 @@ void paffy_hip_destroy(paffy_hip_ctx *c) {
     c->index_pool.clear();
     if (c->one_batch.p) (void)hipFree(c->one_batch.p);
     DevBuf *bufs[] = {&c->tile_counts, &c->sep_pos, &c->nl_idx, &c->meta, &c->out_len, &c->out_rows, &c->status, &c->err_aux,
-                      &c->n_ops, &c->arena_off, &c->out_off, &c->w_list, &c->b_list, &c->b_list1, &c->arena, &c->info, &c->synth_sizes, &c->rec_plan, &c->ops_mirror, &c->seq_blob, &c->seq_table, &c->seq_names, &c->seq_name_off, &c->synth4_contigs, &c->synth4_q, &c->synth4_t, &c->seq_comp, &c->seq_raw, &c->pretty_off, &c->pretty_out, &c->pretty_err, &c->host_in, &c->host_out, &c->rec_stats, &c->flat_nd, &c->flat_rec, &c->flat_chunks, &c->flat_sums, &c->flat_done, &c->flat_items, &c->flat_pieces, &c->add_pieces, &c->add_scr_cnt, &c->add_scr_off, &c->add_new_cnt, &c->add_new_off, &c->add_text, &c->add_bad, &c->add_part, &c->add_scratch, &c->add_new_ops, &c->bed_keys, &c->bed_tab, &c->bed_starts, &c->bed_len, &c->bed_off, &c->bed_tiles,
+                      &c->n_ops, &c->arena_off, &c->out_off, &c->w_list, &c->b_list, &c->b_list1, &c->arena, &c->info, &c->synth_sizes, &c->rec_plan, &c->ops_mirror, &c->seq_blob, &c->seq_table, &c->seq_names, &c->seq_name_off, &c->synth4_contigs, &c->synth4_q, &c->synth4_t, &c->seq_comp, &c->seq_raw, &c->pretty_off, &c->pretty_out, &c->pretty_err, &c->host_in, &c->host_out, &c->rec_stats, &c->flat_nd, &c->flat_rec, &c->flat_chunks, &c->flat_sums, &c->flat_done, &c->flat_items, &c->flat_pieces, &c->add_pieces, &c->add_scr_cnt, &c->add_scr_off, &c->add_new_cnt, &c->add_new_off, &c->add_text, &c->add_bad, &c->add_part, &c->add_scratch, &c->add_new_ops, &c->view_sums, &c->bed_keys, &c->bed_tab, &c->bed_starts, &c->bed_len, &c->bed_off, &c->bed_tiles,
                       &c->rec_qseq, &c->rec_tseq, &c->tile_keys, &c->tile_order, &c->tile_rank, &c->tile_coff, &c->tile_cbase,
                       &c->tile_cov, &c->tile_level, &c->tile_len, &c->tile_items, &c->tile_slots, &c->tile_parts, &c->scan_part, &c->dedupe_keys, &c->emit_order, &c->order_cnt, &c->up_table, &c->up_names};
     for (DevBuf *b : bufs)
@@ -1369,6 +1373,7 @@ static void plan_begin(paffy_hip_ctx *c, PlanKind kind, int64_t in_bytes, paffy_
     memset(&c->kp, 0, sizeof(c->kp));
     c->flat_left = -1;
     memset(c->flat_reasons, 0, sizeof(c->flat_reasons));
+    c->plan_stats_only = false;
     c->line_n = 0;
     c->bed_runs = 0;
     c->plan_seq_lookup = false;
@@ -1470,7 +1475,8 @@ enum FlatMode {
     FLAT_MODE_NONE, /* the record kernels size every record */
     FLAT_MODE_PASS, /* the flat pass (flat_kernel.h); what it leaves goes to the record kernels */
     FLAT_MODE_ADD,  /* `paffy add_mismatches` alone: the flat parse and the encoder on its pieces (flat_add_kernel.h) */
-    FLAT_MODE_REMOVE /* `paffy add_mismatches -a` alone: the flat parse and the merge of the M/=/X runs on its pieces (flat_remove_kernel.h) */
+    FLAT_MODE_REMOVE, /* `paffy add_mismatches -a` alone: the flat parse and the merge of the M/=/X runs on its pieces (flat_remove_kernel.h) */
+    FLAT_MODE_VIEW  /* `paffy view` without rows, under paffy_hip_stats_only: the flat parse and the count walk alone (flat_view_kernel.h) */
 };
 struct StageClass {
     paffy_stage stages[PAFFY_MAX_STAGES]; /* kinds without the PAFFY_NO_CHECK flag; a leading dechunk is its paf_check */
@@ -1543,6 +1549,10 @@ static int classify_stages(paffy_hip_ctx *c, const paffy_stage *stages, int32_t 
     if (n_stages == 1 && norm[0].kind == PAFFY_ADD_MISMATCHES && s.nocheck_mask == 0 && !flat_off && c->n_seqs > 0) s.flat = FLAT_MODE_ADD;
     /* `paffy add_mismatches -a` alone, with its paf_check: the same parse, the runs merged across the pieces (flat_remove_kernel.h) */
     else if (n_stages == 1 && norm[0].kind == PAFFY_REMOVE_MISMATCHES && s.nocheck_mask == 0 && !flat_off) s.flat = FLAT_MODE_REMOVE;
+    /* `paffy view` when it prints no rows: the sums of the encoded records, nothing else (flat_view_kernel.h); only for a caller that
+       has said so -- without the setting [ADD, STATS] leaves ops and a line plan behind, and goes through the record kernels */
+    else if (c->stats_only && n_stages == 2 && norm[0].kind == PAFFY_ADD_MISMATCHES && norm[1].kind == PAFFY_STATS && s.nocheck_mask == 0 && !flat_off && c->n_seqs > 0)
+        s.flat = FLAT_MODE_VIEW;
     else if (lean_or_filter && s.nocheck_mask == 0 && !flat_off) s.flat = FLAT_MODE_PASS;
     /* the first instantiation that knows every stage kind: the lean kinds; them and add_mismatches (the encoder wants the registers); them
        with filter / trim -f / stats / check; no stage of the kinds that came with the encoder; all */
@@ -1784,6 +1794,43 @@ static int plan_flat_remove(paffy_hip_ctx *c, uint32_t n_lines, bool *need_recor
     return 0;
 }
 
+/* [ADD_MISMATCHES, STATS] under paffy_hip_stats_only: the flat parse, then the count walk on its pieces. No scratch and no new ops, so
+   no capacity to run out of and one pass. *need_records: records were left to the record kernels (which then also reduce the sums). */
+static int plan_flat_view(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records) {
+    KParams &kp = c->kp;
+    const FlatParams fp = flat_params(c, 0u);
+    LAUNCH(c, "k_flat_parse", k_flat_parse<0u>, dim3(2048), dim3(64 * FLAT_PARSE_WAVES), 0, fp);
+    const uint32_t n_slots = c->flat_piece_slots;
+    if (ensure(c, c->add_pieces, sizeof(AddPiece) * (size_t)n_slots) || ensure(c, c->view_sums, sizeof(ViewSum) * (size_t)n_slots) ||
+        ensure(c, c->add_bad, sizeof(uint32_t) * (size_t)(n_lines + 1)))
+        return PAFFY_E_HIP;
+    ViewParams vp;
+    memset(&vp, 0, sizeof(vp));
+    AddParams &ap = vp.A;
+    ap.P = kp;
+    ap.sums = fp.sums;
+    ap.pieces = static_cast<AddPiece *>(c->add_pieces.p);
+    ap.n_piece_slots = n_slots;
+    ap.rec_bad = static_cast<uint32_t *>(c->add_bad.p);
+    ap.flat_done = static_cast<uint8_t *>(c->flat_done.p);
+    vp.vsum = static_cast<ViewSum *>(c->view_sums.p);
+    HIPCHK(c, hipMemsetAsync(c->add_pieces.p, 0xff, sizeof(AddPiece) * (size_t)n_slots, c->stream)); /* rec = FLAT_NO_CHUNK */
+    LAUNCH(c, "k_view_prep", k_view_prep, dim3((n_lines + 255) / 256), dim3(256), 0, vp);
+    LAUNCH(c, "k_view_count", k_view_count, dim3(2048), dim3(64 * ADD_WAVES), 0, vp);
+    LAUNCH(c, "k_view_final", k_view_final, dim3((n_lines + 255) / 256), dim3(256), 0, vp);
+    if (post_scans(c, n_lines)) return PAFFY_E_HIP;
+    if (fetch_info(c)) return PAFFY_E_HIP;
+    *need_records = c->h_info->flat_legacy > 0;
+    c->flat_left = c->h_info->flat_legacy;
+    kp.flat_done = static_cast<const uint8_t *>(c->flat_done.p);
+    if (!*need_records) { /* the batch's sums (the record kernels' launch chain does this when it runs) */
+        LAUNCH(c, "k_stats_reduce", k_stats_reduce, dim3(std::min<uint32_t>(512u, (n_lines + PAFFY_NT - 1) / PAFFY_NT)), dim3(PAFFY_NT), 0, kp.rec_stats, n_lines,
+               static_cast<DevInfo *>(c->info.p)->stats);
+        if (fetch_info(c)) return PAFFY_E_HIP;
+    }
+    return 0;
+}
+
 /* the flat pass: *need_records as above; *g_count = the records it left to the four-wave writers */
 static int plan_flat(paffy_hip_ctx *c, const StageClass &s, uint32_t n_lines, bool *need_records, uint32_t *g_count) {
     KParams &kp = c->kp;
@@ -1970,11 +2017,18 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
         uint32_t flat_g_count = 0;
         if (s.flat == FLAT_MODE_ADD) rc = plan_flat_add(c, n_lines, &need_records);
         else if (s.flat == FLAT_MODE_REMOVE) rc = plan_flat_remove(c, n_lines, &need_records);
+        else if (s.flat == FLAT_MODE_VIEW) rc = plan_flat_view(c, n_lines, &need_records);
         else if (s.flat == FLAT_MODE_PASS) rc = plan_flat(c, s, n_lines, &need_records, &flat_g_count);
         if (!rc && need_records) rc = plan_records(c, s, n_lines, lvl0_long, flat_g_count);
     }
     if (rc) return rc;
-    return plan_finish(c, n_lines, info);
+    rc = plan_finish(c, n_lines, info);
+    if (!rc && s.flat == FLAT_MODE_VIEW) { /* sums only: the records the record kernels took were sized there, but nothing of this plan is emitted */
+        c->plan_stats_only = true;
+        c->plan.out_bytes = info->out_bytes = 0;
+        c->plan.n_rows = info->n_rows = 0;
+    }
+    return rc;
 }
 
 } /* extern "C" */
@@ -2978,8 +3032,16 @@ int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, in
 
 #include "dedupe_parts_kernel.h"
 
+/* a plan made under paffy_hip_stats_only has sums and nothing else: what reads ops, rows or a line plan is refused */
+static bool stats_only_refuses(paffy_hip_ctx *c, const char *what) {
+    if (!c->planned || !c->plan_stats_only) return false;
+    c->last_error = std::string(what) + ": the plan was made under paffy_hip_stats_only (sums only: no ops, rows or lines were built)";
+    return true;
+}
+
 int64_t paffy_hip_plan_rows(paffy_hip_ctx *c, int64_t cap, uint32_t *record, int64_t *out_off) {
     if (!c || !record || !out_off) return PAFFY_E_ARG;
+    if (stats_only_refuses(c, "paffy_hip_plan_rows")) return PAFFY_E_STATE;
     if (!c->planned || c->plan_kind != PLAN_LINES) return PAFFY_E_STATE;
     const int64_t n = (int64_t)c->line_n;
     if (cap < n + 1) return PAFFY_E_CAPACITY;
@@ -2995,6 +3057,7 @@ int64_t paffy_hip_plan_rows(paffy_hip_ctx *c, int64_t cap, uint32_t *record, int
 int paffy_hip_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap) {
     if (!c) return PAFFY_E_ARG;
     if (!c->planned) return PAFFY_E_STATE;
+    if (stats_only_refuses(c, "paffy_hip_emit")) return PAFFY_E_STATE;
     if (c->plan.out_bytes == 0 || (c->plan_kind == PLAN_RECORDS && c->kp.n_rec == 0)) return 0;
     if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15)) return PAFFY_E_ARG;
     if (out_cap < c->plan.out_bytes) return PAFFY_E_CAPACITY;
@@ -3031,6 +3094,7 @@ int paffy_hip_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap) {
  * large output through a bounded staging buffer. *bytes = what was written. */
 int paffy_hip_emit_lines(paffy_hip_ctx *c, int64_t first, int64_t n, void *d_out, int64_t out_cap, int64_t *bytes) {
     if (!c || !bytes || first < 0 || n < 0) return PAFFY_E_ARG;
+    if (stats_only_refuses(c, "paffy_hip_emit_lines")) return PAFFY_E_STATE;
     if (!c->planned || c->plan_kind != PLAN_LINES) return PAFFY_E_STATE;
     *bytes = 0;
     if ((uint64_t)(first + n) > c->line_n) return PAFFY_E_ARG;
@@ -3458,6 +3522,7 @@ int64_t paffy_hip_plan_record_stats(paffy_hip_ctx *c, int64_t cap_records, int64
 
 int paffy_hip_plan_record_layout(paffy_hip_ctx *c, int64_t first, int64_t count, uint32_t *flags, uint32_t *klass) {
     if (!c || (count > 0 && (!flags || !klass))) return PAFFY_E_ARG;
+    if (stats_only_refuses(c, "paffy_hip_plan_record_layout")) return PAFFY_E_STATE;
     if (!c->planned || c->plan_kind != PLAN_RECORDS) return PAFFY_E_STATE;
     if (first < 0 || count < 0 || first + count > c->plan.n_records) return PAFFY_E_ARG;
     if (count == 0) return 0;
@@ -3534,6 +3599,12 @@ int paffy_hip_bed_counts(paffy_hip_ctx *c, int64_t sequence, int64_t start, int6
 }
 
 /* ---- paf_pretty_print's base-level rows (pretty_kernel.h) ---- */
+int paffy_hip_stats_only(paffy_hip_ctx *c, int on) {
+    if (!c) return PAFFY_E_ARG;
+    c->stats_only = on != 0;
+    return 0;
+}
+
 int paffy_hip_keep_raw_sequences(paffy_hip_ctx *c, int on) {
     if (!c) return PAFFY_E_ARG;
     c->keep_raw = on != 0;
@@ -3541,6 +3612,7 @@ int paffy_hip_keep_raw_sequences(paffy_hip_ctx *c, int on) {
 }
 
 static int pretty_params(paffy_hip_ctx *c, int64_t first, int64_t count, PrettyParams *pp) {
+    if (stats_only_refuses(c, "alignment rows")) return PAFFY_E_STATE;
     if (!c->planned || c->plan_kind != PLAN_RECORDS) return PAFFY_E_STATE;
     if (first < 0 || count < 0 || first + count > c->plan.n_records) return PAFFY_E_ARG;
     if (c->n_seqs <= 0 || !c->seq_raw.p) {

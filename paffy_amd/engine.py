@@ -201,6 +201,7 @@ def lib():
         L.paffy_hip_fasta_index_headers.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64)]
         L.paffy_hip_fasta_seen.argtypes = [vp, vp, i64, C.c_int, C.POINTER(C.c_uint8)]
         L.paffy_hip_keep_raw_sequences.argtypes = [vp, C.c_int]
+        L.paffy_hip_stats_only.argtypes = [vp, C.c_int]
         L.paffy_hip_plan_record_stats.restype = i64
         L.paffy_hip_plan_record_stats.argtypes = [vp, i64, C.POINTER(i64)]
         L.paffy_hip_plan_record_layout.argtypes = [vp, i64, i64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -723,6 +724,12 @@ class Engine:
             self._check(int(got), "paffy_hip_plan_record_stats")
         return [tuple(out[6 * i:6 * i + 6]) for i in range(got)]
 
+    def stats_only(self, on=True):
+        """Sums only (`paffy view` without base-level rows): later plans of [ADD_MISMATCHES, STATS] count the matching columns on the
+        pieces of the flat pass and build nothing else -- plan_stats and record_stats answer, emit and the row getters raise. Sticky;
+        every other stage list plans as without it."""
+        self._check(lib().paffy_hip_stats_only(self._ctx, 1 if on else 0), "paffy_hip_stats_only")
+
     def record_layout(self, first, count):
         """(RecPlan flags, classes) of records [first, first + count) of the last plan: how each record's ops are kept (diagnostics, as
         flat_stats: the tests use it to know which representation was read)."""
@@ -1055,6 +1062,25 @@ def add_mismatches(data, seqs=None, remove=False):
     e = _engine()
     e.set_sequences(seqs)
     return e.run([stage(ADD_MISMATCHES)], data)[0]
+
+
+def view_stats(data, seqs):
+    """The numbers of `paffy view [fasta...]` (impl/paf_view.c) without its base-level rows: paf_stats_calc of every record as
+    add_mismatches encodes it against seqs ({header: bases}). Returns (six totals, list of six-tuples per record): matches, mismatches,
+    inserts, deletes, insert bases, delete bases."""
+    e = _engine()
+    e.set_sequences(seqs)
+    e.stats_only(True)
+    try:
+        d_in = e.to_device(data)
+        info = e.plan([stage(ADD_MISMATCHES), stage(STATS)], d_in, len(data))
+        if info.error.code:
+            L = lib()
+            raise PafError(f"record {info.error.record}: {L.paffy_hip_error_string(info.error.code).decode()}", info,
+                           L.paffy_hip_error_exit_status(info.error.code))
+        return e.plan_stats(), e.record_stats(info.n_records)
+    finally:
+        e.stats_only(False)
 
 
 def tile(data):

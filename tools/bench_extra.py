@@ -2,7 +2,8 @@
 """Side measurements for DESIGN.md (not the driver's bench contract): `tile` and single commands
 on the synthetic stream, records/s with inputs resident in HBM. dechunk / pass / upconvert: the cfg3 stream, chunk-named for the first two.
 remove_eqx: `add_mismatches -a` on the cfg4 stream as `add_mismatches` wrote it (= and X runs: the command's real input; `remove` times
-the plain M/I/D stream, where almost nothing merges)."""
+the plain M/I/D stream, where almost nothing merges). view / view_stats_only: what `paffy view` plans on the cfg4 stream -- [ADD_MISMATCHES,
+STATS] and its sums, nothing emitted -- by the default plan and under Engine.stats_only (plan-only rates, inputs resident in HBM)."""
 import argparse
 import json
 import os
@@ -32,11 +33,12 @@ def main():
     ap.add_argument("--records", type=int, default=200000)
     ap.add_argument("--mean-ops", type=int, default=2048)
     ap.add_argument("--contigs", type=int, default=24, help="contigs of the synthetic stream (chain: fewer contigs = larger groups)")
-    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "dedupe", "bed", "stats", "chain",
+    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "view", "view_stats_only", "dedupe", "bed", "stats", "chain",
                                                     "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload"])
     ap.add_argument("--genome-gb", type=float, default=3.1, help="faffy_*: bases of the synthetic genome (24 contigs)")
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
     ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome")
+    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the plan (the smallest counts)")
     ap.add_argument("--parts", type=int, default=0, help="chain: chain in parts -- this many contexts on the one GPU, taken in turn (0: the plain one-context run)")
     a = ap.parse_args()
     if a.cmd == "chain" and a.parts > 0:
@@ -50,7 +52,8 @@ def main():
     import paffy_amd
 
     eng = paffy_amd.Engine()
-    if a.cmd in ("add", "remove_eqx"):
+    view = a.cmd in ("view", "view_stats_only")
+    if a.cmd in ("add", "remove_eqx") or view:
         # cfg4: 24 + 24 contigs of 50-250 Mb generated on the device, records on homologous bases (2 % substitutions)
         t0 = time.perf_counter()
         if os.environ.get("PAFFY_X_SMALL_GENOME"):  # experiment: genomes small enough to stay in the caches
@@ -95,8 +98,18 @@ def main():
     kinds["upconvert"] = paffy_amd.UPCONVERT
     res = []
     eng.profile(True)
-    for rep in range(3):
+    if a.cmd == "view_stats_only":
+        eng.stats_only(True)
+    sums = None
+    for rep in range(a.repeats):
         t0 = time.perf_counter()
+        if view:  # the plan and its sums; nothing is emitted (the plan synchronises on its own)
+            info = eng.plan([paffy_amd.stage(paffy_amd.ADD_MISMATCHES), paffy_amd.stage(paffy_amd.STATS)], buf, nbytes)
+            sums = eng.plan_stats()
+            dt = time.perf_counter() - t0
+            assert info.error.code == 0
+            res.append(dt)
+            continue
         if a.cmd == "bed":
             opts = paffy_amd.engine.BedOpts(0, 0, 0, 1, 1)  # -n: both sides of every record
             info = paffy_amd.engine.PlanInfo()
@@ -122,7 +135,9 @@ def main():
         res.append(dt)
     dt = min(res)
     prof = {k: round(v[0] / max(1, v[1]), 3) for k, v in eng.profile_read().items()}
-    extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx") else {}
+    extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx") or view else {}
+    if view:
+        extra["sums"] = list(sums)
     print(json.dumps({**extra, "cmd": a.cmd, "records": a.records, "mean_ops": a.mean_ops, "in_bytes": nbytes, "out_bytes": int(info.out_bytes),
                       "seconds": round(dt, 4), "repeats": [round(x, 4) for x in res], "records_per_s": round(a.records / dt, 1),
                       "GBps": round((nbytes + info.out_bytes) / dt / 1e9, 1), "kernel_ms": prof}))
