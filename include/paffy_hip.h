@@ -234,6 +234,39 @@ int paffy_hip_dedupe_reset(paffy_hip_ctx *ctx);
 #define PAFFY_DEDUPE_KEEP_ALL 2
 
 /*
+ * `paffy split_file [-q] [-m min_length]` (impl/paf_split_file.c:142-170): the lines of a batch grouped by output file.
+ *   split_begin: starts a run -- the contig is the query (by_query) or the target, min_length as -m -- and forgets the files of an
+ *                earlier run. PAFFY_SPLIT_NARROW_SALT0 (environment, read here; anything but empty or "0") cuts the first name hash
+ *                to two bits, so that a test gets the regrouping of colliding names to run.
+ *   split_plan:  the normalised lines of paffy_hip_dedupe_plan(.., PAFFY_DEDUPE_KEEP_ALL, ..) -- every record in front of the first one
+ *                that fails, which info->error reports as there -- regrouped: a group is a contig name with its "small" bit
+ *                (min_length > 0 and the contig length on the record's own line < min_length), groups come in the order of their first
+ *                record, lines inside a group keep input order. Names are grouped by a salted 64-bit hash and checked byte for byte; names
+ *                that collide under eight salts: PAFFY_E_UNSUPPORTED. The file of every group is decided here, once per distinct (name,
+ *                small bit) of the batch: a name's own file, or the current small_<k> file, which a new small contig joins unless there
+ *                is none or its length would take the file's contig lengths past min_length. Groups of the batch that share a small_<k>
+ *                file are merged, their lines in input order as the reference writes them. Followed by paffy_hip_emit (or _emit_lines,
+ *                _plan_rows): every file's lines are one stretch of the output. Without a split_begin: PAFFY_E_STATE.
+ *   split_groups: the stretches of the plan in output order, one per file that gets lines of the batch, in the order of the files' first
+ *                records (cap smaller than their number: PAFFY_E_CAPACITY). file: dense id in opening order over the run; new_file: the
+ *                batch opens it (open files in this order to open them in the reference's order); first_record: the batch's record behind
+ *                the stretch's first line. Returns their number; PAFFY_E_STATE unless the last plan is a split plan.
+ *   split_file_name: the file's name without the caller's prefix and ".paf" -- the contig name with '/' replaced by '_', or small_<k> --
+ *                NUL-terminated into buf. Returns its length (cap <= length: PAFFY_E_CAPACITY, nothing written).
+ *   split_file_count: files opened by the run so far. split_salt: the salt the last plan's grouping passed its byte check with.
+ */
+typedef struct {
+    int64_t file, out_off, bytes, lines, first_record;
+    int32_t new_file, is_small;
+} paffy_split_group;
+int paffy_hip_split_begin(paffy_hip_ctx *ctx, int by_query, int64_t min_length);
+int paffy_hip_split_plan(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len, paffy_plan_info *info);
+int64_t paffy_hip_split_groups(paffy_hip_ctx *ctx, int64_t cap, paffy_split_group *groups);
+int64_t paffy_hip_split_file_name(paffy_hip_ctx *ctx, int64_t file, char *buf, int64_t cap);
+int64_t paffy_hip_split_file_count(paffy_hip_ctx *ctx);
+int paffy_hip_split_salt(paffy_hip_ctx *ctx);
+
+/*
  * Dedupe in parts: `paffy dedupe [-a]` sharded by KEY OWNER. "First seen wins" is a decision per class of records -- a class
  * is a key (the 128-bit hash of paffy_hip_dedupe_plan), with check_inverse a key and its swapped key, named by the smaller of the two --
  * so it needs a class's records in one place, not the input. A part is a context that holds any share of the records, each with a global

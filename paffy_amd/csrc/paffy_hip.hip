@@ -1080,6 +1080,7 @@ struct paffy_hip_ctx {
     int dd_part_stage = 0;
     bool dd_part_failed = false;
     struct DedupeParts *dd_parts = nullptr; /* the round's entry map and verdicts; the owner's memory */
+    struct SplitState *split = nullptr; /* `paffy split_file` (split_host.h): grouping scratch and the files of the run */
     DevBuf scan_part, emit_order, order_cnt, tile_keys, tile_order, tile_rank, tile_coff, tile_cbase, tile_cov, tile_level, tile_len, tile_items, tile_slots, tile_parts;
     bool keep_raw = false;    /* paffy_hip_keep_raw_sequences: seq_raw holds the bases as loaded (paf_pretty_print shows their case) */
     bool plan_seq_lookup = false; /* rec_qseq / rec_tseq belong to the current plan */
@@ -1133,6 +1134,7 @@ struct paffy_hip_ctx {
     int64_t flat_left = -1, flat_reasons[16] = {0}; /* paffy_hip_flat_stats */
     bool stats_only = false;      /* paffy_hip_stats_only: the caller will only ask a plan for its sums */
     bool plan_stats_only = false; /* the last plan took FLAT_MODE_VIEW: it has sums, no ops and no line plan */
+    bool plan_split = false;      /* the last plan is paffy_hip_split_plan's: a line plan with a group table (paffy_hip_split_groups) */
     DevBuf view_sums;             /* flat_view_kernel.h: six sums per piece slot */
     uint32_t flat_chunk_slots = 0;
     bool lvl0_long_ok = false, lvl0_long_off = false; /* the longer first store level: shown safe by the batch before / overflowed once */
@@ -1307,6 +1309,7 @@ static void stream_detach(struct paffy_hip_stream *s);
 static void cov_free(paffy_hip_ctx *c); /* coverage_host.h state */
 static void dedupe_free(paffy_hip_ctx *c); /* dedupe_host.h state */
 static void dedupe_parts_free(paffy_hip_ctx *c); /* dedupe_parts_kernel.h state */
+static void split_free(paffy_hip_ctx *c); /* split_host.h state */
 static void index_drop(paffy_hip_ctx *c, const void *d_in);
 static void index_drop_all(paffy_hip_ctx *c);
 static void chain_free(paffy_hip_ctx *c);
@@ -1338,6 +1341,7 @@ void paffy_hip_destroy(paffy_hip_ctx *c) {
         if (b->p) (void)hipFree(b->p);
     dedupe_free(c);
     dedupe_parts_free(c);
+    split_free(c);
     (void)paffy_hip_stream_trim(c);
     delete c->bed_params;
     if (c->h_info) (void)hipHostFree(c->h_info);
@@ -1374,6 +1378,7 @@ static void plan_begin(paffy_hip_ctx *c, PlanKind kind, int64_t in_bytes, paffy_
     c->flat_left = -1;
     memset(c->flat_reasons, 0, sizeof(c->flat_reasons));
     c->plan_stats_only = false;
+    c->plan_split = false;
     c->line_n = 0;
     c->bed_runs = 0;
     c->plan_seq_lookup = false;
@@ -2978,26 +2983,18 @@ static int dedupe_plan_lines(paffy_hip_ctx *c, const uint8_t *in, uint32_t nk, p
     return 0;
 }
 
-int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int check_inverse, paffy_plan_info *info) {
-    if (!c || !info) return PAFFY_E_ARG;
-    if (in_len < 0 || in_len >= (1ll << 31) - 64 || (in_len > 0 && !d_in) || (reinterpret_cast<uintptr_t>(d_in) & 15)) return PAFFY_E_ARG;
-    plan_begin(c, PLAN_LINES, in_len, info); /* same writer as tile: header + the cigar text as it was read */
-    if (in_len == 0) {
-        c->planned = true;
-        return 0;
-    }
-    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+/* the head of a dedupe plan (plan_begin has run): index, header parse, keys, the selection and the record that ends the run. *n = the
+   batch's records, tile_order[0 .. *nk) = the records written, in input order. Shared with the plan of split_file (split_host.h). */
+static int dedupe_plan_select(paffy_hip_ctx *c, const uint8_t *in, int64_t in_len, int check_inverse, uint32_t *n_out, uint32_t *nk_out) {
     uint32_t n = 0;
+    *n_out = 0;
+    *nk_out = 0;
     {
         int rc = index_and_parse(c, in, (uint32_t)in_len, &n);
         if (rc) return rc;
     }
     c->plan.n_records = n;
-    if (n == 0) {
-        *info = c->plan;
-        c->planned = true;
-        return 0;
-    }
+    if (n == 0) return 0;
     const uint32_t grid = (n + PAFFY_NT - 1) / PAFFY_NT;
     if (ensure(c, c->dedupe_keys, sizeof(DedupeKey) * (size_t)n)) return PAFFY_E_HIP;
     if (ensure(c, c->tile_level, sizeof(int64_t) * (size_t)n)) return PAFFY_E_HIP;
@@ -3027,8 +3024,34 @@ int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, in
             c->plan.error.stage = 0;
         }
     }
+    *n_out = n;
+    *nk_out = nk;
+    return 0;
+}
+
+int paffy_hip_dedupe_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int check_inverse, paffy_plan_info *info) {
+    if (!c || !info) return PAFFY_E_ARG;
+    if (in_len < 0 || in_len >= (1ll << 31) - 64 || (in_len > 0 && !d_in) || (reinterpret_cast<uintptr_t>(d_in) & 15)) return PAFFY_E_ARG;
+    plan_begin(c, PLAN_LINES, in_len, info); /* same writer as tile: header + the cigar text as it was read */
+    if (in_len == 0) {
+        c->planned = true;
+        return 0;
+    }
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    uint32_t n = 0, nk = 0;
+    {
+        int rc = dedupe_plan_select(c, in, in_len, check_inverse, &n, &nk);
+        if (rc) return rc;
+    }
+    if (n == 0) {
+        *info = c->plan;
+        c->planned = true;
+        return 0;
+    }
     return dedupe_plan_lines(c, in, nk, info);
 }
+
+#include "split_host.h"
 
 #include "dedupe_parts_kernel.h"
 

@@ -40,6 +40,12 @@ class PlanInfo(C.Structure):
                 ("error", _Error)]
 
 
+class SplitGroup(C.Structure):
+    """paffy_split_group: one stretch of a split_file plan's output and the file it belongs to."""
+    _fields_ = [("file", C.c_int64), ("out_off", C.c_int64), ("bytes", C.c_int64), ("lines", C.c_int64), ("first_record", C.c_int64),
+                ("new_file", C.c_int32), ("is_small", C.c_int32)]
+
+
 class FastaRecord(C.Structure):
     """paffy_fasta_record: the header in the text (after '>'), the bases in the compact buffer."""
     _fields_ = [("hdr_off", C.c_int64), ("hdr_len", C.c_int64), ("seq_off", C.c_int64), ("seq_len", C.c_int64)]
@@ -161,6 +167,15 @@ def lib():
         L.paffy_hip_sync.argtypes = [vp]
         L.paffy_hip_dedupe_plan.argtypes = [vp, vp, i64, C.c_int, C.POINTER(PlanInfo)]
         L.paffy_hip_dedupe_reset.argtypes = [vp]
+        L.paffy_hip_split_begin.argtypes = [vp, C.c_int, i64]
+        L.paffy_hip_split_plan.argtypes = [vp, vp, i64, C.POINTER(PlanInfo)]
+        L.paffy_hip_split_groups.restype = i64
+        L.paffy_hip_split_groups.argtypes = [vp, i64, C.POINTER(SplitGroup)]
+        L.paffy_hip_split_file_name.restype = i64
+        L.paffy_hip_split_file_name.argtypes = [vp, i64, C.c_char_p, i64]
+        L.paffy_hip_split_file_count.restype = i64
+        L.paffy_hip_split_file_count.argtypes = [vp]
+        L.paffy_hip_split_salt.argtypes = [vp]
         L.paffy_hip_dedupe_part_keys.argtypes = [vp, vp, i64, C.c_int, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)]
         L.paffy_hip_dedupe_part_decide.argtypes = [vp, vp, i64, C.c_int, vp]
         L.paffy_hip_dedupe_part_verdicts.argtypes = [vp, vp, i64, C.POINTER(i64)]
@@ -571,6 +586,86 @@ class Engine:
             raise PafError(f"record {info.error.record}: {L.paffy_hip_error_string(info.error.code).decode()}", info,
                            L.paffy_hip_error_exit_status(info.error.code))
         return out, info
+
+    # ---- paffy split_file: the lines of a batch grouped by output file (include/paffy_hip.h) ----
+    def split_begin(self, by_query=False, min_length=0):
+        """Starts a split_file run on this context and forgets the files of an earlier one."""
+        self._check(lib().paffy_hip_split_begin(self._ctx, 1 if by_query else 0, int(min_length)), "paffy_hip_split_begin")
+
+    def split_plan(self, d_in, in_len):
+        """Plans the grouped lines of a device batch; emit follows, split_groups says which stretch of the output is whose."""
+        info = PlanInfo()
+        self._check(lib().paffy_hip_split_plan(self._ctx, C.c_void_p(d_in.data_ptr()) if in_len else None, in_len, C.byref(info)), "paffy_hip_split_plan")
+        return info
+
+    def split_groups(self):
+        """The stretches of the last split plan in output order, one per file that gets lines of the batch (SplitGroup: file, out_off, bytes,
+        lines, first_record, new_file, is_small)."""
+        L = lib()
+        cap = 256
+        while True:
+            buf = (SplitGroup * cap)()
+            n = L.paffy_hip_split_groups(self._ctx, cap, buf)
+            if n == -4:  # PAFFY_E_CAPACITY
+                cap *= 8
+                continue
+            if n < 0:
+                self._check(int(n), "paffy_hip_split_groups")
+            return list(buf[:n])
+
+    def split_file_name(self, file):
+        """Name of a file of the run without prefix and ".paf" (bytes): the contig name with '/' as '_', or small_<k>."""
+        L = lib()
+        cap = 256
+        while True:
+            buf = C.create_string_buffer(cap)
+            n = L.paffy_hip_split_file_name(self._ctx, file, buf, cap)
+            if n == -4:  # PAFFY_E_CAPACITY
+                cap *= 8
+                continue
+            if n < 0:
+                self._check(int(n), "paffy_hip_split_file_name")
+            return buf.raw[:n]
+
+    def split_salt(self):
+        """Salt of the name hash the last split plan's grouping passed its byte check with (0 unless names collided)."""
+        n = lib().paffy_hip_split_salt(self._ctx)
+        if n < 0:
+            self._check(int(n), "paffy_hip_split_salt")
+        return n
+
+    def split_file(self, data, by_query=False, min_length=0, batch_bytes=None, raise_on_error=True):
+        """paffy split_file [-q] [-m min_length] (impl/paf_split_file.c) over PAF text; returns ({file name without prefix and ".paf"
+        (str): its bytes}, in opening order, PlanInfo of the last batch). With batch_bytes the text goes to the device in pieces of at most that
+        size; the files carry on from piece to piece. A failing record ends the run behind the records in front of it."""
+        self.split_begin(by_query, min_length)
+        files, names = {}, {}
+        info = PlanInfo()
+        done = 0
+        for piece in (self.split_lines(data, batch_bytes) if batch_bytes else [data]):
+            d_in = self.to_device(piece)
+            info = self.split_plan(d_in, len(piece))
+            out = b""
+            if info.out_bytes:
+                d_out = self.alloc_out(info.out_bytes)
+                self.emit(d_out)
+                self.sync()
+                out = d_out[: info.out_bytes].cpu().numpy().tobytes()
+            for g in self.split_groups():
+                if g.new_file:
+                    names[g.file] = os.fsdecode(self.split_file_name(g.file))  # as os.listdir would name the file
+                    files.setdefault(names[g.file], [])
+                files[names[g.file]].append(out[g.out_off : g.out_off + g.bytes])
+            if info.error.code:
+                info.error.record += done  # counted over the whole text
+                break
+            done += info.n_records
+        files = {k: b"".join(v) for k, v in files.items()}
+        if info.error.code and raise_on_error:
+            L = lib()
+            raise PafError(f"record {info.error.record}: {L.paffy_hip_error_string(info.error.code).decode()}", info,
+                           L.paffy_hip_error_exit_status(info.error.code))
+        return files, info
 
     # ---- dedupe in parts: `paffy dedupe` sharded by key owner (include/paffy_hip.h; shard.dedupe_sharded drives these) ----
     def dedupe_reset(self):
@@ -1108,3 +1203,8 @@ def filter(data, **thresholds):  # noqa: A001 -- named after the reference comma
 def dedupe(data, check_inverse=False):
     """paffy dedupe [-a] (impl/paf_dedupe.c)."""
     return _engine().dedupe(data, check_inverse)[0]
+
+
+def split_file(data, by_query=False, min_length=0, batch_bytes=None):
+    """paffy split_file [-q] [-m min_length] (impl/paf_split_file.c): {file name without prefix and ".paf": bytes}, in opening order."""
+    return _engine().split_file(data, by_query, min_length, batch_bytes)[0]
