@@ -164,80 +164,65 @@ static int g_alignment_rows = 0; /* paffy view -a: the base-level rows under eve
 void host_set_alignment_rows(int on) { g_alignment_rows = on; }
 
 /*
- * paf_pretty_print per record (impl/paf.c:269-315): the stats line -- the six sums come from the GPU's PAFFY_STATS stage, the
- * fields from the GPU's parse -- and under -a the base-level rows, written by the GPU (paffy_hip_plan_alignment_rows) and fetched
- * in pieces of at most 128 MiB.
+ * paf_pretty_print per record (impl/paf.c:269-315): the stats line and, under -a, the base-level rows behind it are written by the
+ * GPU into device memory (paffy_hip_plan_view_text: the fields are the plan's own header parse, the sums its PAFFY_STATS stage) and
+ * fetched in ranges of records of at most 128 MiB of text (at least one record): one copy and one fwrite per range.
  */
-static int stats_lines(paffy_hip_ctx *ctx, const char *buf, const paffy_record *recs, int64_t n_records, int64_t record_base) {
-    int64_t *t = (int64_t *)malloc(sizeof(int64_t) * 6 * (size_t)(n_records > 0 ? n_records : 1));
-    int64_t *off = NULL;
-    char *rows = NULL;
-    int64_t rows_first = 0, rows_end = 0; /* records [rows_first, rows_end) are in `rows` */
-    int rc = paffy_hip_plan_record_stats(ctx, n_records, t) == n_records ? 0 : PAFFY_E_STATE;
-    if (!rc && g_alignment_rows) {
-        off = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n_records + 1));
-        rc = paffy_hip_plan_alignment_sizes(ctx, 0, n_records, off);
-        if (!rc) { /* sizes -> running sums */
-            int64_t at = 0;
-            for (int64_t r = 0; r < n_records; r++) {
-                int64_t b = off[r];
-                off[r] = at;
-                at += b;
-            }
-            off[n_records] = at;
+static int stats_lines(paffy_hip_ctx *ctx, int64_t n_records, int64_t record_base) {
+    if (n_records <= 0) return 0;
+    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n_records + 1));
+    char *text = NULL;
+    void *d_text = NULL;
+    int64_t cap = 0;
+    int rc = paffy_hip_plan_view_sizes(ctx, 0, n_records, g_alignment_rows, off);
+    if (!rc) { /* sizes -> running sums */
+        int64_t at = 0;
+        for (int64_t r = 0; r < n_records; r++) {
+            int64_t b = off[r];
+            off[r] = at;
+            at += b;
         }
+        off[n_records] = at;
     }
-    for (int64_t r = 0; r < n_records && !rc; r++) {
-        const paffy_record *p = &recs[r];
-        const int64_t *s = t + 6 * r; /* matches, mismatches, inserts, deletes, insert bases, delete bases */
-        fprintf(g_stats_lines, "Query:%.*s\tQ-start:%" PRIi64 "\tQ-length:%" PRIi64 "\tTarget:%.*s\tT-start:%" PRIi64 "\tT-length:%" PRIi64
-                "\tSame-strand:%i\tScore:%" PRIi64 "\tIdentity:%f\tIdentity-with-gaps%f\tAligned-bases:%" PRIi64 "\tQuery-inserts:%" PRIi64
-                "\tQuery-deletes:%" PRIi64 "\n",
-                (int)p->query_name_len, buf + p->query_name_off, p->query_start, p->query_end - p->query_start, (int)p->target_name_len,
-                buf + p->target_name_off, p->target_start, p->target_end - p->target_start, (int)p->same_strand, p->score,
-                (float)s[0] / (s[0] + s[1]), (float)s[0] / (s[0] + s[1] + s[4] + s[5]), s[0] + s[1], s[2], s[3]);
-        if (!g_alignment_rows) continue;
-        if (r >= rows_end) { /* the next piece: as many records as fit 128 MiB (at least one) */
-            rows_first = r;
-            rows_end = r + 1;
-            while (rows_end < n_records && off[rows_end + 1] - off[rows_first] <= ((int64_t)128 << 20)) rows_end++;
-            free(rows);
-            rows = (char *)malloc((size_t)(off[rows_end] - off[rows_first]) + 1);
-            paffy_error e;
-            rc = paffy_hip_plan_alignment_rows(ctx, rows_first, rows_end - rows_first, off + rows_first, rows, &e);
-            if (!rc && e.code) { /* e.record counts from the batch's first record, whichever piece it was fetched in */
-                fflush(g_stats_lines);
-                die_like_reference(&e, record_base);
+    for (int64_t first = 0, end; first < n_records && !rc; first = end) {
+        end = first + 1;
+        while (end < n_records && off[end + 1] - off[first] <= ((int64_t)128 << 20)) end++;
+        const int64_t bytes = off[end] - off[first];
+        if (bytes > cap) { /* the first range is the longest but for a record of more than 128 MiB */
+            free(text);
+            if (d_text) paffy_hip_free(d_text);
+            d_text = NULL;
+            cap = bytes;
+            text = (char *)malloc((size_t)cap + 1);
+            if (!text || paffy_hip_malloc(&d_text, cap) != 0) {
+                rc = PAFFY_E_HIP;
+                break;
             }
-            if (rc) break;
         }
-        fwrite(rows + (off[r] - off[rows_first]), 1, (size_t)(off[r + 1] - off[r]), g_stats_lines);
+        paffy_error e;
+        rc = paffy_hip_plan_view_text(ctx, first, end - first, g_alignment_rows, off + first, d_text, cap, &e);
+        if (!rc && e.code) { /* e.record counts from the batch's first record, whichever range it was fetched in */
+            /* rows that reach outside a sequence (only = / X / I / D ops: the mismatch encoder looked at no base of the record). What
+               has gone out by then has always been the ranges before this one and the stats line of this one's first record */
+            int64_t line = 0;
+            if (paffy_hip_plan_view_sizes(ctx, first, 1, 0, &line) == 0 && line <= bytes && paffy_hip_memcpy_d2h(text, d_text, line) == 0)
+                fwrite(text, 1, (size_t)line, g_stats_lines);
+            fflush(g_stats_lines);
+            die_like_reference(&e, record_base);
+        }
+        if (!rc) rc = paffy_hip_memcpy_d2h(text, d_text, bytes);
+        if (!rc && fwrite(text, 1, (size_t)bytes, g_stats_lines) != (size_t)bytes) rc = PAFFY_E_HIP;
     }
-    free(rows);
+    if (d_text) paffy_hip_free(d_text);
+    free(text);
     free(off);
-    free(t);
     return rc;
 }
 
 static int stats_chunk(paffy_hip_ctx *ctx, const paffy_stage *stages, int n_stages, const char *buf, int64_t len, int64_t record_base,
                        paffy_plan_info *info) {
-    /* the fields of the stats lines first: parsing is a plan of its own and the stage plan must be the current one afterwards */
-    paffy_record *recs = NULL;
-    uint64_t *ops = NULL;
-    int64_t n_ops = 0;
-    if (g_stats_lines) {
-        int rc0 = paffy_hip_parse_host(ctx, buf, len, &recs, &ops, &n_ops, info);
-        free(ops);
-        if (rc0 || info->error.code) {
-            free(recs);
-            return rc0;
-        }
-    }
     void *d_in = NULL;
-    if (paffy_hip_malloc(&d_in, len + 64) != 0) {
-        free(recs);
-        return PAFFY_E_HIP;
-    }
+    if (paffy_hip_malloc(&d_in, len + 64) != 0) return PAFFY_E_HIP;
     int rc = paffy_hip_memcpy_h2d(d_in, buf, len);
     if (!rc) rc = paffy_hip_plan(ctx, stages, n_stages, d_in, len, info);
     int64_t sums[6];
@@ -245,10 +230,16 @@ static int stats_chunk(paffy_hip_ctx *ctx, const paffy_stage *stages, int n_stag
     if (!rc && info->error.code == 0) {
         for (int k = 0; k < 6; k++) g_stats[k] += sums[k];
         g_stats_records += info->n_records;
-        if (g_stats_lines) rc = stats_lines(ctx, buf, recs, info->n_records, record_base);
+        if (g_stats_lines) rc = stats_lines(ctx, info->n_records, record_base);
+    } else if (!rc && g_stats_lines) {
+        /* a chunk with a failing record writes nothing. What is reported is the first line that does not parse, if there is one,
+           before the first record the stages fail on -- the order in which the lines' fields used to be read (a parse of the whole
+           chunk) and the stages run: a plan of the parse alone tells */
+        const paffy_stage pass = {PAFFY_PASS, 0.0f, 0.0f};
+        paffy_plan_info parsed;
+        if (paffy_hip_plan(ctx, &pass, 1, d_in, len, &parsed) == 0 && parsed.error.code) *info = parsed;
     }
     paffy_hip_free(d_in);
-    free(recs);
     return rc;
 }
 

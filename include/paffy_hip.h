@@ -493,13 +493,14 @@ int paffy_hip_flat_stats(paffy_hip_ctx *ctx, int64_t *left, int64_t reasons[16])
  * `paffy view` (paf_pretty_print, impl/paf.c:269-281). Returns n_records or a negative error. */
 int64_t paffy_hip_plan_record_stats(paffy_hip_ctx *ctx, int64_t cap_records, int64_t *sums);
 /*
- * Sums only: the caller declares that all it will ask of a plan is paffy_hip_plan_stats and paffy_hip_plan_record_stats (`paffy view`
- * when it prints no base-level rows). Sticky, like paffy_hip_keep_raw_sequences. It takes effect for the stage list that is exactly
+ * Sums only: the caller declares that all it will ask of a plan is paffy_hip_plan_stats, paffy_hip_plan_record_stats and, with
+ * with_rows = 0, paffy_hip_plan_view_sizes and paffy_hip_plan_view_text (`paffy view` when it prints no base-level rows: its stats
+ * lines need the header fields and the sums, which such a plan has). Sticky, like paffy_hip_keep_raw_sequences. It takes effect for the stage list that is exactly
  * [PAFFY_ADD_MISMATCHES, PAFFY_STATS], both with their paf_check, with sequences loaded and PAFFY_NO_FLAT unset: the plan then counts
  * the matching columns of every M op on the pieces of the flat pass (paffy_amd/csrc/flat_view_kernel.h) and builds neither the = / X ops
  * nor a line: info.n_records and info.error are as ever, info.out_bytes and info.n_rows are 0, the sums are those of the default plan,
- * and paffy_hip_emit, paffy_hip_emit_lines, paffy_hip_plan_rows, paffy_hip_plan_record_layout, paffy_hip_plan_alignment_sizes and
- * paffy_hip_plan_alignment_rows return PAFFY_E_STATE (paffy_hip_last_error names this setting). paffy_hip_flat_stats tells how many
+ * and paffy_hip_emit, paffy_hip_emit_lines, paffy_hip_plan_rows, paffy_hip_plan_record_layout, paffy_hip_plan_alignment_sizes,
+ * paffy_hip_plan_alignment_rows and the two paffy_hip_plan_view_* calls with with_rows != 0 return PAFFY_E_STATE (paffy_hip_last_error names this setting). paffy_hip_flat_stats tells how many
  * records went through the record kernels all the same. Every other stage list plans exactly as without the setting.
  */
 int paffy_hip_stats_only(paffy_hip_ctx *ctx, int on);
@@ -529,6 +530,26 @@ int paffy_hip_plan_record_layout(paffy_hip_ctx *ctx, int64_t first, int64_t coun
 int paffy_hip_keep_raw_sequences(paffy_hip_ctx *ctx, int on);
 int paffy_hip_plan_alignment_sizes(paffy_hip_ctx *ctx, int64_t first, int64_t count, int64_t *h_bytes);
 int paffy_hip_plan_alignment_rows(paffy_hip_ctx *ctx, int64_t first, int64_t count, const int64_t *h_off, char *h_out, paffy_error *err);
+
+/*
+ * What `paffy view` writes per record, as text in device memory: for records [first, first + count) of the planned batch the stats
+ * line of paf_pretty_print (impl/paf.c:269-281) and, with with_rows != 0, the record's base-level rows right behind it (the block of
+ * paffy_hip_plan_alignment_rows). The line's fields are those of the record as it was read (the header parse of the plan; the stage
+ * list of `view`, [PAFFY_ADD_MISMATCHES, PAFFY_STATS], changes none of them), its six sums those of the plan's PAFFY_STATS stage, its
+ * two %f fields the reference's float quotients as glibc prints them ("-nan" for a record without aligned bases). Nothing is parsed
+ * again and nothing but the sizes comes to the host.
+ * _sizes gives the bytes of each record's block. _text writes the blocks to d_out, record first + i at d_out + h_off[i] - h_off[0]
+ * (h_off: count + 1 running sums of the sizes, so that a batch can be fetched in pieces), and returns when they are written; no byte
+ * outside [d_out, d_out + h_off[count] - h_off[0]) is touched. Offsets that are not the running sums of the sizes: PAFFY_E_ARG.
+ * PAFFY_E_ARG also when first + count exceeds the batch or h_off[count] - h_off[0] > out_cap. PAFFY_E_STATE, with a
+ * paffy_hip_last_error that names the reason, when the last plan is not a record plan, had no PAFFY_STATS stage or reported a failing
+ * record, and with with_rows != 0 also without raw sequences (paffy_hip_keep_raw_sequences) and for a plan made under
+ * paffy_hip_stats_only. The rows' failures (a missing or short sequence) are reported in *err exactly as paffy_hip_plan_alignment_rows
+ * reports them. The batch text must still be in place: the names are copied from it.
+ */
+int paffy_hip_plan_view_sizes(paffy_hip_ctx *ctx, int64_t first, int64_t count, int with_rows, int64_t *h_bytes);
+int paffy_hip_plan_view_text(paffy_hip_ctx *ctx, int64_t first, int64_t count, int with_rows, const int64_t *h_off, void *d_out, int64_t out_cap,
+                             paffy_error *err);
 
 /*
  * Records as structs, for hosts that hold `Paf` objects (the per-record API of inc/paf.h:75-269, host/paf_api.c): the text is

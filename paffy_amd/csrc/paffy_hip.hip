@@ -1136,6 +1136,7 @@ struct paffy_hip_ctx {
     bool plan_stats_only = false; /* the last plan took FLAT_MODE_VIEW: it has sums, no ops and no line plan */
     bool plan_split = false;      /* the last plan is paffy_hip_split_plan's: a line plan with a group table (paffy_hip_split_groups) */
     DevBuf view_sums;             /* flat_view_kernel.h: six sums per piece slot */
+    DevBuf view_work;             /* view_line_kernel.h: sizes, row offsets and the offsets' verdict of a paffy_hip_plan_view_* call */
     uint32_t flat_chunk_slots = 0;
     bool lvl0_long_ok = false, lvl0_long_off = false; /* the longer first store level: shown safe by the batch before / overflowed once */
     /* device buffers of the two slots of a closed stream (paffy_hip_stream_close), taken again by the next paffy_hip_stream_open: a
@@ -1334,7 +1335,7 @@ void paffy_hip_destroy(paffy_hip_ctx *c) {
     c->index_pool.clear();
     if (c->one_batch.p) (void)hipFree(c->one_batch.p);
     DevBuf *bufs[] = {&c->tile_counts, &c->sep_pos, &c->nl_idx, &c->meta, &c->out_len, &c->out_rows, &c->status, &c->err_aux,
-                      &c->n_ops, &c->arena_off, &c->out_off, &c->w_list, &c->b_list, &c->b_list1, &c->arena, &c->info, &c->synth_sizes, &c->rec_plan, &c->ops_mirror, &c->seq_blob, &c->seq_table, &c->seq_names, &c->seq_name_off, &c->synth4_contigs, &c->synth4_q, &c->synth4_t, &c->seq_comp, &c->seq_raw, &c->pretty_off, &c->pretty_out, &c->pretty_err, &c->host_in, &c->host_out, &c->rec_stats, &c->flat_nd, &c->flat_rec, &c->flat_chunks, &c->flat_sums, &c->flat_done, &c->flat_items, &c->flat_pieces, &c->add_pieces, &c->add_scr_cnt, &c->add_scr_off, &c->add_new_cnt, &c->add_new_off, &c->add_text, &c->add_bad, &c->add_part, &c->add_scratch, &c->add_new_ops, &c->view_sums, &c->bed_keys, &c->bed_tab, &c->bed_starts, &c->bed_len, &c->bed_off, &c->bed_tiles,
+                      &c->n_ops, &c->arena_off, &c->out_off, &c->w_list, &c->b_list, &c->b_list1, &c->arena, &c->info, &c->synth_sizes, &c->rec_plan, &c->ops_mirror, &c->seq_blob, &c->seq_table, &c->seq_names, &c->seq_name_off, &c->synth4_contigs, &c->synth4_q, &c->synth4_t, &c->seq_comp, &c->seq_raw, &c->pretty_off, &c->pretty_out, &c->pretty_err, &c->host_in, &c->host_out, &c->rec_stats, &c->flat_nd, &c->flat_rec, &c->flat_chunks, &c->flat_sums, &c->flat_done, &c->flat_items, &c->flat_pieces, &c->add_pieces, &c->add_scr_cnt, &c->add_scr_off, &c->add_new_cnt, &c->add_new_off, &c->add_text, &c->add_bad, &c->add_part, &c->add_scratch, &c->add_new_ops, &c->view_sums, &c->view_work, &c->bed_keys, &c->bed_tab, &c->bed_starts, &c->bed_len, &c->bed_off, &c->bed_tiles,
                       &c->rec_qseq, &c->rec_tseq, &c->tile_keys, &c->tile_order, &c->tile_rank, &c->tile_coff, &c->tile_cbase,
                       &c->tile_cov, &c->tile_level, &c->tile_len, &c->tile_items, &c->tile_slots, &c->tile_parts, &c->scan_part, &c->dedupe_keys, &c->emit_order, &c->order_cnt, &c->up_table, &c->up_names};
     for (DevBuf *b : bufs)
@@ -2042,6 +2043,7 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
 #include "dedupe_host.h"
 #include "chain_host.h"
 #include "pretty_kernel.h"
+#include "view_line_kernel.h"
 #include "fasta_host.h"
 
 static CovState &cov_state(paffy_hip_ctx *c) {
@@ -3701,6 +3703,110 @@ int paffy_hip_plan_alignment_rows(paffy_hip_ctx *c, int64_t first, int64_t count
     unsigned long long e = 0;
     HIPCHK(c, hipMemcpyAsync(&e, c->pretty_err.p, sizeof(e), hipMemcpyDeviceToHost, c->stream));
     if (total > 0) HIPCHK(c, hipMemcpyAsync(h_out, c->pretty_out.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (e != ~0ull) {
+        err->code = (int32_t)(e & 0xff);
+        err->record = (int64_t)(e >> 8);
+        err->stage = -1;
+    }
+    return 0;
+}
+
+/* ---- paf_pretty_print's text in device memory: the stats line (view_line_kernel.h), with the rows behind it on demand ---- */
+static int view_params(paffy_hip_ctx *c, const char *what, int64_t first, int64_t count, int with_rows, ViewLineParams *vp, PrettyParams *pp) {
+    if (!c->planned || c->plan_kind != PLAN_RECORDS) {
+        c->last_error = std::string(what) + ": the last plan is not a record plan (paffy_hip_plan)";
+        return PAFFY_E_STATE;
+    }
+    if (first < 0 || count < 0 || first + count > c->plan.n_records) return PAFFY_E_ARG;
+    if (c->plan.n_records > 0 && !c->kp.rec_stats) {
+        c->last_error = std::string(what) + ": the plan has no PAFFY_STATS stage";
+        return PAFFY_E_STATE;
+    }
+    if (c->plan.error.code) {
+        c->last_error = std::string(what) + ": the plan reported a failing record";
+        return PAFFY_E_STATE;
+    }
+    if (with_rows) { /* as for paffy_hip_plan_alignment_*: raw sequences, and a plan that kept its ops */
+        int rc = pretty_params(c, first, count, pp);
+        if (rc) return rc;
+    }
+    memset(vp, 0, sizeof(*vp));
+    vp->in = c->kp.in;
+    vp->meta = c->kp.meta;
+    vp->rec_stats = c->kp.rec_stats;
+    vp->first = (uint32_t)first;
+    vp->count = (uint32_t)count;
+    return 0;
+}
+
+/* view_work: count sizes (the rows' bytes, then the blocks'), count + 1 row offsets, the verdict on the offsets */
+static int view_work(paffy_hip_ctx *c, int64_t count, int64_t **bytes, int64_t **rows_off, uint32_t **bad) {
+    if (ensure(c, c->view_work, sizeof(int64_t) * (size_t)(2 * count + 2))) return PAFFY_E_HIP;
+    *bytes = static_cast<int64_t *>(c->view_work.p);
+    *rows_off = *bytes + count;
+    *bad = reinterpret_cast<uint32_t *>(*rows_off + count + 1);
+    return 0;
+}
+
+int paffy_hip_plan_view_sizes(paffy_hip_ctx *c, int64_t first, int64_t count, int with_rows, int64_t *h_bytes) {
+    if (!c || (count > 0 && !h_bytes)) return PAFFY_E_ARG;
+    ViewLineParams vp;
+    PrettyParams pp;
+    int rc = view_params(c, "paffy_hip_plan_view_sizes", first, count, with_rows, &vp, &pp);
+    if (rc || count == 0) return rc;
+    int64_t *bytes, *rows_off;
+    uint32_t *bad;
+    if (view_work(c, count, &bytes, &rows_off, &bad)) return PAFFY_E_HIP;
+    if (with_rows) LAUNCH(c, "k_pretty_size", k_pretty_size, dim3((unsigned)count), dim3(PRETTY_NT), 0, pp, bytes);
+    LAUNCH(c, "k_view_line_size", k_view_line_size, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, vp, bytes, with_rows ? 1 : 0);
+    HIPCHK(c, hipMemcpyAsync(h_bytes, bytes, sizeof(int64_t) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int paffy_hip_plan_view_text(paffy_hip_ctx *c, int64_t first, int64_t count, int with_rows, const int64_t *h_off, void *d_out, int64_t out_cap,
+                             paffy_error *err) {
+    if (!c || !err || out_cap < 0 || (count > 0 && !h_off)) return PAFFY_E_ARG;
+    memset(err, 0, sizeof(*err));
+    ViewLineParams vp;
+    PrettyParams pp;
+    int rc = view_params(c, "paffy_hip_plan_view_text", first, count, with_rows, &vp, &pp);
+    if (rc || count == 0) return rc;
+    const int64_t total = h_off[count] - h_off[0];
+    if (total < 0 || total > out_cap || !d_out) return PAFFY_E_ARG;
+    int64_t *bytes, *rows_off;
+    uint32_t *bad;
+    if (view_work(c, count, &bytes, &rows_off, &bad)) return PAFFY_E_HIP;
+    if (ensure(c, c->pretty_off, sizeof(int64_t) * (size_t)(count + 1))) return PAFFY_E_HIP;
+    if (ensure(c, c->pretty_err, sizeof(unsigned long long))) return PAFFY_E_HIP;
+    std::vector<int64_t> off((size_t)count + 1);
+    for (int64_t i = 0; i <= count; i++) off[(size_t)i] = h_off[i] - h_off[0];
+    HIPCHK(c, hipMemcpyAsync(c->pretty_off.p, off.data(), sizeof(int64_t) * (size_t)(count + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
+    if (with_rows) LAUNCH(c, "k_pretty_size", k_pretty_size, dim3((unsigned)count), dim3(PRETTY_NT), 0, pp, bytes);
+    vp.off = static_cast<const int64_t *>(c->pretty_off.p);
+    vp.rows_bytes = with_rows ? bytes : nullptr;
+    vp.rows_off = with_rows ? rows_off : nullptr;
+    vp.out = static_cast<uint8_t *>(d_out);
+    vp.out_cap = total;
+    vp.bad = bad;
+    LAUNCH(c, "k_view_line_emit", k_view_line_emit, dim3((unsigned)((count + VIEW_LINE_WAVES - 1) / VIEW_LINE_WAVES)), dim3(64 * VIEW_LINE_WAVES), 0, vp);
+    uint32_t h_bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* `off` is a local; the rows are written only where the lines' offsets held */
+    if (h_bad) {
+        c->last_error = "paffy_hip_plan_view_text: the offsets are not the running sums of paffy_hip_plan_view_sizes";
+        return PAFFY_E_ARG;
+    }
+    if (!with_rows) return 0;
+    HIPCHK(c, hipMemsetAsync(c->pretty_err.p, 0xff, sizeof(unsigned long long), c->stream));
+    pp.row_off = rows_off;
+    pp.out = static_cast<uint8_t *>(d_out);
+    pp.err = static_cast<unsigned long long *>(c->pretty_err.p);
+    LAUNCH(c, "k_pretty_rows", k_pretty_rows, dim3((unsigned)count), dim3(PRETTY_NT), 0, pp);
+    unsigned long long e = 0;
+    HIPCHK(c, hipMemcpyAsync(&e, c->pretty_err.p, sizeof(e), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (e != ~0ull) {
         err->code = (int32_t)(e & 0xff);

@@ -222,6 +222,8 @@ def lib():
         L.paffy_hip_plan_record_layout.argtypes = [vp, i64, i64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.paffy_hip_plan_alignment_sizes.argtypes = [vp, i64, i64, C.POINTER(i64)]
         L.paffy_hip_plan_alignment_rows.argtypes = [vp, i64, i64, C.POINTER(i64), C.c_void_p, C.POINTER(_Error)]
+        L.paffy_hip_plan_view_sizes.argtypes = [vp, i64, i64, C.c_int, C.POINTER(i64)]
+        L.paffy_hip_plan_view_text.argtypes = [vp, i64, i64, C.c_int, C.POINTER(i64), vp, i64, C.POINTER(_Error)]
         _lib = L
     return _lib
 
@@ -857,6 +859,40 @@ class Engine:
         self._check(lib().paffy_hip_plan_alignment_rows(self._ctx, first, count, off, C.cast(buf, C.c_void_p), C.byref(err)), "paffy_hip_plan_alignment_rows")
         return bytes(buf[: total + guard]), ((err.code, err.record) if err.code else None)
 
+    def view_sizes(self, first, count, with_rows=False):
+        """Bytes of what `paffy view` writes for each of records [first, first + count) of the last plan (a STATS stage in it): the stats
+        line of paf_pretty_print and, with_rows, the base-level rows behind it."""
+        out = (C.c_int64 * max(1, count))()
+        self._check(lib().paffy_hip_plan_view_sizes(self._ctx, first, count, 1 if with_rows else 0, out), "paffy_hip_plan_view_sizes")
+        return list(out[:count])
+
+    def view_text(self, first, count, with_rows=False, offsets=None, guard=0, out_cap=None):
+        """That text, written on the device (paffy_hip_plan_view_text) and copied back: bytes. offsets: count + 1 running sums of the sizes
+        (default: built from view_sizes); only their differences count. guard: the destination lies between that many bytes of 0xA5 on
+        either side, and the call asserts that they are intact afterwards. out_cap: the capacity the library is told (default: the
+        text's bytes). A failing record of the rows raises PafError with the record's index in the planned batch."""
+        t = self.torch
+        if offsets is None:
+            offsets = [0]
+            for b in self.view_sizes(first, count, with_rows):
+                offsets.append(offsets[-1] + b)
+        if len(offsets) != count + 1:
+            raise ValueError("count + 1 offsets")
+        off = (C.c_int64 * (count + 1))(*offsets)
+        total = max(0, offsets[count] - offsets[0])
+        lead = (guard + 15) // 16 * 16  # the destination itself need not be aligned; its front guard ends right at it
+        buf = t.full((lead + total + guard + 16,), 0xA5, dtype=t.uint8, device=self.device)
+        err = _Error()
+        rc = lib().paffy_hip_plan_view_text(self._ctx, first, count, 1 if with_rows else 0, off, C.c_void_p(buf.data_ptr() + lead),
+                                            total if out_cap is None else out_cap, C.byref(err))
+        self._check(rc, "paffy_hip_plan_view_text")
+        host = buf.cpu().numpy().tobytes()
+        assert host[:lead] == b"\xa5" * lead and host[lead + total:] == b"\xa5" * (guard + 16), "paffy_hip_plan_view_text wrote outside its destination"
+        if err.code:
+            L = lib()
+            raise PafError(f"record {err.record}: {L.paffy_hip_error_string(err.code).decode()}", err, L.paffy_hip_error_exit_status(err.code))
+        return host[lead:lead + total]
+
     def synth4_setup(self, seed, mean_ops, n_contigs=24, tlen_min=50_000_000, tlen_span=200_000_000, genomes=True):
         """cfg4 workload: master alignments of n_contigs contig pairs and, with `genomes`, both genomes
         written into the sequence store of this engine (what set_sequences would hold)."""
@@ -1176,6 +1212,42 @@ def view_stats(data, seqs):
         return e.plan_stats(), e.record_stats(info.n_records)
     finally:
         e.stats_only(False)
+
+
+def view(data, seqs, include_alignment=False, per_alignment=True, aggregate=False):
+    """What `paffy view [fasta...] [-a] [-t] [-s]` (impl/paf_view.c) writes to its output for PAF text `data` and seqs ({header: bases}):
+    per record the stats line of paf_pretty_print (with include_alignment the base-level rows behind it) unless per_alignment is off,
+    then with `aggregate` the totals' line. All of the per-record text is written on the GPU (Engine.view_text); the plans are sums-only
+    exactly when the CLI's are: whenever no rows are printed."""
+    import struct
+
+    e = _engine()
+    rows = bool(include_alignment and per_alignment)
+    e.keep_raw_sequences(bool(include_alignment))
+    e.set_sequences(seqs)
+    e.stats_only(not rows)
+    try:
+        d_in = e.to_device(data)
+        info = e.plan([stage(ADD_MISMATCHES), stage(STATS)], d_in, len(data))
+        if info.error.code:
+            L = lib()
+            raise PafError(f"record {info.error.record}: {L.paffy_hip_error_string(info.error.code).decode()}", info,
+                           L.paffy_hip_error_exit_status(info.error.code))
+        out = e.view_text(0, info.n_records, rows) if per_alignment else b""
+        if aggregate:
+            def f32(x):
+                return struct.unpack("<f", struct.pack("<f", x))[0]
+
+            def ratio(a, b):  # (float)a / b: a float division, "-nan" for 0.0f / 0.0f as x86-64 glibc prints it
+                return "-nan" if b == 0 else "%f" % f32(f32(a) / f32(b))
+
+            m, x, qi, qd, qib, qdb = e.plan_stats()
+            out += ("Total-alignments:%d\tAvg-Identity:%s\tAvg-Identity-with-gaps:%s\tAligned-bases:%d\tAligned-bases-with-gaps:%d\tQuery-inserts:%d\tQuery-deletes:%d\n"
+                    % (info.n_records, ratio(m, m + x), ratio(m, m + x + qib + qdb), m + x, m + x + qib + qdb, qi, qd)).encode()
+        return out
+    finally:
+        e.stats_only(False)
+        e.keep_raw_sequences(False)
 
 
 def tile(data):

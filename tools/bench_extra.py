@@ -3,7 +3,9 @@
 on the synthetic stream, records/s with inputs resident in HBM. dechunk / pass / upconvert: the cfg3 stream, chunk-named for the first two.
 remove_eqx: `add_mismatches -a` on the cfg4 stream as `add_mismatches` wrote it (= and X runs: the command's real input; `remove` times
 the plain M/I/D stream, where almost nothing merges). view / view_stats_only: what `paffy view` plans on the cfg4 stream -- [ADD_MISMATCHES,
-STATS] and its sums, nothing emitted -- by the default plan and under Engine.stats_only (plan-only rates, inputs resident in HBM)."""
+STATS] and its sums, nothing emitted -- by the default plan and under Engine.stats_only (plan-only rates, inputs resident in HBM).
+view_lines: the sums-only plan, then the per-record stats lines of `paffy view` written into device memory (paffy_hip_plan_view_sizes /
+_view_text, view_line_kernel.h): plan + sizes + text, everything resident."""
 import argparse
 import json
 import os
@@ -33,7 +35,7 @@ def main():
     ap.add_argument("--records", type=int, default=200000)
     ap.add_argument("--mean-ops", type=int, default=2048)
     ap.add_argument("--contigs", type=int, default=24, help="contigs of the synthetic stream (chain: fewer contigs = larger groups)")
-    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "view", "view_stats_only", "dedupe", "bed", "stats", "chain",
+    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "view", "view_stats_only", "view_lines", "dedupe", "bed", "stats", "chain",
                                                     "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload"])
     ap.add_argument("--genome-gb", type=float, default=3.1, help="faffy_*: bases of the synthetic genome (24 contigs)")
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
@@ -52,7 +54,7 @@ def main():
     import paffy_amd
 
     eng = paffy_amd.Engine()
-    view = a.cmd in ("view", "view_stats_only")
+    view = a.cmd in ("view", "view_stats_only", "view_lines")
     if a.cmd in ("add", "remove_eqx") or view:
         # cfg4: 24 + 24 contigs of 50-250 Mb generated on the device, records on homologous bases (2 % substitutions)
         t0 = time.perf_counter()
@@ -98,14 +100,31 @@ def main():
     kinds["upconvert"] = paffy_amd.UPCONVERT
     res = []
     eng.profile(True)
-    if a.cmd == "view_stats_only":
+    if a.cmd in ("view_stats_only", "view_lines"):
         eng.stats_only(True)
     sums = None
+    text_out, text_bytes = None, 0
     for rep in range(a.repeats):
         t0 = time.perf_counter()
         if view:  # the plan and its sums; nothing is emitted (the plan synchronises on its own)
             info = eng.plan([paffy_amd.stage(paffy_amd.ADD_MISMATCHES), paffy_amd.stage(paffy_amd.STATS)], buf, nbytes)
             sums = eng.plan_stats()
+            if a.cmd == "view_lines":  # the lines of all records into one device buffer (allocated by the first repeat, kept)
+                import ctypes as C
+
+                import numpy as np
+
+                L, n = paffy_amd.engine.lib(), info.n_records
+                sizes = np.empty(n, dtype=np.int64)
+                assert L.paffy_hip_plan_view_sizes(eng._ctx, 0, n, 0, sizes.ctypes.data_as(C.POINTER(C.c_int64))) == 0
+                off = np.zeros(n + 1, dtype=np.int64)
+                np.cumsum(sizes, out=off[1:])
+                text_bytes = int(off[n])
+                if text_out is None or text_out.numel() < text_bytes:
+                    text_out = eng.alloc_out(text_bytes)
+                err = paffy_amd.engine._Error()
+                assert L.paffy_hip_plan_view_text(eng._ctx, 0, n, 0, off.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(text_out.data_ptr()), text_bytes, C.byref(err)) == 0
+                assert err.code == 0
             dt = time.perf_counter() - t0
             assert info.error.code == 0
             res.append(dt)
@@ -138,6 +157,8 @@ def main():
     extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx") or view else {}
     if view:
         extra["sums"] = list(sums)
+    if a.cmd == "view_lines":
+        extra["text_bytes"] = text_bytes
     print(json.dumps({**extra, "cmd": a.cmd, "records": a.records, "mean_ops": a.mean_ops, "in_bytes": nbytes, "out_bytes": int(info.out_bytes),
                       "seconds": round(dt, 4), "repeats": [round(x, 4) for x in res], "records_per_s": round(a.records / dt, 1),
                       "GBps": round((nbytes + info.out_bytes) / dt / 1e9, 1), "kernel_ms": prof}))
