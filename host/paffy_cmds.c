@@ -504,6 +504,23 @@ int paffy_view_main(int argc, char *argv[]) {
     host_get_stats(t, &n_alignments);
     host_set_stats(0);
     if (rc) return rc;
+    /* one of N workers of the launcher (host/paffy_launch.c): the six sums and the record count go to the file it names; the launcher
+       prints the aggregate line of all parts and runs the two asserts */
+    const char *sums_path = getenv("PAFFY_VIEW_SUMS");
+    if (sums_path && *sums_path) {
+        int64_t rec[7];
+        memcpy(rec, t, sizeof(t));
+        rec[6] = n_alignments;
+        FILE *sf = fopen(sums_path, "w");
+        if (!sf || fwrite(rec, sizeof(int64_t), 7, sf) != 7 || fclose(sf) != 0) {
+            fprintf(stderr, "paffy view: cannot write %s\n", sums_path);
+            return 1;
+        }
+        fflush(out);
+        if (o.in_path) fclose(in);
+        if (o.out_path) fclose(out);
+        return 0;
+    }
     if (!aggregate) memset(t, 0, sizeof(t)); /* the reference only adds the records up under -s (impl/paf_view.c:163-168) */
     if (aggregate) /* impl/paf_view.c:176-184, same float arithmetic and format */
         fprintf(out, "Total-alignments:%" PRIi64 "\tAvg-Identity:%f\tAvg-Identity-with-gaps:%f\tAligned-bases:%" PRIi64 "\tAligned-bases-with-gaps:%" PRIi64

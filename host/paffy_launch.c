@@ -10,6 +10,12 @@
  *     reads the r-th of N contiguous byte ranges of the input, cut at line ends (PAFFY_RANGE; no copy of the input), and writes a
  *     spool file; the spools are concatenated in rank order. A failing record ends the run as one process would: everything before it
  *     is written, the worker's exit status (or signal) becomes ours.
+ *   view: a stream command whose last line is about all records. The cut, PAFFY_RANGE and the spools are the stream commands'; every worker
+ *     loads the FASTA files. A worker that is given PAFFY_VIEW_SUMS=<spooldir>/<rank>.sums writes seven int64 there when it ends well (the
+ *     six sums of paf_stats_calc and its record count), prints no Total-alignments line and runs neither closing assert. The spools are
+ *     concatenated in rank order, the sums added up, and what paffy_view_main does behind its last record is done here: the aggregate line
+ *     under -s, same float expressions and format, then the two asserts (-u, -v; an empty input fails the first: abort()). A failing worker
+ *     ends the run as for the stream commands; one that ends well without sums ends it with status 1.
  *   tile: its state is per QUERY sequence (impl/paf_tile.c:160-175, impl/paf.c:675-688). The launcher makes two passes over the input
  *     (bytes of every query name; heaviest name to the lightest worker), routes every line to its worker's spool together with its
  *     global line number, each worker tiles its sequences, and the outputs -- each already in (s1 desc, AS desc, input order) order
@@ -75,12 +81,13 @@
  * Environment: PAFFY_GPUS=N; PAFFY_ONE_DEVICE=1 (rehearsal: every worker uses device 0); PAFFY_WORKER=path (another worker binary:
  * the CPU tests put a stand-in there); PAFFY_TMPDIR. Set for the workers: PAFFY_RANK, PAFFY_WORLD, PAFFY_DEVICE, PAFFY_RANGE (stream),
  * PAFFY_ROWS_FILE (tile), PAFFY_CHAIN_PART and PAFFY_CHAIN_FDS (chain), PAFFY_BED_PART and PAFFY_BED_FDS (to_bed), PAFFY_DEDUPE_PART,
- * PAFFY_DEDUPE_FDS and PAFFY_DEDUPE_SHARE_BYTES (dedupe).
+ * PAFFY_DEDUPE_FDS and PAFFY_DEDUPE_SHARE_BYTES (dedupe), PAFFY_VIEW_SUMS (view).
  */
 #define _GNU_SOURCE
 #include <errno.h>
 #include <fcntl.h>
 #include <getopt.h>
+#include <inttypes.h>
 #include <limits.h>
 #include <strings.h>
 #include <time.h>
@@ -100,10 +107,10 @@
 static char g_worker[PATH_MAX];
 static char g_tmpdir[PATH_MAX];  /* where the private spool directory is made */
 static char g_spooldir[PATH_MAX]; /* mkdtemp(<tmpdir>/paffy.XXXXXX), mode 0700: nobody else can plant a link under a name we open */
-enum { SP_IN, SP_OUT, SP_ROWS, SP_IDX, SP_TAILS, SP_IDS, SP_LKEYS, SP_SIDES, SP_BKEYS, SP_SEEN, SP_SEEN_ALL, SP_TAIL, SP_ENT, SP_CNT, SP_VER, SPOOL_KINDS };
-static const char *const k_spool_ext[SPOOL_KINDS] = {"in", "out", "rows", "idx", "tails", "ids", "lkeys", "sides", "bkeys", "seen", "seen_all", "tail", "ent", "cnt", "ver"};
+enum { SP_IN, SP_OUT, SP_ROWS, SP_IDX, SP_TAILS, SP_IDS, SP_LKEYS, SP_SIDES, SP_BKEYS, SP_SEEN, SP_SEEN_ALL, SP_TAIL, SP_ENT, SP_CNT, SP_VER, SP_SUMS, SPOOL_KINDS };
+static const char *const k_spool_ext[SPOOL_KINDS] = {"in", "out", "rows", "idx", "tails", "ids", "lkeys", "sides", "bkeys", "seen", "seen_all", "tail", "ent", "cnt", "ver", "sums"};
 /* per rank: input, output, rows (tile), index, chain's tail keys, chain ids, line keys, to_bed's side masks, block keys, seen flags, their union, the -q tail,
-   and dedupe's entries, entry counts and verdict bytes */
+   dedupe's entries, entry counts and verdict bytes, and view's sums */
 static char g_spool[MAX_RANKS][SPOOL_KINDS][PATH_MAX];
 static char g_stdin_spool[PATH_MAX];
 static int g_n = 0;
@@ -213,6 +220,12 @@ static const struct option k_to_bed[] = {{"logLevel", required_argument, 0, 'l'}
 static const struct option k_dedupe[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
                                          {"checkInverse", no_argument, 0, 'a'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
 
+/* view: its FASTA files are positional and every worker loads them (impl/paf_view.c:75-105) */
+static const struct option k_view[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
+                                       {"includeAlignment", no_argument, 0, 'a'}, {"printAggregateStats", no_argument, 0, 's'}, {"noPerAlignmentStats", no_argument, 0, 't'},
+                                       {"errorIfIdentityLowerThanX", required_argument, 0, 'u'}, {"errorIfAlignedBasesLowerThanX", required_argument, 0, 'v'},
+                                       {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+
 static const struct option k_chain[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
                                         {"maxGapLength", required_argument, 0, 'g'}, {"trimFraction", required_argument, 0, 't'}, {"chainGapOpen", required_argument, 0, 'd'},
                                         {"chainGapExtend", required_argument, 0, 'e'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
@@ -230,6 +243,7 @@ static void parse_cmdline(int argc, char **argv, CmdLine *cl) {
     else if (!strcmp(cmd, "chain")) { optstring = "l:i:o:hg:t:d:e:"; lopts = k_chain; }
     else if (!strcmp(cmd, "to_bed")) { optstring = "l:i:o:hbefm:nq:"; lopts = k_to_bed; }
     else if (!strcmp(cmd, "dedupe")) { optstring = "l:i:o:ha"; lopts = k_dedupe; }
+    else if (!strcmp(cmd, "view")) { optstring = "l:i:o:hastu:v:"; lopts = k_view; }
     /* getopt_long permutes the array it is given: a copy of argv[1..] (argv[1], the subcommand, stands where the program name would) */
     char **v = (char **)calloc((size_t)argc + 1, sizeof(char *));
     for (int i = 1; i < argc; i++) v[i - 1] = argv[i];
@@ -322,6 +336,8 @@ static pid_t spawn(char **wargv, int rank, int world, int one_device, const char
     else unsetenv("PAFFY_RANGE");
     if (rows_path) setenv("PAFFY_ROWS_FILE", rows_path, 1);
     else unsetenv("PAFFY_ROWS_FILE");
+    if (g_spool[rank][SP_SUMS][0]) setenv("PAFFY_VIEW_SUMS", g_spool[rank][SP_SUMS], 1); /* view: where this worker leaves its sums */
+    else unsetenv("PAFFY_VIEW_SUMS");
     for (int k = LINK_CHAIN; k <= LINK_DEDUPE; k++) {
         unsetenv(k_link_part[k]);
         unsetenv(k_link_fds[k]);
@@ -349,9 +365,62 @@ static int status_of(int st) {
     return WEXITSTATUS(st);
 }
 
-/* ---------------- stream commands ---------------- */
+/* ---------------- stream commands, and view ---------------- */
 
-static int run_stream(const char *cmd, const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path) {
+static int read_all(int fd, void *buf, size_t n);
+static int has_flag(const CmdLine *cl, char key, const char *takes_value);
+
+/* view: the six sums and the record count of every worker that ended well, added up (paf_stats_calc's order, impl/paf.c:236-260) */
+typedef struct {
+    int64_t t[6], n_alignments;
+} ViewTotals;
+
+static int add_view_sums(const char *path, ViewTotals *vt) {
+    int64_t rec[7];
+    const int fd = open(path, O_RDONLY | O_NOFOLLOW);
+    const int ok = fd >= 0 && read_all(fd, rec, sizeof(rec)) == 0;
+    if (fd >= 0) close(fd);
+    if (!ok) return -1;
+    for (int k = 0; k < 6; k++) vt->t[k] += rec[k];
+    vt->n_alignments += rec[6];
+    return 0;
+}
+
+/* what paffy_view_main does behind its last record (host/paffy_cmds.c; impl/paf_view.c:163-188), on the sums of all parts: the aggregate
+   line under -s, in the same float arithmetic and format, then the two asserts (NaN >= x is false: an empty input fails the first) */
+static int view_close(const CmdLine *cl, const ViewTotals *vt, int out_fd) {
+    float min_identity = 0.0f;
+    int64_t min_aligned = 0, t[6];
+    for (int i = 0; i < cl->n_opts; i++) { /* the last -u / -v holds, as in the worker's getopt loop */
+        const char k = cl->opts[i][1];
+        if (!strchr("luv", k)) continue;
+        if (k == 'u') min_identity = (float)atof(cl->opts[i + 1]);
+        if (k == 'v') min_aligned = atoi(cl->opts[i + 1]);
+        i++;
+    }
+    memcpy(t, vt->t, sizeof(t));
+    if (!has_flag(cl, 's', "luv")) memset(t, 0, sizeof(t)); /* the reference only adds the records up under -s (impl/paf_view.c:163-168) */
+    else {
+        char line[512];
+        const int len = snprintf(line, sizeof(line), "Total-alignments:%" PRIi64 "\tAvg-Identity:%f\tAvg-Identity-with-gaps:%f\tAligned-bases:%" PRIi64
+                                 "\tAligned-bases-with-gaps:%" PRIi64 "\tQuery-inserts:%" PRIi64 "\tQuery-deletes:%" PRIi64 "\n",
+                                 vt->n_alignments, (float)t[0] / (t[0] + t[1]), (float)t[0] / (t[0] + t[1] + t[4] + t[5]), t[0] + t[1], t[0] + t[1] + t[4] + t[5], t[2], t[3]);
+        for (int o = 0; o < len;) {
+            const ssize_t w = write(out_fd, line + o, (size_t)(len - o));
+            if (w < 0 && errno == EINTR) continue;
+            if (w <= 0) return 1;
+            o += (int)w;
+        }
+    }
+    if (!((float)t[0] / (t[0] + t[1]) >= min_identity) || !(t[0] + t[1] >= min_aligned)) {
+        fprintf(stderr, "paffy view: Assertion failed (average identity or aligned bases below the requested minimum)\n");
+        cleanup();
+        abort();
+    }
+    return 0;
+}
+
+static int run_stream(const char *cmd, const CmdLine *cl, int n, int one_device, const char *in_path, const char *out_path, ViewTotals *vt) {
     int fd = open(in_path, O_RDONLY);
     struct stat sb;
     if (fd < 0 || fstat(fd, &sb) != 0) {
@@ -383,6 +452,7 @@ static int run_stream(const char *cmd, const CmdLine *cl, int n, int one_device,
     pid_t pids[MAX_RANKS];
     for (int r = 0; r < n; r++) {
         snprintf(g_spool[r][SP_OUT], PATH_MAX, "%s/%d.out", g_spooldir, r);
+        if (vt) snprintf(g_spool[r][SP_SUMS], PATH_MAX, "%s/%d.sums", g_spooldir, r);
         char range[64];
         snprintf(range, sizeof(range), "%lld:%lld", (long long)cut[r], (long long)cut[r + 1]);
         char **wv = worker_argv(cmd, cl, in_path, g_spool[r][SP_OUT]);
@@ -423,7 +493,18 @@ static int run_stream(const char *cmd, const CmdLine *cl, int n, int one_device,
             if (out_fd != 1) close(out_fd);
             return status_of(st);
         }
+        if (vt && add_view_sums(g_spool[r][SP_SUMS], vt) != 0) { /* it ended well and left no sums: no aggregate line can be right */
+            fprintf(stderr, "paffy view: worker %d left no sums in %s\n", r, g_spool[r][SP_SUMS]);
+            for (int q = r + 1; q < n; q++) kill(pids[q], SIGTERM);
+            for (int q = r + 1; q < n; q++) {
+                waitpid(pids[q], NULL, 0);
+                g_pids[q] = 0;
+            }
+            if (out_fd != 1) close(out_fd);
+            return 1;
+        }
     }
+    if (vt && !rc) rc = view_close(cl, vt, out_fd);
     if (out_fd != 1) close(out_fd);
     return rc;
 }
@@ -1405,12 +1486,14 @@ int main(int argc, char **argv) {
     const int is_chain = argc >= 2 && !strcmp(argv[1], "chain");
     const int is_bed = argc >= 2 && !strcmp(argv[1], "to_bed");
     const int is_dedupe = argc >= 2 && !strcmp(argv[1], "dedupe");
-    int shard = n > 1 && argc >= 2 && (is_stream_cmd(argv[1]) || !strcmp(argv[1], "tile") || is_chain || is_bed || is_dedupe);
+    const int is_view = argc >= 2 && !strcmp(argv[1], "view");
+    int shard = n > 1 && argc >= 2 && (is_stream_cmd(argv[1]) || !strcmp(argv[1], "tile") || is_chain || is_bed || is_dedupe || is_view);
     CmdLine cl;
     memset(&cl, 0, sizeof(cl));
     if (shard) {
         parse_cmdline(argc, argv, &cl);
         shard = cl.ok; /* -h, or something getopt_long would reject: the one worker says what the reference says */
+        if (is_view && cl.n_pos == 0) shard = 0; /* no sequence file: it says that too (impl/paf_view.c:108-111) */
         if (shard && (is_chain || is_bed || is_dedupe) && cl.in_path) { /* and so it does for an input that cannot be opened */
             const int fd = open(cl.in_path, O_RDONLY);
             if (fd < 0) shard = 0;
@@ -1463,10 +1546,13 @@ int main(int argc, char **argv) {
             return 127;
         }
     }
+    ViewTotals view_totals;
+    memset(&view_totals, 0, sizeof(view_totals));
     const int rc = !strcmp(argv[1], "tile") ? run_tile(&cl, n, one_device, in_path, out_path)
                    : (is_chain ? run_chain(&cl, n, one_device, in_path, out_path)
                                : (is_bed ? run_to_bed(&cl, n, one_device, in_path, out_path)
-                                         : (is_dedupe ? run_dedupe(&cl, n, one_device, in_path, out_path) : run_stream(argv[1], &cl, n, one_device, in_path, out_path))));
+                                         : (is_dedupe ? run_dedupe(&cl, n, one_device, in_path, out_path)
+                                                      : run_stream(argv[1], &cl, n, one_device, in_path, out_path, is_view ? &view_totals : NULL))));
     free(cl.copy);
     return rc;
 }

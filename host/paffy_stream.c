@@ -90,9 +90,16 @@ void host_log_info(const char *fmt, ...) {
     va_end(ap);
 }
 
-static size_t chunk_bytes(void) {
+/* PAFFY_CHUNK_MB, or the command's default */
+static double now_s(void) {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+static size_t chunk_bytes(long default_mb) {
     const char *e = getenv("PAFFY_CHUNK_MB");
-    long mb = e ? atol(e) : 256;
+    long mb = e ? atol(e) : default_mb;
     if (mb < 1) mb = 1;
     if (mb > 1900) mb = 1900; /* one batch stays below 2 GiB */
     return (size_t)mb << 20;
@@ -145,7 +152,8 @@ static int dedupe_chunk(paffy_hip_ctx *ctx, const char *h_in, int64_t in_len, ch
     return rc;
 }
 
-/* paffy view -s -t: nothing is written per record; the PAFFY_STATS sums of every chunk are added up */
+/* paffy view: the chunks go through a stream in view mode (paffy_hip_stream_open_view), which adds up the PAFFY_STATS sums of every
+   chunk; under -s -t nothing is written per record */
 static int g_stats_mode = 0;
 static int64_t g_stats[6], g_stats_records;
 void host_set_stats(int on) {
@@ -163,85 +171,8 @@ void host_set_stats_lines(FILE *fh) { g_stats_lines = fh; }
 static int g_alignment_rows = 0; /* paffy view -a: the base-level rows under every stats line */
 void host_set_alignment_rows(int on) { g_alignment_rows = on; }
 
-/*
- * paf_pretty_print per record (impl/paf.c:269-315): the stats line and, under -a, the base-level rows behind it are written by the
- * GPU into device memory (paffy_hip_plan_view_text: the fields are the plan's own header parse, the sums its PAFFY_STATS stage) and
- * fetched in ranges of records of at most 128 MiB of text (at least one record): one copy and one fwrite per range.
- */
-static int stats_lines(paffy_hip_ctx *ctx, int64_t n_records, int64_t record_base) {
-    if (n_records <= 0) return 0;
-    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n_records + 1));
-    char *text = NULL;
-    void *d_text = NULL;
-    int64_t cap = 0;
-    int rc = paffy_hip_plan_view_sizes(ctx, 0, n_records, g_alignment_rows, off);
-    if (!rc) { /* sizes -> running sums */
-        int64_t at = 0;
-        for (int64_t r = 0; r < n_records; r++) {
-            int64_t b = off[r];
-            off[r] = at;
-            at += b;
-        }
-        off[n_records] = at;
-    }
-    for (int64_t first = 0, end; first < n_records && !rc; first = end) {
-        end = first + 1;
-        while (end < n_records && off[end + 1] - off[first] <= ((int64_t)128 << 20)) end++;
-        const int64_t bytes = off[end] - off[first];
-        if (bytes > cap) { /* the first range is the longest but for a record of more than 128 MiB */
-            free(text);
-            if (d_text) paffy_hip_free(d_text);
-            d_text = NULL;
-            cap = bytes;
-            text = (char *)malloc((size_t)cap + 1);
-            if (!text || paffy_hip_malloc(&d_text, cap) != 0) {
-                rc = PAFFY_E_HIP;
-                break;
-            }
-        }
-        paffy_error e;
-        rc = paffy_hip_plan_view_text(ctx, first, end - first, g_alignment_rows, off + first, d_text, cap, &e);
-        if (!rc && e.code) { /* e.record counts from the batch's first record, whichever range it was fetched in */
-            /* rows that reach outside a sequence (only = / X / I / D ops: the mismatch encoder looked at no base of the record). What
-               has gone out by then has always been the ranges before this one and the stats line of this one's first record */
-            int64_t line = 0;
-            if (paffy_hip_plan_view_sizes(ctx, first, 1, 0, &line) == 0 && line <= bytes && paffy_hip_memcpy_d2h(text, d_text, line) == 0)
-                fwrite(text, 1, (size_t)line, g_stats_lines);
-            fflush(g_stats_lines);
-            die_like_reference(&e, record_base);
-        }
-        if (!rc) rc = paffy_hip_memcpy_d2h(text, d_text, bytes);
-        if (!rc && fwrite(text, 1, (size_t)bytes, g_stats_lines) != (size_t)bytes) rc = PAFFY_E_HIP;
-    }
-    if (d_text) paffy_hip_free(d_text);
-    free(text);
-    free(off);
-    return rc;
-}
-
-static int stats_chunk(paffy_hip_ctx *ctx, const paffy_stage *stages, int n_stages, const char *buf, int64_t len, int64_t record_base,
-                       paffy_plan_info *info) {
-    void *d_in = NULL;
-    if (paffy_hip_malloc(&d_in, len + 64) != 0) return PAFFY_E_HIP;
-    int rc = paffy_hip_memcpy_h2d(d_in, buf, len);
-    if (!rc) rc = paffy_hip_plan(ctx, stages, n_stages, d_in, len, info);
-    int64_t sums[6];
-    if (!rc) rc = paffy_hip_plan_stats(ctx, sums);
-    if (!rc && info->error.code == 0) {
-        for (int k = 0; k < 6; k++) g_stats[k] += sums[k];
-        g_stats_records += info->n_records;
-        if (g_stats_lines) rc = stats_lines(ctx, info->n_records, record_base);
-    } else if (!rc && g_stats_lines) {
-        /* a chunk with a failing record writes nothing. What is reported is the first line that does not parse, if there is one,
-           before the first record the stages fail on -- the order in which the lines' fields used to be read (a parse of the whole
-           chunk) and the stages run: a plan of the parse alone tells */
-        const paffy_stage pass = {PAFFY_PASS, 0.0f, 0.0f};
-        paffy_plan_info parsed;
-        if (paffy_hip_plan(ctx, &pass, 1, d_in, len, &parsed) == 0 && parsed.error.code) *info = parsed;
-    }
-    paffy_hip_free(d_in);
-    return rc;
-}
+/* paf_pretty_print per record (impl/paf.c:269-315): the text is fetched in ranges of records of at most this much (at least one record) */
+#define VIEW_RANGE_BYTES ((int64_t)128 << 20)
 
 /* every piece of the oldest submitted chunk to `out` */
 static int drain_chunk(paffy_hip_stream *st, FILE *out) {
@@ -254,25 +185,59 @@ static int drain_chunk(paffy_hip_stream *st, FILE *out) {
     }
 }
 
+/* paffy view, after a chunk has been drained: rows that reach outside a sequence (only = / X / I / D ops: the mismatch encoder looked at no
+   base of the record) end the process where the reference's read ends it, with the text up to the record's stats line written */
+static void view_rows_check(paffy_hip_stream *st, FILE *out, int64_t record_base) {
+    int64_t sums[6], n = 0;
+    paffy_error e;
+    if (paffy_hip_stream_view_status(st, sums, &n, &e) != 0 || !e.code) return;
+    fflush(out);
+    die_like_reference(&e, record_base);
+}
+
 /*
  * The stream commands (impl/paf_invert.c:84-89 and friends): chunks of whole lines go through pinned buffers; while the GPU works on
- * chunk k + 1 (copy in, sizing, line writer) the host drains the output of chunk k piece by piece into `out`.
+ * chunk k + 1 (copy in, sizing, line writer) the host drains the output of chunk k piece by piece into `out`. `paffy view` is one of
+ * them (g_stats_mode): its stream is in view mode, the text of a chunk comes in ranges, and a chunk of more than one range has to be
+ * drained before the next buffer is to be had.
  */
 static int pipelined_stream(paffy_hip_ctx *ctx, const paffy_stage *stages, int n_stages, FILE *in, FILE *out) {
-    const int64_t cap0 = (int64_t)chunk_bytes();
+    const int view = g_stats_mode;
+    /* the stream's two input buffers are pinned, and pinning costs by the byte: `paffy view`, whose output is a fraction of its input,
+       takes chunks of 64 MiB unless PAFFY_CHUNK_MB says otherwise */
+    const int64_t cap0 = (int64_t)chunk_bytes(view ? 64 : 256);
+    /* PAFFY_STREAM_TIMES=1: where the loop's time went, on stderr when it ends well (tools/view_stream_bench.py reads it) */
+    const int timed = getenv("PAFFY_STREAM_TIMES") != NULL;
+    double t_open = 0, t_read = 0, t_submit = 0, t_drain = 0, t_close = 0, t0 = now_s();
+    int64_t n_chunks = 0;
+    /* the pinned output pieces as well: 8 MiB each for text (three of 64 MiB cost more to pin and unpin than their longer copies save: 0.14 s of
+       `view -a -s` on 100 MB of input went into opening and closing the stream), next to nothing where nothing is written */
+    const int view_text = g_stats_lines ? (g_alignment_rows ? 2 : 1) : 0;
+    const int64_t view_piece = view_text ? (int64_t)8 << 20 : 4096;
     paffy_hip_stream *st = NULL;
-    if (paffy_hip_stream_open(ctx, stages, n_stages, cap0, (int64_t)64 << 20, &st) != 0) {
+    if ((view ? paffy_hip_stream_open_view(ctx, view_text, cap0, view_piece, VIEW_RANGE_BYTES, &st)
+              : paffy_hip_stream_open(ctx, stages, n_stages, cap0, (int64_t)64 << 20, &st)) != 0) {
         fprintf(stderr, "paffy: could not set up the streaming buffers: %s\n", paffy_hip_last_error(ctx));
         return 1;
     }
+    t_open = now_s() - t0;
     const char *carry = NULL; /* the partial last line of the chunk before, still in that chunk's buffer */
-    int64_t carry_len = 0, records_done = 0;
+    int64_t carry_len = 0, records_done = 0, pending_base = 0; /* pending_base: the first record of the chunk not yet drained */
     int eof = 0, rc = 0, pending = 0;
     paffy_plan_info info;
     memset(&info, 0, sizeof(info));
     while (!rc && (!eof || carry_len > 0)) {
         int64_t cap = 0;
         char *buf = paffy_hip_stream_input(st, cap0, 0, &cap);
+        if (!buf && view && pending) { /* the chunk before has ranges still to be written: it is read out first */
+            if (drain_chunk(st, out)) {
+                rc = 1;
+                break;
+            }
+            pending = 0;
+            view_rows_check(st, out, pending_base);
+            buf = paffy_hip_stream_input(st, cap0, 0, &cap);
+        }
         if (!buf) {
             rc = 1;
             break;
@@ -285,6 +250,7 @@ static int pipelined_stream(paffy_hip_ctx *ctx, const paffy_stage *stages, int n
         }
         if (carry_len) memcpy(buf, carry, (size_t)carry_len);
         int64_t use = 0;
+        t0 = now_s();
         for (;;) {
             if (!eof && have < cap) {
                 size_t got = fread(buf + have, 1, (size_t)(cap - have), in);
@@ -302,16 +268,24 @@ static int pipelined_stream(paffy_hip_ctx *ctx, const paffy_stage *stages, int n
                 break;
             }
         }
+        t_read += now_s() - t0;
         if (rc || use == 0) break;
+        t0 = now_s();
+        n_chunks++;
         if (paffy_hip_stream_submit(st, use, &info) != 0) {
             fprintf(stderr, "paffy: GPU call failed: %s\n", paffy_hip_last_error(ctx));
             rc = 1;
             break;
         }
+        t_submit += now_s() - t0;
         carry = buf + use; /* stays where it is until this slot is filled again, two chunks from now */
         carry_len = have - use;
+        t0 = now_s();
         if (pending && drain_chunk(st, out)) rc = 1; /* the chunk before, while the GPU works on this one */
+        t_drain += now_s() - t0;
+        if (view && pending && !rc) view_rows_check(st, out, pending_base); /* the earlier failure speaks */
         pending = 1;
+        pending_base = records_done;
         if (info.error.code) { /* everything before the failing record is written, then the process ends like the reference */
             if (!rc) rc = drain_chunk(st, out);
             fflush(out);
@@ -319,9 +293,21 @@ static int pipelined_stream(paffy_hip_ctx *ctx, const paffy_stage *stages, int n
         }
         records_done += info.n_records;
     }
+    t0 = now_s();
     if (!rc && pending && drain_chunk(st, out)) rc = 1;
+    t_drain += now_s() - t0;
+    if (view && !rc) {
+        if (pending) view_rows_check(st, out, pending_base);
+        paffy_error e;
+        if (paffy_hip_stream_view_status(st, g_stats, &g_stats_records, &e) != 0) rc = 1;
+    }
     if (rc && ctx) fprintf(stderr, "paffy: streaming failed: %s\n", paffy_hip_last_error(ctx));
+    t0 = now_s();
     paffy_hip_stream_close(st);
+    t_close = now_s() - t0;
+    if (timed && !rc)
+        fprintf(stderr, "paffy stream times: chunks %lld open %.4f read %.4f submit %.4f drain %.4f close %.4f\n", (long long)n_chunks, t_open, t_read, t_submit,
+                t_drain, t_close);
     return rc;
 }
 
@@ -418,13 +404,13 @@ int host_stream(const paffy_stage *stages, int n_stages, FILE *in, FILE *out) {
         abort();
     }
     paffy_hip_set_filter(ctx, &g_filter);
-    if (!g_dedupe_mode && !g_stats_mode) {
+    if (!g_dedupe_mode) {
         int rc = pipelined_stream(ctx, stages, n_stages, in, out);
         paffy_hip_destroy(ctx);
         fflush(out);
         return rc;
     }
-    const size_t cap = chunk_bytes();
+    const size_t cap = chunk_bytes(256);
     size_t buf_cap = cap + (1 << 20), have = 0;
     char *buf = (char *)malloc(buf_cap);
     int64_t records_done = 0;
@@ -449,7 +435,7 @@ int host_stream(const paffy_stage *stages, int n_stages, FILE *in, FILE *out) {
         char *h_out = NULL;
         int64_t out_len = 0;
         paffy_plan_info info;
-        int r = g_dedupe_mode ? dedupe_chunk(ctx, buf, (int64_t)use, &h_out, &out_len, &info) : stats_chunk(ctx, stages, n_stages, buf, (int64_t)use, records_done, &info);
+        int r = dedupe_chunk(ctx, buf, (int64_t)use, &h_out, &out_len, &info);
         if (r != 0) {
             fprintf(stderr, "paffy: GPU call failed (%d): %s\n", r, paffy_hip_last_error(ctx));
             rc = 1;
@@ -524,7 +510,7 @@ int host_split_file(FILE *in, const char *prefix, int by_query, int64_t min_leng
     int64_t d_in_cap = 0, d_out_cap = 0, h_out_cap = 0, groups_cap = 0;
     char *h_out = NULL;
     paffy_split_group *groups = NULL;
-    const size_t cap = chunk_bytes();
+    const size_t cap = chunk_bytes(256);
     size_t buf_cap = cap + (1 << 20), have = 0;
     char *buf = (char *)malloc(buf_cap);
     int eof = 0, rc = 0;
@@ -960,7 +946,7 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
     memset(&bpart, 0, sizeof(bpart));
     const int in_bed_part = bed ? bed_part_open(&bpart, bed) : 0;
     if (in_bed_part < 0) return 1;
-    const size_t cap = chunk_bytes();
+    const size_t cap = chunk_bytes(256);
     size_t buf_cap = cap + (1 << 20), have = 0;
     char *buf = (char *)malloc(buf_cap);
     void **d_batches = NULL;
@@ -1202,7 +1188,7 @@ int host_dedupe_part(const char *in_path, const char *out_path, int check_invers
     memcpy(P.dir, prefix, (size_t)(slash - prefix));
     P.rank = atoi(rank);
     P.world = atoi(world);
-    P.share = share && atoll(share) >= 1 ? (int64_t)atoll(share) : (int64_t)chunk_bytes();
+    P.share = share && atoll(share) >= 1 ? (int64_t)atoll(share) : (int64_t)chunk_bytes(256);
     P.fd = open(in_path, O_RDONLY);
     const off_t size = P.fd < 0 ? -1 : lseek(P.fd, 0, SEEK_END);
     if (size < 0 || P.world < 1 || P.rank < 0 || P.rank >= P.world) {

@@ -552,6 +552,43 @@ int paffy_hip_plan_view_text(paffy_hip_ctx *ctx, int64_t first, int64_t count, i
                              paffy_error *err);
 
 /*
+ * The same text with its layout kept on the device: nothing per record crosses to the host and back (the two calls above bring the
+ * sizes to the host, 8 bytes per record, and take their running sums back, 8 more).
+ * _layout sizes every block of the planned batch, leaves the n_records + 1 running sums on the device and cuts the records into ranges
+ * of at most range_bytes (>= 1) of text each, greedily from record 0: a range takes records while the sum stays within range_bytes and
+ * one record at least, so a longer block is a range of its own. *total_bytes = the batch's text, *n_ranges = the ranges (0 for an
+ * empty batch). Only the range table comes to the host: _ranges copies it out -- n_ranges + 1 entries, the first record and the first
+ * byte of every range and the closing {n_records, total_bytes}; returns n_ranges (cap_ranges <= n_ranges: PAFFY_E_CAPACITY).
+ * _emit_range writes range `range` at d_out (out_cap at least the range's bytes, or PAFFY_E_CAPACITY) and returns when it is written;
+ * *bytes = the range's bytes. The rows' failures come back in *err exactly as paffy_hip_plan_view_text reports them (err->record counts
+ * from the batch's first record), and *bytes is then what the reference had printed of this range by then: every block in front of the
+ * failing record and that record's stats line. The state checks are those of paffy_hip_plan_view_text; _ranges and _emit_range without
+ * a _layout of the current plan: PAFFY_E_STATE. The batch text must still be in place.
+ */
+int paffy_hip_plan_view_layout(paffy_hip_ctx *ctx, int with_rows, int64_t range_bytes, int64_t *total_bytes, int64_t *n_ranges);
+int64_t paffy_hip_plan_view_ranges(paffy_hip_ctx *ctx, int64_t cap_ranges, int64_t *first_record, int64_t *first_byte);
+int paffy_hip_plan_view_emit_range(paffy_hip_ctx *ctx, int64_t range, void *d_out, int64_t out_cap, int64_t *bytes, paffy_error *err);
+
+/*
+ * A stream in view mode (`paffy view`): open / input / submit / read / close as above, the stage list is [PAFFY_ADD_MISMATCHES,
+ * PAFFY_STATS] and what read hands out is the view text of the chunk. text: 0 nothing (the sums only: `view -s -t`), 1 the stats
+ * lines, 2 the lines with the base-level rows (raw sequences needed). paffy_hip_stats_only and paffy_hip_keep_raw_sequences of the
+ * context apply as ever.
+ *   submit: copies in, plans, and on a plan without a failing record adds the six sums and the records to the stream's totals, lays the
+ *           text out (ranges of range_bytes) and writes range 0; info.out_bytes = the chunk's text. A chunk with a failing record has no
+ *           output and info.error tells why -- a line that does not parse before an earlier record a stage fails on, the order the
+ *           reference meets them in.
+ *   A chunk of more than one range is open: read writes its later ranges as the earlier ones have been handed out, from the plan of
+ *           the chunk, so input returns NULL until the chunk is read out (read it, then ask again). A chunk of one range pipelines
+ *           like a chunk of any other stream.
+ *   view_status: the totals, and in *rows_err the rows' failure of the chunk read last (code 0: none; the record counts from that
+ *           chunk's first record). The text read of that chunk ends with the failing record's stats line. Once a chunk's rows have
+ *           failed, submit returns PAFFY_E_STATE.
+ */
+int paffy_hip_stream_open_view(paffy_hip_ctx *ctx, int text, int64_t chunk_bytes, int64_t piece_bytes, int64_t range_bytes, paffy_hip_stream **stream);
+int paffy_hip_stream_view_status(paffy_hip_stream *stream, int64_t sums[6], int64_t *n_records, paffy_error *rows_err);
+
+/*
  * Records as structs, for hosts that hold `Paf` objects (the per-record API of inc/paf.h:75-269, host/paf_api.c): the text is
  * parsed on the GPU (paf_parse + cigar_parse, impl/paf.c:70-209) and the fields come back as arrays -- one paffy_record per line,
  * names and cigar text as slices of h_in, the ops of all records back to back in the CigarRecord layout of inc/paf.h:61-64

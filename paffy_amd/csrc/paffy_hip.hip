@@ -1137,6 +1137,12 @@ struct paffy_hip_ctx {
     bool plan_split = false;      /* the last plan is paffy_hip_split_plan's: a line plan with a group table (paffy_hip_split_groups) */
     DevBuf view_sums;             /* flat_view_kernel.h: six sums per piece slot */
     DevBuf view_work;             /* view_line_kernel.h: sizes, row offsets and the offsets' verdict of a paffy_hip_plan_view_* call */
+    /* paffy_hip_plan_view_layout: the sizes of the batch's blocks, their running sums, the rows' bytes and offsets and the verdict of a range
+       (view_layout), the ranges the cut kernel wrote (view_ranges_dev) and their copy on the host (view_tab: n_ranges + 1 entries) */
+    DevBuf view_layout, view_ranges_dev;
+    std::vector<int64_t> view_tab; /* {first record, first byte} per range */
+    bool view_laid = false; /* the layout belongs to the current plan (plan_begin clears it) */
+    bool view_laid_rows = false;
     uint32_t flat_chunk_slots = 0;
     bool lvl0_long_ok = false, lvl0_long_off = false; /* the longer first store level: shown safe by the batch before / overflowed once */
     /* device buffers of the two slots of a closed stream (paffy_hip_stream_close), taken again by the next paffy_hip_stream_open: a
@@ -1335,7 +1341,7 @@ void paffy_hip_destroy(paffy_hip_ctx *c) {
     c->index_pool.clear();
     if (c->one_batch.p) (void)hipFree(c->one_batch.p);
     DevBuf *bufs[] = {&c->tile_counts, &c->sep_pos, &c->nl_idx, &c->meta, &c->out_len, &c->out_rows, &c->status, &c->err_aux,
-                      &c->n_ops, &c->arena_off, &c->out_off, &c->w_list, &c->b_list, &c->b_list1, &c->arena, &c->info, &c->synth_sizes, &c->rec_plan, &c->ops_mirror, &c->seq_blob, &c->seq_table, &c->seq_names, &c->seq_name_off, &c->synth4_contigs, &c->synth4_q, &c->synth4_t, &c->seq_comp, &c->seq_raw, &c->pretty_off, &c->pretty_out, &c->pretty_err, &c->host_in, &c->host_out, &c->rec_stats, &c->flat_nd, &c->flat_rec, &c->flat_chunks, &c->flat_sums, &c->flat_done, &c->flat_items, &c->flat_pieces, &c->add_pieces, &c->add_scr_cnt, &c->add_scr_off, &c->add_new_cnt, &c->add_new_off, &c->add_text, &c->add_bad, &c->add_part, &c->add_scratch, &c->add_new_ops, &c->view_sums, &c->view_work, &c->bed_keys, &c->bed_tab, &c->bed_starts, &c->bed_len, &c->bed_off, &c->bed_tiles,
+                      &c->n_ops, &c->arena_off, &c->out_off, &c->w_list, &c->b_list, &c->b_list1, &c->arena, &c->info, &c->synth_sizes, &c->rec_plan, &c->ops_mirror, &c->seq_blob, &c->seq_table, &c->seq_names, &c->seq_name_off, &c->synth4_contigs, &c->synth4_q, &c->synth4_t, &c->seq_comp, &c->seq_raw, &c->pretty_off, &c->pretty_out, &c->pretty_err, &c->host_in, &c->host_out, &c->rec_stats, &c->flat_nd, &c->flat_rec, &c->flat_chunks, &c->flat_sums, &c->flat_done, &c->flat_items, &c->flat_pieces, &c->add_pieces, &c->add_scr_cnt, &c->add_scr_off, &c->add_new_cnt, &c->add_new_off, &c->add_text, &c->add_bad, &c->add_part, &c->add_scratch, &c->add_new_ops, &c->view_sums, &c->view_work, &c->view_layout, &c->view_ranges_dev, &c->bed_keys, &c->bed_tab, &c->bed_starts, &c->bed_len, &c->bed_off, &c->bed_tiles,
                       &c->rec_qseq, &c->rec_tseq, &c->tile_keys, &c->tile_order, &c->tile_rank, &c->tile_coff, &c->tile_cbase,
                       &c->tile_cov, &c->tile_level, &c->tile_len, &c->tile_items, &c->tile_slots, &c->tile_parts, &c->scan_part, &c->dedupe_keys, &c->emit_order, &c->order_cnt, &c->up_table, &c->up_names};
     for (DevBuf *b : bufs)
@@ -1383,6 +1389,7 @@ static void plan_begin(paffy_hip_ctx *c, PlanKind kind, int64_t in_bytes, paffy_
     c->line_n = 0;
     c->bed_runs = 0;
     c->plan_seq_lookup = false;
+    c->view_laid = false;
 }
 
 /* Separator index + header parse shared by plan and tile_plan. */
@@ -3187,6 +3194,10 @@ struct StreamSlot {
     hipEvent_t ev_in = nullptr, ev_emit = nullptr;
     int64_t out_len = 0, read_at = 0; /* bytes of output, bytes already handed to the host */
     bool busy = false;
+    /* view mode: the chunk's ranges, the one in d_out, the verdict of that range (pinned) and whether read has looked at it */
+    int64_t view_ranges = 0, view_range_at = 0;
+    int64_t *h_verdict = nullptr;
+    bool verdict_seen = false, view_open = false; /* view_open: this chunk has more than one range */
 };
 struct paffy_hip_stream {
     paffy_hip_ctx *c = nullptr;
@@ -3202,7 +3213,16 @@ struct paffy_hip_stream {
     int64_t piece_len[3] = {0, 0, 0};
     int64_t issued_at = 0; /* bytes of the draining chunk whose copy has been issued */
     int n_issued = 0, n_returned = 0;
+    /* paffy_hip_stream_open_view: -1 a stream of stage lists; 0 sums only, 1 stats lines, 2 lines and base-level rows */
+    int view_text = -1;
+    int64_t view_range_bytes = 0;
+    int64_t view_sums[6] = {0, 0, 0, 0, 0, 0}, view_records = 0;
+    bool view_open = false; /* the chunk submitted last has ranges still to be written: the plan stays until it is read out */
+    paffy_error view_rows_err = {0, 0, 0, 0};
+    bool view_failed = false;
 };
+static int view_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_info *info);
+static int view_stream_read(paffy_hip_stream *s, const char **piece, int64_t *len);
 
 static void stream_detach(paffy_hip_stream *s) { s->c = nullptr; }
 
@@ -3279,6 +3299,7 @@ void paffy_hip_stream_close(paffy_hip_stream *s) {
         }
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
         if (sl.ev_emit) (void)hipEventDestroy(sl.ev_emit);
+        if (sl.h_verdict) (void)hipHostFree(sl.h_verdict);
     }
     for (int k = 0; k < 3; k++) {
         if (s->piece[k]) (void)hipHostFree(s->piece[k]);
@@ -3294,7 +3315,7 @@ void paffy_hip_stream_close(paffy_hip_stream *s) {
 char *paffy_hip_stream_input(paffy_hip_stream *s, int64_t want, int64_t keep, int64_t *cap) {
     if (!s || !cap) return nullptr;
     StreamSlot &sl = s->slot[s->fill];
-    if (sl.busy) return nullptr;
+    if (sl.busy || s->view_open) return nullptr;
     if (want > (int64_t)sl.h_cap) {
         if (want >= (1ll << 31) - 64) return nullptr;
         char *nb = nullptr;
@@ -3308,13 +3329,10 @@ char *paffy_hip_stream_input(paffy_hip_stream *s, int64_t want, int64_t keep, in
     return sl.h_in;
 }
 
-/* the first in_len bytes of the current input buffer (whole lines) go through the stage list; *info is complete on return (the
-   plan is synchronous), the output is drained with paffy_hip_stream_read */
-int paffy_hip_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_info *info) {
-    if (!s || !info || in_len < 0) return PAFFY_E_ARG;
+/* ---- what both kinds of stream (stage lists, view mode) do alike ---- */
+/* stage-in: room for the chunk on the device, its copy on the H2D stream, and the kernels wait for it */
+static int stream_stage_in(paffy_hip_stream *s, StreamSlot &sl, int64_t in_len) {
     paffy_hip_ctx *c = s->c;
-    StreamSlot &sl = s->slot[s->fill];
-    if (sl.busy || in_len > (int64_t)sl.h_cap) return PAFFY_E_STATE;
     if ((size_t)in_len + 64 > sl.d_in_cap) {
         if (sl.d_in) HIPCHK(c, hipFree(sl.d_in));
         sl.d_in = nullptr;
@@ -3324,38 +3342,27 @@ int paffy_hip_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_info
     if (in_len > 0) HIPCHK(c, hipMemcpyAsync(sl.d_in, sl.h_in, (size_t)in_len, hipMemcpyHostToDevice, s->s_h2d));
     HIPCHK(c, hipEventRecord(sl.ev_in, s->s_h2d));
     HIPCHK(c, hipStreamWaitEvent(c->stream, sl.ev_in, 0));
-    int rc = paffy_hip_plan(c, s->stages, s->n_stages, sl.d_in, in_len, info);
-    if (rc) return rc;
-    sl.out_len = info->out_bytes;
-    sl.read_at = 0;
-    if (sl.out_len > 0) {
-        if ((size_t)sl.out_len + 64 > sl.d_out_cap) {
-            if (sl.d_out) HIPCHK(c, hipFree(sl.d_out));
-            sl.d_out = nullptr;
-            sl.d_out_cap = (size_t)sl.out_len + (size_t)sl.out_len / 4 + 4096;
-            HIPCHK(c, hipMalloc(&sl.d_out, sl.d_out_cap));
-        }
-        rc = paffy_hip_emit(c, sl.d_out, (int64_t)sl.d_out_cap);
-        if (rc) return rc;
-    }
-    HIPCHK(c, hipEventRecord(sl.ev_emit, c->stream));
+    return 0;
+}
+/* room for `bytes` of output in the slot; slack: a quarter more, so that a chunk a little longer than the last costs no allocation */
+static int stream_out_room(paffy_hip_ctx *c, StreamSlot &sl, int64_t bytes, bool slack) {
+    if ((size_t)bytes + 64 <= sl.d_out_cap) return 0;
+    if (sl.d_out) HIPCHK(c, hipFree(sl.d_out));
+    sl.d_out = nullptr;
+    sl.d_out_cap = (size_t)bytes + (slack ? (size_t)bytes / 4 : 0) + 4096;
+    HIPCHK(c, hipMalloc(&sl.d_out, sl.d_out_cap));
+    return 0;
+}
+/* the writers of the slot's output are enqueued: the chunk is the stream's */
+static int stream_submitted(paffy_hip_stream *s, StreamSlot &sl) {
+    HIPCHK(s->c, hipEventRecord(sl.ev_emit, s->c->stream));
     sl.busy = true;
     s->fill ^= 1;
     return 0;
 }
-
-/* the next piece of the oldest submitted chunk's output: *len bytes at *piece, valid until the call after next (three pinned pieces
-   rotate: this call starts the copy that follows the piece it hands out, into the buffer handed out two calls ago); *len = 0: that
-   chunk has been read completely (or nothing was submitted) */
-int paffy_hip_stream_read(paffy_hip_stream *s, const char **piece, int64_t *len) {
-    if (!s || !piece || !len) return PAFFY_E_ARG;
+/* keep two copies in flight: the piece handed out now and the one after it, of the sl.out_len bytes in the slot's output */
+static int stream_issue_pieces(paffy_hip_stream *s, StreamSlot &sl) {
     paffy_hip_ctx *c = s->c;
-    *piece = nullptr;
-    *len = 0;
-    StreamSlot &sl = s->slot[s->drain];
-    if (!sl.busy) return 0;
-    if (s->n_issued == 0) HIPCHK(c, hipStreamWaitEvent(s->s_d2h, sl.ev_emit, 0)); /* first piece of this chunk */
-    /* keep two copies in flight: the piece handed out now and the one after it */
     while (s->n_issued < s->n_returned + 2 && s->issued_at < sl.out_len) {
         const int k = s->n_issued % 3;
         const int64_t n = sl.out_len - s->issued_at < (int64_t)s->piece_cap ? sl.out_len - s->issued_at : (int64_t)s->piece_cap;
@@ -3365,19 +3372,65 @@ int paffy_hip_stream_read(paffy_hip_stream *s, const char **piece, int64_t *len)
         s->issued_at += n;
         s->n_issued++;
     }
-    if (s->n_returned == s->n_issued) { /* everything of this chunk has been handed out */
-        sl.busy = false;
-        s->drain ^= 1;
-        s->issued_at = 0;
-        s->n_issued = s->n_returned = 0;
-        return 0;
-    }
+    return 0;
+}
+/* everything of the draining chunk has been handed out: the next chunk's turn */
+static void stream_chunk_done(paffy_hip_stream *s, StreamSlot &sl) {
+    sl.busy = false;
+    s->drain ^= 1;
+    s->issued_at = 0;
+    s->n_issued = s->n_returned = 0;
+}
+/* the oldest piece in flight, once it has arrived */
+static int stream_hand_out(paffy_hip_stream *s, const char **piece, int64_t *len) {
     const int k = s->n_returned % 3;
-    HIPCHK(c, hipEventSynchronize(s->ev_piece[k]));
+    HIPCHK(s->c, hipEventSynchronize(s->ev_piece[k]));
     *piece = s->piece[k];
     *len = s->piece_len[k];
     s->n_returned++;
     return 0;
+}
+
+/* the first in_len bytes of the current input buffer (whole lines) go through the stage list; *info is complete on return (the
+   plan is synchronous), the output is drained with paffy_hip_stream_read */
+int paffy_hip_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_info *info) {
+    if (!s || !info || in_len < 0) return PAFFY_E_ARG;
+    if (s->view_text >= 0) return view_stream_submit(s, in_len, info);
+    paffy_hip_ctx *c = s->c;
+    StreamSlot &sl = s->slot[s->fill];
+    if (sl.busy || in_len > (int64_t)sl.h_cap) return PAFFY_E_STATE;
+    int rc = stream_stage_in(s, sl, in_len);
+    if (!rc) rc = paffy_hip_plan(c, s->stages, s->n_stages, sl.d_in, in_len, info);
+    if (rc) return rc;
+    sl.out_len = info->out_bytes;
+    sl.read_at = 0;
+    if (sl.out_len > 0) {
+        rc = stream_out_room(c, sl, sl.out_len, true);
+        if (!rc) rc = paffy_hip_emit(c, sl.d_out, (int64_t)sl.d_out_cap);
+        if (rc) return rc;
+    }
+    return stream_submitted(s, sl);
+}
+
+/* the next piece of the oldest submitted chunk's output: *len bytes at *piece, valid until the call after next (three pinned pieces
+   rotate: this call starts the copy that follows the piece it hands out, into the buffer handed out two calls ago); *len = 0: that
+   chunk has been read completely (or nothing was submitted) */
+int paffy_hip_stream_read(paffy_hip_stream *s, const char **piece, int64_t *len) {
+    if (!s || !piece || !len) return PAFFY_E_ARG;
+    if (s->view_text >= 0) return view_stream_read(s, piece, len);
+    paffy_hip_ctx *c = s->c;
+    *piece = nullptr;
+    *len = 0;
+    StreamSlot &sl = s->slot[s->drain];
+    if (!sl.busy) return 0;
+    if (s->n_issued == 0) HIPCHK(c, hipStreamWaitEvent(s->s_d2h, sl.ev_emit, 0)); /* first piece of this chunk */
+    int rc = stream_issue_pieces(s, sl);
+    if (rc) return rc;
+    if (s->n_returned == s->n_issued) { /* everything of this chunk has been handed out */
+        stream_chunk_done(s, sl);
+        return 0;
+    }
+    return stream_hand_out(s, piece, len);
 }
 
 /* exclusive scan of n int64 values on the device (two levels); *total on the host */
@@ -3814,6 +3867,295 @@ int paffy_hip_plan_view_text(paffy_hip_ctx *c, int64_t first, int64_t count, int
         err->stage = -1;
     }
     return 0;
+}
+
+/*
+ * ---- the layout of a planned batch's view text, kept on the device ----
+ * view_layout: size[n + 1] (the blocks' bytes and a closing 0, so that the scan leaves the total in off[n]), off[n + 1], rows_bytes[n + 1],
+ * rows_off[n + 1], then verdict[3], the rows' failure, *bad and the number of ranges.
+ */
+struct ViewLayout {
+    int64_t *size, *off, *rows_bytes, *rows_off, *verdict;
+    unsigned long long *err;
+    uint32_t *bad, *n_ranges;
+};
+static ViewLayout view_layout_of(paffy_hip_ctx *c, int64_t n) {
+    ViewLayout L;
+    int64_t *p = static_cast<int64_t *>(c->view_layout.p);
+    L.size = p;
+    L.off = p + (n + 1);
+    L.rows_bytes = p + 2 * (n + 1);
+    L.rows_off = p + 3 * (n + 1);
+    L.verdict = p + 4 * (n + 1);
+    L.err = reinterpret_cast<unsigned long long *>(L.verdict + 3);
+    L.bad = reinterpret_cast<uint32_t *>(L.verdict + 4);
+    L.n_ranges = L.bad + 1;
+    return L;
+}
+
+int paffy_hip_plan_view_layout(paffy_hip_ctx *c, int with_rows, int64_t range_bytes, int64_t *total_bytes, int64_t *n_ranges) {
+    if (!c || !total_bytes || !n_ranges || range_bytes < 1) return PAFFY_E_ARG;
+    *total_bytes = 0;
+    *n_ranges = 0;
+    c->view_laid = false;
+    if (range_bytes > (1ll << 61)) range_bytes = 1ll << 61;
+    ViewLineParams vp;
+    PrettyParams pp;
+    const int64_t n = c->planned ? c->plan.n_records : 0;
+    int rc = view_params(c, "paffy_hip_plan_view_layout", 0, n, with_rows, &vp, &pp);
+    if (rc) return rc;
+    c->view_laid_rows = with_rows != 0;
+    c->view_tab.assign(2, 0);
+    if (n == 0) {
+        c->view_laid = true;
+        return 0;
+    }
+    if (ensure(c, c->view_layout, sizeof(int64_t) * (size_t)(4 * (n + 1) + 8))) return PAFFY_E_HIP;
+    const ViewLayout L = view_layout_of(c, n);
+    HIPCHK(c, hipMemsetAsync(L.size + n, 0, sizeof(int64_t), c->stream));
+    if (with_rows) {
+        LAUNCH(c, "k_pretty_size", k_pretty_size, dim3((unsigned)n), dim3(PRETTY_NT), 0, pp, L.rows_bytes);
+        HIPCHK(c, hipMemcpyAsync(L.size, L.rows_bytes, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    }
+    LAUNCH(c, "k_view_line_size", k_view_line_size, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, vp, L.size, with_rows ? 1 : 0);
+    int64_t total = 0;
+    rc = scan64(c, L.size, (uint64_t)n + 1, L.off, &total); /* the total comes to the host; off[n] holds it on the device */
+    if (rc) return rc;
+    if (total <= range_bytes) { /* one range: nothing to cut */
+        c->view_tab.assign({0, 0, n, total});
+    } else {
+        /* two ranges in a row hold more than range_bytes, or they would be one */
+        int64_t cap = 2 * (total / range_bytes) + 3;
+        if (cap > n) cap = n;
+        if (ensure(c, c->view_ranges_dev, sizeof(ViewRange) * (size_t)(cap + 1))) return PAFFY_E_HIP;
+        ViewRange *tab = static_cast<ViewRange *>(c->view_ranges_dev.p);
+        LAUNCH(c, "k_view_range_cut", k_view_range_cut, dim3(1), dim3(64), 0, static_cast<const int64_t *>(L.off), (uint32_t)n, range_bytes, tab, (uint32_t)cap, L.n_ranges);
+        uint32_t nr = 0;
+        HIPCHK(c, hipMemcpyAsync(&nr, L.n_ranges, sizeof(nr), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (nr == 0 || (int64_t)nr > cap) {
+            c->last_error = "paffy_hip_plan_view_layout: more ranges than the sizes allow";
+            return PAFFY_E_STATE;
+        }
+        static_assert(sizeof(ViewRange) == 2 * sizeof(int64_t), "the range table is pairs of int64");
+        c->view_tab.assign(2 * ((size_t)nr + 1), 0);
+        HIPCHK(c, hipMemcpyAsync(c->view_tab.data(), tab, sizeof(ViewRange) * ((size_t)nr + 1), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->view_tab[2 * (size_t)nr] != n || c->view_tab[2 * (size_t)nr + 1] != total) {
+            c->last_error = "paffy_hip_plan_view_layout: the ranges do not end with the batch";
+            return PAFFY_E_STATE;
+        }
+    }
+    c->view_laid = true;
+    *total_bytes = total;
+    *n_ranges = (int64_t)(c->view_tab.size() / 2) - 1;
+    return 0;
+}
+
+int64_t paffy_hip_plan_view_ranges(paffy_hip_ctx *c, int64_t cap_ranges, int64_t *first_record, int64_t *first_byte) {
+    if (!c || cap_ranges < 0 || !first_record || !first_byte) return PAFFY_E_ARG;
+    if (!c->planned || !c->view_laid) return PAFFY_E_STATE;
+    const int64_t nr = (int64_t)(c->view_tab.size() / 2) - 1;
+    if (cap_ranges < nr + 1) return PAFFY_E_CAPACITY;
+    for (int64_t r = 0; r <= nr; r++) {
+        first_record[r] = c->view_tab[2 * (size_t)r];
+        first_byte[r] = c->view_tab[2 * (size_t)r + 1];
+    }
+    return nr;
+}
+
+/* range `range` of the layout into d_out, enqueued: *bytes = the range's bytes; h_verdict[3] (k_view_range_verdict) is written when the
+   context's stream gets there */
+static int view_emit_range(paffy_hip_ctx *c, int64_t range, void *d_out, int64_t out_cap, int64_t *bytes, int64_t *h_verdict) {
+    if (!c->planned || !c->view_laid) {
+        c->last_error = "paffy_hip_plan_view_emit_range: no paffy_hip_plan_view_layout of the current plan";
+        return PAFFY_E_STATE;
+    }
+    const int64_t nr = (int64_t)(c->view_tab.size() / 2) - 1;
+    if (range < 0 || range >= nr) return PAFFY_E_ARG;
+    const int64_t first = c->view_tab[2 * (size_t)range], count = c->view_tab[2 * (size_t)range + 2] - first;
+    const int64_t base = c->view_tab[2 * (size_t)range + 1], len = c->view_tab[2 * (size_t)range + 3] - base;
+    if (!d_out) return PAFFY_E_ARG;
+    if (len > out_cap) return PAFFY_E_CAPACITY;
+    const bool with_rows = c->view_laid_rows;
+    ViewLineParams vp;
+    PrettyParams pp;
+    int rc = view_params(c, "paffy_hip_plan_view_emit_range", first, count, with_rows, &vp, &pp);
+    if (rc) return rc;
+    const ViewLayout L = view_layout_of(c, c->plan.n_records);
+    HIPCHK(c, hipMemsetAsync(L.bad, 0, sizeof(uint32_t), c->stream));
+    vp.off = L.off + first;
+    vp.off_base = base;
+    vp.rows_bytes = with_rows ? L.rows_bytes + first : nullptr;
+    vp.rows_off = with_rows ? L.rows_off + first : nullptr;
+    vp.out = static_cast<uint8_t *>(d_out);
+    vp.out_cap = len;
+    vp.bad = L.bad;
+    LAUNCH(c, "k_view_line_emit", k_view_line_emit, dim3((unsigned)((count + VIEW_LINE_WAVES - 1) / VIEW_LINE_WAVES)), dim3(64 * VIEW_LINE_WAVES), 0, vp);
+    if (with_rows) { /* the offsets are the layout's own: the rows go where the lines left them room */
+        HIPCHK(c, hipMemsetAsync(L.err, 0xff, sizeof(unsigned long long), c->stream));
+        pp.row_off = L.rows_off + first;
+        pp.out = static_cast<uint8_t *>(d_out);
+        pp.err = L.err;
+        LAUNCH(c, "k_pretty_rows", k_pretty_rows, dim3((unsigned)count), dim3(PRETTY_NT), 0, pp);
+    }
+    LAUNCH(c, "k_view_range_verdict", k_view_range_verdict, dim3(1), dim3(64), 0, with_rows ? L.err : nullptr, static_cast<const uint32_t *>(L.bad),
+           static_cast<const int64_t *>(L.off), static_cast<const int64_t *>(L.size), static_cast<const int64_t *>(L.rows_bytes), base, L.verdict);
+    HIPCHK(c, hipMemcpyAsync(h_verdict, L.verdict, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    *bytes = len;
+    return 0;
+}
+
+/* what a verdict says: PAFFY_E_STATE for refused offsets; a rows failure in *err with *bytes = what the reference had printed of the range */
+static int view_verdict(paffy_hip_ctx *c, const int64_t *h_verdict, int64_t *bytes, paffy_error *err) {
+    memset(err, 0, sizeof(*err));
+    if (h_verdict[2]) {
+        c->last_error = "paffy_hip_plan_view_emit_range: a record's offsets are not the running sums of its size";
+        return PAFFY_E_STATE;
+    }
+    if (h_verdict[0] != -1) {
+        const unsigned long long e = (unsigned long long)h_verdict[0];
+        err->code = (int32_t)(e & 0xff);
+        err->record = (int64_t)(e >> 8);
+        err->stage = -1;
+        *bytes = h_verdict[1];
+    }
+    return 0;
+}
+
+int paffy_hip_plan_view_emit_range(paffy_hip_ctx *c, int64_t range, void *d_out, int64_t out_cap, int64_t *bytes, paffy_error *err) {
+    if (!c || !bytes || !err) return PAFFY_E_ARG;
+    memset(err, 0, sizeof(*err));
+    *bytes = 0;
+    int64_t verdict[3] = {-1, -1, 0};
+    int rc = view_emit_range(c, range, d_out, out_cap, bytes, verdict);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return view_verdict(c, verdict, bytes, err);
+}
+
+/*
+ * ---- a stream in view mode: the chunks go through [PAFFY_ADD_MISMATCHES, PAFFY_STATS], what comes back is the view text ----
+ * A chunk of one range (the common case) pipelines like any other chunk. A chunk of more ranges is "open": its later ranges are written into
+ * the slot's output buffer by paffy_hip_stream_read, each once the pieces of the range before it have arrived, and the plan they are written
+ * from must stay -- paffy_hip_stream_input answers NULL until the chunk is read out.
+ */
+int paffy_hip_stream_open_view(paffy_hip_ctx *c, int text, int64_t chunk_bytes, int64_t piece_bytes, int64_t range_bytes, paffy_hip_stream **out) {
+    if (!c || !out || text < 0 || text > 2 || range_bytes < 1) return PAFFY_E_ARG;
+    const paffy_stage st[2] = {{PAFFY_ADD_MISMATCHES, 0.05f, 1.0f}, {PAFFY_STATS, 0.0f, 0.0f}};
+    paffy_hip_stream *s = nullptr;
+    int rc = paffy_hip_stream_open(c, st, 2, chunk_bytes, piece_bytes, &s);
+    if (rc) return rc;
+    s->view_text = text;
+    s->view_range_bytes = range_bytes;
+    for (int k = 0; k < 2; k++)
+        if (hipHostMalloc(reinterpret_cast<void **>(&s->slot[k].h_verdict), 4 * sizeof(int64_t)) != hipSuccess) {
+            c->last_error = "paffy_hip_stream_open_view: pinned buffers";
+            paffy_hip_stream_close(s);
+            return PAFFY_E_HIP;
+        }
+    *out = s;
+    return 0;
+}
+
+int paffy_hip_stream_view_status(paffy_hip_stream *s, int64_t sums[6], int64_t *n_records, paffy_error *rows_err) {
+    if (!s || !sums || !n_records || !rows_err) return PAFFY_E_ARG;
+    if (s->view_text < 0) return PAFFY_E_STATE;
+    for (int k = 0; k < 6; k++) sums[k] = s->view_sums[k];
+    *n_records = s->view_records;
+    *rows_err = s->view_rows_err;
+    return 0;
+}
+
+static int view_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_info *info) {
+    paffy_hip_ctx *c = s->c;
+    if (!c) return PAFFY_E_STATE;
+    StreamSlot &sl = s->slot[s->fill];
+    if (s->view_failed) {
+        c->last_error = "paffy_hip_stream_submit: the rows of an earlier chunk failed (paffy_hip_stream_view_status)";
+        return PAFFY_E_STATE;
+    }
+    if (sl.busy || s->view_open || in_len > (int64_t)sl.h_cap) return PAFFY_E_STATE;
+    int rc = stream_stage_in(s, sl, in_len);
+    if (!rc) rc = paffy_hip_plan(c, s->stages, s->n_stages, sl.d_in, in_len, info);
+    if (rc) return rc;
+    sl.out_len = sl.read_at = 0;
+    sl.view_ranges = sl.view_range_at = 0;
+    sl.verdict_seen = sl.view_open = false;
+    info->out_bytes = 0;
+    info->n_rows = 0;
+    if (info->error.code == 0) {
+        int64_t sums[6];
+        rc = paffy_hip_plan_stats(c, sums);
+        if (rc) return rc;
+        for (int k = 0; k < 6; k++) s->view_sums[k] += sums[k];
+        s->view_records += info->n_records;
+        if (s->view_text > 0 && info->n_records > 0) {
+            int64_t total = 0, nr = 0, longest = 0;
+            rc = paffy_hip_plan_view_layout(c, s->view_text == 2, s->view_range_bytes, &total, &nr);
+            if (rc) return rc;
+            for (int64_t r = 0; r < nr; r++) longest = std::max(longest, c->view_tab[2 * (size_t)r + 3] - c->view_tab[2 * (size_t)r + 1]);
+            rc = stream_out_room(c, sl, longest, nr == 1);
+            if (!rc) rc = view_emit_range(c, 0, sl.d_out, (int64_t)sl.d_out_cap, &sl.out_len, sl.h_verdict);
+            if (rc) return rc;
+            sl.view_ranges = nr;
+            info->out_bytes = total;
+            info->n_rows = info->n_records;
+            sl.view_open = s->view_open = nr > 1;
+        }
+    } else if (s->view_text > 0) {
+        /* a chunk with a failing record writes nothing. What is reported is the first line that does not parse, if there is one, before
+           the first record the stages fail on -- the order the reference reads and works in: a plan of the parse alone tells */
+        const paffy_stage pass = {PAFFY_PASS, 0.0f, 0.0f};
+        paffy_plan_info parsed;
+        if (paffy_hip_plan(c, &pass, 1, sl.d_in, in_len, &parsed) == 0 && parsed.error.code) {
+            *info = parsed;
+            info->out_bytes = 0;
+            info->n_rows = 0;
+        }
+    }
+    return stream_submitted(s, sl);
+}
+
+static int view_stream_read(paffy_hip_stream *s, const char **piece, int64_t *len) {
+    paffy_hip_ctx *c = s->c;
+    *piece = nullptr;
+    *len = 0;
+    if (!c) return PAFFY_E_STATE;
+    StreamSlot &sl = s->slot[s->drain];
+    if (!sl.busy) return 0;
+    for (;;) {
+        if (sl.view_ranges > 0 && !sl.verdict_seen) { /* the range in d_out is written: what its writers found */
+            HIPCHK(c, hipStreamWaitEvent(s->s_d2h, sl.ev_emit, 0));
+            HIPCHK(c, hipEventSynchronize(sl.ev_emit));
+            sl.verdict_seen = true;
+            paffy_error e;
+            int rc = view_verdict(c, sl.h_verdict, &sl.out_len, &e);
+            if (rc) return rc;
+            if (e.code) { /* the text ends with the failing record's stats line; no later range is written */
+                s->view_rows_err = e;
+                s->view_failed = true;
+                sl.view_ranges = sl.view_range_at + 1;
+            }
+        }
+        int rc = stream_issue_pieces(s, sl);
+        if (rc) return rc;
+        if (s->n_returned < s->n_issued) break;
+        /* every piece of the range has arrived: the next range may take its place in d_out */
+        if (sl.view_range_at + 1 < sl.view_ranges) {
+            sl.view_range_at++;
+            s->issued_at = 0;
+            sl.verdict_seen = false;
+            rc = view_emit_range(c, sl.view_range_at, sl.d_out, (int64_t)sl.d_out_cap, &sl.out_len, sl.h_verdict);
+            if (rc) return rc;
+            HIPCHK(c, hipEventRecord(sl.ev_emit, c->stream));
+            continue;
+        }
+        if (sl.view_open) sl.view_open = s->view_open = false; /* the chunk has been read out */
+        stream_chunk_done(s, sl);
+        return 0;
+    }
+    return stream_hand_out(s, piece, len);
 }
 
 int paffy_hip_parse_host(paffy_hip_ctx *c, const char *h_in, int64_t in_len, paffy_record **recs, uint64_t **ops, int64_t *n_ops_total,

@@ -95,7 +95,9 @@ __global__ __launch_bounds__(PRETTY_NT) void k_pretty_size(PrettyParams P, int64
     const RecMeta m = P.meta[rec];
     const RecPlan pl = P.plan[rec];
     int64_t cols = 0;
-    if ((pl.flags & 8u) && pl.n != 0) cols = pretty_columns(P, m, pl, rec, tmp);
+    /* a record that was read without a cigar has none behind any stage list; its RecPlan is not looked at (a sizing pass that left the
+       record to nobody would have left the plan of an earlier batch there) */
+    if (m.has_cg && m.cg_len > 0 && (pl.flags & 8u) && pl.n != 0) cols = pretty_columns(P, m, pl, rec, tmp);
     if (cols < 0) cols = 0;
     if (threadIdx.x == 0) bytes[blockIdx.x] = 3 * cols + 3 * ((cols + PRETTY_WINDOW - 1) / PRETTY_WINDOW);
 }
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(PRETTY_NT) void k_pretty_rows(PrettyParams P) {
     const uint32_t rec = P.first + blockIdx.x, t = threadIdx.x;
     const RecMeta m = P.meta[rec];
     const RecPlan pl = P.plan[rec];
-    if (!(pl.flags & 8u) || pl.n == 0) return; /* cigar_count(NULL) == 0: no rows */
+    if (!m.has_cg || m.cg_len == 0 || !(pl.flags & 8u) || pl.n == 0) return; /* cigar_count(NULL) == 0: no rows */
     const bool swapped = (pl.flags & 4u) != 0, rev = (pl.flags & 1u) != 0, swp = (pl.flags & 2u) != 0;
     const int32_t qi = swapped ? P.rec_tseq[rec] : P.rec_qseq[rec], ti = swapped ? P.rec_qseq[rec] : P.rec_tseq[rec];
     if (qi < 0 || ti < 0) {

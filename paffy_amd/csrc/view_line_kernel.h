@@ -23,6 +23,18 @@
  * n = __double2ll_rn(q * 1e6) printed as n / 10^6, '.', and the six digits of n % 10^6; n == 10^6 gives "1.000000".
  *
  * The emit kernel trusts no offset: a record whose off[i + 1] - off[i] is not the size of its block writes nothing and raises *bad.
+ *
+ * The layout of a whole batch stays on the device (paffy_hip_plan_view_layout): the blocks' sizes, their n + 1 running sums, and the
+ * ranges of records the text is fetched in.
+ *
+ *   k_view_range_cut      one wave: the batch's records cut into ranges of at most range_bytes of text, greedily from record 0 (a range
+ *                         takes records while the sum stays within range_bytes, and one record at least). The ranges depend on each
+ *                         other in turn, so the wave walks them; what it searches is the end of each -- the last offset within
+ *                         off[first] + range_bytes -- with 64 probes per step (a ballot gives the stretch to search next: three
+ *                         steps for 200 000 records). It writes {first record, first byte} per range and the closing {n, total}.
+ *   k_view_range_verdict  one lane behind the writers of a range: the rows' failure, the bytes the reference would have printed of the
+ *                         range by then (every block in front of the failing record and that record's stats line) and *bad, in three
+ *                         int64 the host reads with one copy -- after the next plan has replaced the offsets, if it likes.
  */
 #ifndef PAFFY_VIEW_LINE_KERNEL_H_
 #define PAFFY_VIEW_LINE_KERNEL_H_
@@ -64,7 +76,8 @@ struct ViewLineParams {
     const int64_t *rec_stats; /* six sums per record */
     uint32_t first, count;    /* records [first, first + count) of the batch */
     /* k_view_line_emit */
-    const int64_t *off;        /* count + 1: record first + i is written at out + off[i] */
+    const int64_t *off;        /* count + 1: record first + i is written at out + off[i] - off_base */
+    int64_t off_base;          /* 0, or the first byte of the range when off[] are the offsets of the whole batch */
     const int64_t *rows_bytes; /* with rows: the bytes of each record's rows (k_pretty_size); NULL without */
     int64_t *rows_off;         /* with rows: where k_pretty_rows writes them, off[i] + the line's bytes */
     uint8_t *out;
@@ -152,10 +165,10 @@ __global__ __launch_bounds__(64 * VIEW_LINE_WAVES) void k_view_line_emit(ViewLin
     const uint32_t ex1 = (uint32_t)__builtin_amdgcn_readlane((int)ex, 1), ex4 = (uint32_t)__builtin_amdgcn_readlane((int)ex, 4);
     const uint32_t n0 = ex1, n1 = ex4 - ex1, n2 = total - ex4; /* the three stretches */
     const int64_t line = (int64_t)total + m.qname_len + m.tname_len;
-    const int64_t at_out = P.off[i];
+    const int64_t at_out = P.off[i] - P.off_base;
     const int64_t want = line + (P.rows_bytes ? P.rows_bytes[i] : 0);
     if (P.rows_off && lane == 0) P.rows_off[i] = at_out + line;
-    if (at_out < 0 || P.off[i + 1] - at_out != want || at_out + want > P.out_cap || n0 > VIEW_LINE_SEG1 || n1 > VIEW_LINE_SEG2 - VIEW_LINE_SEG1 || n2 > VIEW_LINE_LDS - VIEW_LINE_SEG2) {
+    if (at_out < 0 || P.off[i + 1] - P.off_base - at_out != want || at_out + want > P.out_cap || n0 > VIEW_LINE_SEG1 || n1 > VIEW_LINE_SEG2 - VIEW_LINE_SEG1 || n2 > VIEW_LINE_LDS - VIEW_LINE_SEG2) {
         if (lane == 0) atomicOr(P.bad, 1u);
         return;
     }
@@ -191,6 +204,63 @@ __global__ __launch_bounds__(64 * VIEW_LINE_WAVES) void k_view_line_emit(ViewLin
     view_copy_name(o, P.in + m.tname_off, m.tname_len, lane);
     o += m.tname_len;
     view_copy_lds(o, H + VIEW_LINE_SEG2, n2, lane);
+}
+
+/* ---- the layout of a batch: ranges of records of at most range_bytes of text ---- */
+struct ViewRange {
+    int64_t rec, byte; /* the range's first record and the offset of its first byte in the batch's text */
+};
+
+/* off: n + 1 running sums (off[0] = 0). tab: room for cap + 1 entries; more ranges than cap leave *n_ranges = cap + 1 and no closing entry */
+__global__ __launch_bounds__(64) void k_view_range_cut(const int64_t *off, uint32_t n, int64_t range_bytes, ViewRange *tab, uint32_t cap, uint32_t *n_ranges) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t r = 0, first = 0;
+    while (first < n) {
+        if (r >= cap) {
+            if (lane == 0) *n_ranges = cap + 1u;
+            return;
+        }
+        const int64_t at = off[first], limit = at + range_bytes;
+        if (lane == 0) {
+            tab[r].rec = (int64_t)first;
+            tab[r].byte = at;
+        }
+        /* the last end in [first + 1, n] with off[end] <= limit; first + 1 whatever its offset */
+        uint32_t lo = first + 1u, hi = n;
+        while (hi > lo) {
+            const uint32_t step = (hi - lo + 63u) / 64u;
+            const uint64_t probe = (uint64_t)lo + (uint64_t)(lane + 1u) * step;
+            const uint32_t p = probe < hi ? (uint32_t)probe : hi;
+            const uint32_t k = (uint32_t)__popcll(__ballot(off[p] <= limit)); /* the offsets only grow: the lanes that hold are the first k */
+            const uint64_t nlo = (uint64_t)lo + (uint64_t)k * step, nhi = (uint64_t)lo + (uint64_t)(k + 1u) * step;
+            const uint32_t lo2 = k == 0u ? lo : (nlo < hi ? (uint32_t)nlo : hi);
+            hi = k == 64u ? lo2 : (nhi < hi ? (uint32_t)nhi : hi) - 1u;
+            lo = lo2;
+        }
+        first = lo;
+        r++;
+    }
+    if (lane == 0) {
+        tab[r].rec = (int64_t)n;
+        tab[r].byte = off[n];
+        *n_ranges = r;
+    }
+}
+
+/* verdict[0]: the rows' failure (record << 8 | code; -1 none), [1]: the bytes of the range the reference would have printed before it
+   (-1 none), [2]: whether a record's offsets were refused */
+__global__ __launch_bounds__(64) void k_view_range_verdict(const unsigned long long *err, const uint32_t *bad, const int64_t *off, const int64_t *size,
+                                                           const int64_t *rows_bytes, int64_t off_base, int64_t *verdict) {
+    if (threadIdx.x != 0) return;
+    const unsigned long long e = err ? *err : ~0ull;
+    int64_t printed = -1;
+    if (e != ~0ull) {
+        const uint64_t rec = e >> 8;
+        printed = off[rec] - off_base + size[rec] - rows_bytes[rec];
+    }
+    verdict[0] = (int64_t)e;
+    verdict[1] = printed;
+    verdict[2] = (int64_t)*bad;
 }
 
 #endif

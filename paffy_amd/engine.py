@@ -224,6 +224,12 @@ def lib():
         L.paffy_hip_plan_alignment_rows.argtypes = [vp, i64, i64, C.POINTER(i64), C.c_void_p, C.POINTER(_Error)]
         L.paffy_hip_plan_view_sizes.argtypes = [vp, i64, i64, C.c_int, C.POINTER(i64)]
         L.paffy_hip_plan_view_text.argtypes = [vp, i64, i64, C.c_int, C.POINTER(i64), vp, i64, C.POINTER(_Error)]
+        L.paffy_hip_plan_view_layout.argtypes = [vp, C.c_int, i64, C.POINTER(i64), C.POINTER(i64)]
+        L.paffy_hip_plan_view_ranges.restype = i64
+        L.paffy_hip_plan_view_ranges.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64)]
+        L.paffy_hip_plan_view_emit_range.argtypes = [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(_Error)]
+        L.paffy_hip_stream_open_view.argtypes = [vp, C.c_int, i64, i64, i64, C.POINTER(vp)]
+        L.paffy_hip_stream_view_status.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(_Error)]
         _lib = L
     return _lib
 
@@ -963,6 +969,84 @@ class Engine:
             self.stream_seconds["close"] = time.perf_counter() - t_close
         return records, out_bytes
 
+    # ---- `paffy view` as a stream: the layout of every chunk's text stays on the device ----
+    def view_layout(self, with_rows=False, range_bytes=128 << 20):
+        """Lay out the view text of the last plan on the device (paffy_hip_plan_view_layout): (total bytes, ranges), ranges being the
+        n_ranges + 1 pairs (first record, first byte), the last one (n_records, total)."""
+        L = lib()
+        total, nr = C.c_int64(), C.c_int64()
+        self._check(L.paffy_hip_plan_view_layout(self._ctx, 1 if with_rows else 0, range_bytes, C.byref(total), C.byref(nr)), "paffy_hip_plan_view_layout")
+        rec, byte = (C.c_int64 * (nr.value + 1))(), (C.c_int64 * (nr.value + 1))()
+        got = L.paffy_hip_plan_view_ranges(self._ctx, nr.value + 1, rec, byte)
+        if got != nr.value:
+            raise RuntimeError(f"paffy_hip_plan_view_ranges: {got} for {nr.value} ranges")
+        return total.value, list(zip(rec, byte))
+
+    def view_emit_range(self, rng, nbytes, guard=0, out_cap=None):
+        """Range `rng` of that layout, written on the device and copied back: (bytes, None) or, when the rows of a record fail, (what the
+        reference had printed of the range by then, (code, record in the batch)). nbytes: the range's bytes; guard as in view_text."""
+        t = self.torch
+        lead = (guard + 15) // 16 * 16
+        buf = t.full((lead + nbytes + guard + 16,), 0xA5, dtype=t.uint8, device=self.device)
+        err, n = _Error(), C.c_int64()
+        rc = lib().paffy_hip_plan_view_emit_range(self._ctx, rng, C.c_void_p(buf.data_ptr() + lead), nbytes if out_cap is None else out_cap, C.byref(n), C.byref(err))
+        self._check(rc, "paffy_hip_plan_view_emit_range")
+        host = buf.cpu().numpy().tobytes()
+        assert host[:lead] == b"\xa5" * lead and host[lead + nbytes:] == b"\xa5" * (guard + 16), "paffy_hip_plan_view_emit_range wrote outside its destination"
+        return host[lead:lead + n.value], ((err.code, err.record) if err.code else None)
+
+    def open_view_stream(self, text=1, chunk_bytes=1 << 20, range_bytes=128 << 20, piece_bytes=None):
+        """A stream in view mode (paffy_hip_stream_open_view) as an object: input / submit / read / status / close."""
+        return ViewStream(self, text, chunk_bytes, range_bytes, piece_bytes or getattr(self, "stream_piece_bytes", 64 << 20))
+
+    def view_stream(self, chunks, text=1, range_bytes=128 << 20, sink=None, piece_bytes=None):
+        """What `bin/paffy view` does with its input: host chunks (bytes of whole lines) through a stream in view mode, chunk k + 1
+        submitted before chunk k is drained, a chunk of more than one range drained before the next buffer is asked for. text: 0 sums
+        only, 1 stats lines, 2 lines and base-level rows. sink(piece) gets the text in order (default: it is collected). Returns a dict:
+        text (bytes; None with a sink), sums (six), records, error (None, or (code, record counted from the stream's first record, aux,
+        stage) of the failure that ends the run -- a chunk's failing record, or the rows' failure with stage -1 -- after which nothing
+        more is read), open_chunks (how many chunks had more than one range)."""
+        parts = []
+        put = sink or parts.append
+        st = self.open_view_stream(text, max(4096, max((len(c) for c in chunks), default=4096)), range_bytes, piece_bytes)
+        error, open_chunks, records_done = None, 0, 0
+        pending = None  # the record base of the chunk not yet drained
+
+        def drain(base):
+            for piece in st.pieces():
+                put(piece)
+            rows = st.status()[2]
+            return (rows[0], base + rows[1], 0, -1) if rows else None
+
+        try:
+            for chunk in chunks:
+                if not st.input(chunk):  # the chunk before is open: read it out first
+                    open_chunks += 1
+                    error = drain(pending)
+                    pending = None
+                    if error:
+                        break
+                    if not st.input(chunk):
+                        raise RuntimeError("paffy_hip_stream_input: no buffer behind a drained chunk")
+                info = st.submit(len(chunk))
+                if pending is not None:
+                    error = drain(pending)  # the earlier failure speaks
+                    if error:
+                        break
+                pending = records_done
+                if info.error.code:
+                    drain(pending)
+                    pending = None
+                    error = (info.error.code, records_done + info.error.record, info.error.aux, info.error.stage)
+                    break
+                records_done += info.n_records
+            if pending is not None and not error:
+                error = drain(pending)
+            sums, records, _ = st.status()
+        finally:
+            st.close()
+        return {"text": None if sink else b"".join(parts), "sums": sums, "records": records, "error": error, "open_chunks": open_chunks}
+
     # ---- faffy chunk / extract / merge (FASTA index + item emit) ----
     def fasta_index(self, d_text, text_len, file_starts=(0,)):
         """Index FASTA text on the device (files back to back from file_starts); returns (records, bases). d_text must stay alive
@@ -1145,6 +1229,53 @@ class Engine:
 
 
 _default = None
+
+
+class ViewStream:
+    """paffy_hip_stream_open_view and the stream calls, one to one (Engine.open_view_stream)."""
+
+    def __init__(self, engine, text, chunk_bytes, range_bytes, piece_bytes):
+        self._e = engine
+        self._st = C.c_void_p()
+        engine._check(lib().paffy_hip_stream_open_view(engine._ctx, text, max(4096, chunk_bytes), piece_bytes, range_bytes, C.byref(self._st)), "paffy_hip_stream_open_view")
+
+    def input(self, chunk):
+        """Copies chunk into the next input buffer; False when paffy_hip_stream_input gives none (NULL)."""
+        cap = C.c_int64()
+        buf = lib().paffy_hip_stream_input(self._st, len(chunk), 0, C.byref(cap))
+        if not buf:
+            return False
+        C.memmove(buf, chunk, len(chunk))
+        return True
+
+    def submit_rc(self, n):
+        info = PlanInfo()
+        return lib().paffy_hip_stream_submit(self._st, n, C.byref(info)), info
+
+    def submit(self, n):
+        rc, info = self.submit_rc(n)
+        self._e._check(rc, "paffy_hip_stream_submit")
+        return info
+
+    def pieces(self):
+        """The pieces of the oldest submitted chunk, until it is read out."""
+        while True:
+            piece, n = C.c_void_p(), C.c_int64()
+            self._e._check(lib().paffy_hip_stream_read(self._st, C.byref(piece), C.byref(n)), "paffy_hip_stream_read")
+            if n.value == 0:
+                return
+            yield C.string_at(piece.value, n.value)
+
+    def status(self):
+        """(six sums, records, None or (code, record) of the rows' failure of the chunk read last)."""
+        sums, n, err = (C.c_int64 * 6)(), C.c_int64(), _Error()
+        self._e._check(lib().paffy_hip_stream_view_status(self._st, sums, C.byref(n), C.byref(err)), "paffy_hip_stream_view_status")
+        return list(sums), n.value, ((err.code, err.record) if err.code else None)
+
+    def close(self):
+        if self._st:
+            lib().paffy_hip_stream_close(self._st)
+            self._st = C.c_void_p()
 
 
 def _engine():

@@ -1269,3 +1269,60 @@ def dedupe_sharded(worker, dist, rank, world, rounds, check_inverse, first_recor
         else:
             gather_to_writer(dist, rank, world, {b: _comm(t, comm_device) for b, t in local.items()}, sizes, write, comm_device, writer)
     return {"error": error, "total": sum(sizes), "sizes": sizes, "local": local}
+
+
+# ---- `paffy view` behind PAFFY_GPUS=N (host/paffy_launch.c, run_stream with the view totals) ----
+def stream_cuts(data, n):
+    """The launcher's cut of a stream command's input: n contiguous byte ranges, range r from the first line end at or after
+    len(data) // n * r (never in front of the cut before it). Returns n + 1 offsets."""
+    size = len(data)
+    cuts = [0]
+    for r in range(1, n):
+        pos = max(size // n * r, cuts[-1])
+        nl = data.find(b"\n", pos)
+        cuts.append(size if nl < 0 else nl + 1)
+    cuts.append(size)
+    return cuts
+
+
+def view_in_parts(data, seqs, n, text=1, range_bytes=128 << 20, chunk_bytes=None, engine=None):
+    """`PAFFY_GPUS=n paffy view` without processes: the launcher's cut of `data` (stream_cuts), the parts taken in turn on one engine --
+    each through a stream in view mode of its own, as a worker would, in chunks of whole lines of at most chunk_bytes (default: a part
+    is one chunk) --, their texts put together in part order and their sums added up, as the launcher adds up the workers' sums files.
+    A failing part ends the run: the text of the parts before it and its own stays. seqs: {name: bases}; text: 0 sums only, 1 stats
+    lines, 2 lines and base-level rows. Returns {"text", "sums", "records", "error": None or (part, the failure Engine.view_stream
+    reports, its record counted from the part's first record), "parts": records per part}."""
+    from . import engine as E
+
+    eng = engine or E.Engine()
+    try:
+        if text == 2:
+            eng.keep_raw_sequences(True)
+        eng.stats_only(text != 2)
+        eng.set_sequences(seqs)
+        cuts = stream_cuts(data, n)
+        texts, sums, records, error, parts = [], [0] * 6, 0, None, []
+        for r in range(n):
+            part = data[cuts[r]:cuts[r + 1]]
+            chunks = [part] if part else []
+            if chunk_bytes and part:
+                chunks, lines, cur = [], part.splitlines(keepends=True), b""
+                for ln in lines:
+                    if cur and len(cur) + len(ln) > chunk_bytes:
+                        chunks.append(cur)
+                        cur = b""
+                    cur += ln
+                if cur:
+                    chunks.append(cur)
+            got = eng.view_stream(chunks, text=text, range_bytes=range_bytes)
+            texts.append(got["text"])
+            if got["error"]:
+                error = (r, got["error"])
+                break
+            sums = [a + b for a, b in zip(sums, got["sums"])]
+            records += got["records"]
+            parts.append(got["records"])
+        return {"text": b"".join(texts), "sums": sums, "records": records, "error": error, "parts": parts}
+    finally:
+        if engine is None:
+            eng.close()
