@@ -66,16 +66,14 @@ struct FlatParams {
     uint32_t items_mode; /* the MODE of k_flat_parse: what PieceSum::extra counts (the host picks the instantiation by it) */
 };
 
+/* a + the sum of the products of the four bytes of x and of w: one v_dot4_u32_u8 */
+__device__ __forceinline__ uint32_t udot4(uint32_t x, uint32_t w, uint32_t a) { return __builtin_amdgcn_udot4(x, w, a, false); }
 __device__ __forceinline__ uint32_t nondigit16(const uint4 &v) { /* bit j: byte j of the 16 is not an ASCII digit */
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t m = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        uint32_t nd = nondigit4(w[j]) >> 7;
-        nd = (nd | (nd >> 7) | (nd >> 14) | (nd >> 21)) & 0xfu;
-        m |= nd << (4 * j);
-    }
-    return m;
+    /* nondigit4 leaves 0x80 per such byte: a dot product with the bytes' bit weights gathers a word's four flags in one instruction,
+       128 times too large; two words share a sum (8 bits of flags times 128 stay below 2^16) */
+    const uint32_t lo = udot4(nondigit4(v.y), 0x80402010u, udot4(nondigit4(v.x), 0x08040201u, 0u));
+    const uint32_t hi = udot4(nondigit4(v.w), 0x80402010u, udot4(nondigit4(v.z), 0x08040201u, 0u));
+    return (hi << 1) | (lo >> 7);
 }
 /* sum over the wave: six DPP adds leave it in lane 63 (an inclusive scan takes nine instructions) */
 __device__ __forceinline__ uint32_t wave_fold_u32(uint32_t x) {
@@ -88,10 +86,11 @@ __device__ __forceinline__ uint32_t wave_fold_u32(uint32_t x) {
     return x;
 }
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return wave_last_u32(wave_fold_u32(v)); }
-/* six sums at once, step by step: the chains are independent, so no DPP instruction waits for the one before it */
-__device__ __forceinline__ void wave_sum6_u32(uint32_t (&x)[6]) {
+/* N sums at once, step by step: the chains are independent, so no DPP instruction waits for the one before it */
+template <int N>
+__device__ __forceinline__ void wave_sums_u32(uint32_t (&x)[N]) {
 #define FLAT_FOLD_STEP(CTRL, RM)                                                  \
-    _Pragma("unroll") for (int k = 0; k < 6; k++) x[k] += dpp_mov_u32<CTRL, RM, 0xf>(x[k]);
+    _Pragma("unroll") for (int k = 0; k < N; k++) x[k] += dpp_mov_u32<CTRL, RM, 0xf>(x[k]);
     FLAT_FOLD_STEP(DPP_ROW_SHR(1), 0xf)
     FLAT_FOLD_STEP(DPP_ROW_SHR(2), 0xf)
     FLAT_FOLD_STEP(DPP_ROW_SHR(4), 0xf)
@@ -100,14 +99,26 @@ __device__ __forceinline__ void wave_sum6_u32(uint32_t (&x)[6]) {
     FLAT_FOLD_STEP(DPP_BCAST31, 0xc)
 #undef FLAT_FOLD_STEP
 #pragma unroll
-    for (int k = 0; k < 6; k++) x[k] = wave_last_u32(x[k]);
+    for (int k = 0; k < N; k++) x[k] = wave_last_u32(x[k]);
 }
+__device__ __forceinline__ void wave_sum6_u32(uint32_t (&x)[6]) { wave_sums_u32<6>(x); }
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 __device__ __forceinline__ uint32_t lane_val(uint32_t x, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)l); }
 
-/* bytes of LDS per wave: 16 bytes in front of the tile (the text before it), the tile, the positions of its op letters */
-#define FLAT_PARSE_LDS (16u + FLAT_TILE + 2u * FLAT_P_CAP)
+/* LDS of one parse wave: 16 bytes in front of the tile (the text before it), the tile, then the list of its op letters: one 16-bit entry
+   per letter (a lane's 16 bytes can all be letters, so the list never overflows and the loop that fills it tests nothing), with one
+   entry in front of the list for the last letter before the tile. An entry is the offset, from the start of the kernel's LDS, of the
+   four bytes in front of the letter: the op loop reads text and neighbours by it without adding a base. */
+#define FLAT_P_SLOTS FLAT_TILE
+#define FLAT_PARSE_PL (16u + FLAT_TILE + 16u) /* the list's entry 0; entry -1 lies in the 16 bytes in front of it */
+#define FLAT_PARSE_LDS (FLAT_PARSE_PL + 2u * FLAT_P_SLOTS)
 #define FLAT_PARSE_WAVES 4u
+/* letter -> code (impl/paf.c:96-103) by bits 2..4 of the letter: 'D' 0x44, 'I' 0x49, 'M' 0x4d, 'X' 0x58, '=' 0x3d have 1, 2, 3, 6, 7 there.
+   FLAT_CODE_TAB holds a nibble per value (7: no letter of MID=X has it); FLAT_CODE_LETTERS_* the letter per code for v_perm_b32, by which
+   a trip of the op loop checks that the byte is the letter its code stands for */
+#define FLAT_CODE_TAB 0x34770127u
+#define FLAT_CODE_LETTERS_LO 0x3d44494du /* codes 0..3: M I D = */
+#define FLAT_CODE_LETTERS_HI 0xffffff58u /* code 4: X; 5..7: no byte maps to them and is 0xff */
 /* MODE = what PieceSum::extra counts: 0 the digits of the M ops' lengths beyond the first (shatter's row bytes), 1 the 16-column chunks of the M
    ops (add_mismatches, flat_add_kernel.h), 2 the I ops (the counts of paf_stats_calc, impl/paf.c:236-260) */
 template <uint32_t MODE>
@@ -116,8 +127,10 @@ __global__ __launch_bounds__(64 * FLAT_PARSE_WAVES) void k_flat_parse(FlatParams
     /* the wave's number, in a scalar register: everything derived from it (the chunk, its record, the tile addresses) is wave-uniform,
        and the compiler only knows that when it is told */
     const uint32_t lane = threadIdx.x & 63u, wave = uni(threadIdx.x >> 6);
+    uint8_t *const L = &smem[0][0];
     uint8_t *T = smem[wave];
-    uint16_t *Pl = reinterpret_cast<uint16_t *>(T + 16u + FLAT_TILE);
+    const uint32_t ebase = wave * FLAT_PARSE_LDS + 12u;          /* list entry of the letter at byte 0 of the tile */
+    const uint32_t pl0 = wave * FLAT_PARSE_LDS + FLAT_PARSE_PL;  /* LDS offset of the list's entry 0 */
     const uint32_t n_waves = gridDim.x * FLAT_PARSE_WAVES;
     for (uint32_t c = blockIdx.x * FLAT_PARSE_WAVES + wave; c < F.n_chunk_slots; c += n_waves) {
         const uint32_t rec = F.chunk_rec[c];
@@ -159,7 +172,11 @@ __global__ __launch_bounds__(64 * FLAT_PARSE_WAVES) void k_flat_parse(FlatParams
             prev = hm ? (int32_t)(31 - __clz((int)hm)) - 16 : -17; /* no letter within 16 bytes: the first number of the chunk counts as too long */
             text_end = (uint32_t)((int32_t)(tile << FLAT_TILE_SHIFT) + prev + 1 - (int32_t)cg_off);
         }
-        uint16_t *dst = reinterpret_cast<uint16_t *>(F.ops_mirror + (cg_off >> 1));
+        /* the mirror word of op i of a tile is stored at the LDS offset of the list entry in front of it, from a base that takes the
+           difference up: a scalar base and a 32-bit lane offset, no 64-bit address per op */
+        const uintptr_t dst = reinterpret_cast<uintptr_t>(F.ops_mirror + (cg_off >> 1)) - (uintptr_t)(pl0 - 2u);
+        typedef __attribute__((address_space(1))) uint8_t *GlobalBytes;
+        typedef __attribute__((address_space(1))) uint16_t *GlobalWord;
         for (uint32_t p = p0; p < p1; p++, tile++) {
             const uint32_t t0 = tile << FLAT_TILE_SHIFT, g = t0 + lane * 16u;
             uint4 v = make_uint4(0, 0, 0, 0);
@@ -172,56 +189,83 @@ __global__ __launch_bounds__(64 * FLAT_PARSE_WAVES) void k_flat_parse(FlatParams
             /* a cigar that ends in digits: the reference's switch sees the NUL (impl/paf.c:96-103) */
             uint32_t bad = (hi_b > lo_b && g + hi_b == cg_end && !((ndm >> (hi_b - 1u)) & 1u)) ? 1u : 0u;
             const uint32_t cnt = (uint32_t)__popc(opmask), inc = wave_incl_scan_u32(cnt), total = wave_last_u32(inc);
-            uint32_t rank = inc - cnt;
-            while (opmask) {
-                const uint32_t j = (uint32_t)__ffs((int)opmask) - 1u;
-                opmask &= opmask - 1u;
-                if (rank < FLAT_P_CAP) Pl[rank] = (uint16_t)(lane * 16u + j);
-                rank++;
+            {
+                uint32_t w = pl0 + 2u * (inc - cnt);
+                const uint32_t e0 = ebase + lane * 16u;
+                for (; opmask; opmask &= opmask - 1u, w += 2u) *reinterpret_cast<uint16_t *>(L + w) = (uint16_t)(e0 + (uint32_t)__builtin_ctz(opmask));
+                /* the letter in front of the tile; one further away than 17 bytes fails the same test as one 17 bytes away, and
+                   the byte behind it stays inside the wave's LDS */
+                if (lane == 0) *reinterpret_cast<int16_t *>(L + pl0 - 2u) = (int16_t)((int32_t)ebase + (prev < -17 ? -17 : prev));
             }
             if (total > FLAT_P_CAP) bad = 1u; /* op letters side by side: lengths without digits */
             __builtin_amdgcn_wave_barrier();
             const uint32_t top = total < FLAT_P_CAP ? total : FLAT_P_CAP;
-            /* per lane at most eight ops of at most 8 191 bases: two 16-bit sums per register */
-            uint32_t acc_mx = 0, acc_id = 0, acc_re = 0, nonplain = 0;
-            uint32_t before_first = (uint32_t)prev; /* the letter in front of the iteration's first op (lane 0 takes it) */
-            for (uint32_t i = lane; i < top; i += 64u) {
-                const uint32_t pos = Pl[i];
-                /* the letter in front: the lane below's (active whenever this one is) */
-                const uint32_t before = (uint32_t)__builtin_amdgcn_update_dpp((int)before_first, (int)pos, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-                before_first = lane_val(pos, 63);
-                const uint32_t k = pos - before - 1u; /* digits in front of the letter */
-                /* the four bytes in front of the letter and the letter itself: two aligned words of the staged text */
-                const uint32_t a = 12u + pos, sh = a & 3u;
-                const uint32_t *wp = reinterpret_cast<const uint32_t *>(T + (a - sh));
-                const uint32_t d0 = wp[0], d1 = wp[1];
-                const uint32_t hi = __builtin_amdgcn_alignbyte(d1, d0, sh);
-                const uint32_t ch = (d1 >> (8u * sh)) & 0xffu;
-                const uint32_t kk = k < 4u ? k : 4u;
-                const uint32_t x = kk ? ((hi ^ 0x30303030u) & (0xffffffffu << (32u - 8u * kk))) : 0u;
-                const uint32_t pr = ((x << 3) + (x << 1) + (x >> 8)) & 0x00ff00ffu; /* swar4 without the 32-bit multiply: two 2-digit numbers */
-                const uint32_t len = __umul24(pr & 0xffu, 100u) + (pr >> 16);
-                /* letter -> code (impl/paf.c:96-103): '=' 0x3d, 'D' 0x44, 'I' 0x49, 'M' 0x4d, 'X' 0x58 lie 0, 7, 12, 16, 27 above '=' */
-                const uint32_t dl = ch - 0x3du;
-                const bool known = dl < 28u && ((0x08011081u >> dl) & 1u);
-                const uint32_t code = (0x04001023u >> (dl & 0x1cu)) & 7u;
-                const bool lead0 = kk >= 2u && ((hi >> (8u * (4u - kk))) & 0xffu) == (uint32_t)'0';
-                /* what the flat pass keeps: one to four digits without a leading zero, 1 <= length < 8192, a letter of MID=X */
-                bad |= ((k - 1u > 3u) | (len - 1u >= 8191u) | lead0 | !known) ? 1u : 0u;
-                dst[n + i] = (uint16_t)((len << 3) | code);
-                const uint32_t l16 = len & 0xffffu;
-                acc_mx += l16 << (((0x16u >> code) & 1u) << 4);                                     /* M = | X I D */
-                acc_id += (code == (uint32_t)OP_I ? l16 : 0u) + (code == (uint32_t)OP_D ? l16 << 16 : 0u); /* I | D */
-                if (MODE == 2u) acc_re += (code == (uint32_t)OP_M ? 1u : 0u) + (code == (uint32_t)OP_I ? 1u << 16 : 0u); /* rows | I ops */
-                else acc_re += code == (uint32_t)OP_M ? 1u + ((MODE == 1u ? (len + 15u) >> 4 : kk - 1u) << 16) : 0u; /* rows | digits beyond the first (or 16-column chunks) */
-                nonplain |= code > (uint32_t)OP_D ? 1u : 0u;
+            /* What the flat pass keeps is one to four digits without a leading zero, 1 <= length < 8192 and a letter of MID=X. The tests
+               are gathered by OR over a lane's ops and looked at once per tile; where one fails, the piece is FLAT_F_IRREG and neither
+               its mirror words nor its sums are read by anyone, so lengths and sums are only right for ops that pass.
+                 v_len  the lengths, and (first digit - '1'): 8192 or more if a length is, or if a number starts with '0' (which
+                        includes a length of zero)
+                 v_dig  8 * digits - 1, the shift that makes the digit mask: above 31 for no digit or more than four
+                 v_let  letter of the code ^ the byte: byte 0 is not zero for a byte outside MID=X
+               Per lane at most eight ops of at most 8 191 bases: a 16-bit field holds a lane's sum. */
+            uint32_t v_len = 0, v_dig = 0, v_let = 0;
+            uint32_t acc_m = 0;  /* bases of M | MODE 0: digits beyond the first of M, 1: 16-column chunks of M */
+            uint32_t acc_id = 0; /* bases of I | of D */
+            uint32_t acc_r = 0;  /* M ops | MODE 2: I ops */
+            uint32_t acc_eq = 0, acc_xx = 0; /* bases of = and of X: summed only in trips that meet one */
+            uint32_t eqx = 0;    /* the lane was in such a trip */
+            const uint32_t a_end = pl0 - 2u + 2u * top;
+            const GlobalBytes tile_dst = (GlobalBytes)(dst + 2u * (uintptr_t)n);
+            for (uint32_t a = pl0 - 2u + 2u * lane; a < a_end; a += 128u) {
+                const uint32_t before = (uint32_t)(int32_t)*reinterpret_cast<const int16_t *>(L + a); /* entry of the letter in front */
+                const uint32_t pos = *reinterpret_cast<const uint16_t *>(L + a + 2u);
+                const uint32_t first = L[before + 5u], ch = L[pos + 4u];
+                const uint32_t km1 = pos - before - 2u; /* digits in front of the letter, less one */
+                const uint32_t dig = (km1 << 3) + 7u;
+                /* the four bytes in front of the letter: two aligned words of the staged text */
+                const uint32_t *wp = reinterpret_cast<const uint32_t *>(L + (pos & ~3u));
+                const uint32_t hi = __builtin_amdgcn_alignbyte(wp[1], wp[0], pos & 3u);
+                /* its digits, units in byte 3: xor, not minus (a byte below '0' in front of the digits would borrow from them) */
+                const uint32_t x = (hi ^ 0x30303030u) & (uint32_t)((int32_t)0x80000000 >> (dig & 31u));
+                const uint32_t len = udot4(x, 0x010a0000u, __umul24(udot4(x, 0x0000010au, 0u), 100u));
+                const uint32_t sel = ch & 0x1cu; /* four times bits 2..4 of the letter */
+                const uint32_t code = (FLAT_CODE_TAB >> sel) & 7u;
+                v_let |= __builtin_amdgcn_perm(FLAT_CODE_LETTERS_HI, FLAT_CODE_LETTERS_LO, code) ^ ch;
+                v_len |= len | (first - 0x31u);
+                v_dig |= dig;
+                *(GlobalWord)(tile_dst + a) = (uint16_t)((len << 3) | code);
+                const bool is_m = sel == 0x0cu;
+                acc_m += is_m ? len + ((MODE == 0u ? km1 : MODE == 1u ? (len + 15u) >> 4 : 0u) << 16) : 0u;
+                acc_r += (is_m ? 1u : 0u) + (MODE == 2u ? ((0x100u >> sel) & 1u) << 16 : 0u);
+                acc_id += __umul24(len, (0x00100100u >> sel) & 0x10001u); /* 'I': 1, 'D': 1 << 16 */
+                if (__any(sel >= 0x18u)) { /* rare, and the whole wave's branch: the empty asm keeps it from becoming selects in every trip */
+                    asm volatile("");
+                    acc_eq += sel == 0x1cu ? len : 0u;
+                    acc_xx += sel == 0x18u ? len : 0u;
+                    eqx = 1u;
+                }
             }
-            uint32_t sums6[6] = {acc_mx & 0xffffu, acc_mx >> 16, acc_id & 0xffffu, acc_id >> 16, acc_re & 0xffffu, acc_re >> 16};
-            wave_sum6_u32(sums6);
-            const uint32_t s_m = sums6[0], s_x = sums6[1], s_i = sums6[2], s_d = sums6[3], s_r = sums6[4], s_e = sums6[5];
-            const uint32_t flags = (__any(bad != 0) ? FLAT_F_IRREG : 0u) | (__any(nonplain != 0) ? FLAT_F_NONPLAIN : 0u);
+            const bool nonplain = __any(eqx != 0); /* the lanes that left the loop before that trip have to hear of it */
+            bad |= (v_len >= 8192u || v_dig > 31u || (v_let & 0xffu)) ? 1u : 0u;
+            uint32_t s_m, s_x, s_i, s_d, s_r, s_e;
+            if (MODE == 1u) { /* a lane's chunks can pass 16 bits in the wave's sum: a sum of their own */
+                uint32_t s[5] = {acc_m & 0xffffu, acc_m >> 16, acc_id & 0xffffu, acc_id >> 16, acc_r};
+                wave_sums_u32<5>(s);
+                s_m = s[0]; s_e = s[1]; s_i = s[2]; s_d = s[3]; s_r = s[4];
+            } else { /* at most 512 M ops and 1 536 digits: one sum for both */
+                uint32_t s[4] = {acc_m & 0xffffu, acc_id & 0xffffu, acc_id >> 16, MODE == 2u ? acc_r : (acc_m & 0xffff0000u) | acc_r};
+                wave_sums_u32<4>(s);
+                s_m = s[0]; s_i = s[1]; s_d = s[2]; s_r = s[3] & 0xffffu; s_e = s[3] >> 16;
+            }
+            s_x = s_i + s_d;
+            if (nonplain) {
+                uint32_t s[2] = {acc_eq, acc_xx};
+                wave_sums_u32<2>(s);
+                s_m += s[0]; s_x += s[1];
+            }
+            const uint32_t flags = (__any(bad != 0) ? FLAT_F_IRREG : 0u) | (nonplain ? FLAT_F_NONPLAIN : 0u);
             if (total) {
-                const int32_t last = (int32_t)Pl[top - 1u];
+                const int32_t last = (int32_t)uni(*reinterpret_cast<const uint16_t *>(L + pl0 + 2u * (top - 1u))) - (int32_t)ebase;
                 text_end = t0 + (uint32_t)last + 1u - cg_off;
                 prev = last - (int32_t)FLAT_TILE;
             } else {
