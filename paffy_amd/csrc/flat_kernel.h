@@ -619,7 +619,8 @@ __device__ __forceinline__ void flat_trim_prefix(const FlatRec &R, FlatState &s,
  * block is there; for the records of the wave kernel (one in eight on cfg3) it builds the pieces itself as before (row_pieces_lanes).
  */
 #define FLAT_F_ROW_PIECES 0x200000u
-#define FLAT_F_COPY 0x400000u       /* RecPlan flag bit 22: the line's cigar is a stretch of the input text, written by k_emit_copy (wq[0] = first byte from cg_off, wt[0] = bytes) */
+#define FLAT_F_ROWS_SHORT 0x800000u /* RecPlan flag bit 23: piece A is shorter than 16 bytes, the rows are written by k_emit_rows_short (in place of bit 6) */
+#define FLAT_F_COPY 0x400000u      /* RecPlan flag bit 22: the line's cigar is a stretch of the input text, written by k_emit_copy (wq[0] = first byte from cg_off, wt[0] = bytes) */
 #define FLAT_COPY_MAX (1u << 18)    /* bytes of cigar text one wave copies; longer lines take the writers that split a record */
 #define FLAT_ROW_PIECES_BYTES 144u
 struct LanePieceSink {
@@ -643,7 +644,7 @@ struct LanePieceSink {
         return n + 6;
     }
 };
-__device__ __forceinline__ void lane_row_pieces(uint32_t (*S)[256], uint32_t tid, uint8_t *dst, const RecState &s, const uint8_t *in) { /* lenA, lenB, lenC <= 48 */
+__device__ __forceinline__ void lane_row_pieces(uint32_t (*S)[256], uint32_t tid, uint8_t *dst, const RecState &s, const uint8_t *in) { /* lenA, lenB, lenC <= 48; zero filled, so a piece A below 16 bytes is its own rest chunk */
     u32x4 qn[3], tn[3];
 #pragma unroll
     for (uint32_t j = 0; j < 3; j++) { /* at most 15 bytes beyond a name: the line's later columns */
@@ -1053,17 +1054,22 @@ __global__ __launch_bounds__(256) void k_flat_lane(FlatSizeParams F) {
         if (rewritten && rs.type == 0 && rs.tile_level != -1) rs.type = rs.tile_level > 1 ? 'S' : 'P';
         const FlatPre win = flat_sub(v.whi, v.wlo);
         int64_t bytes, rows;
-        bool rows_kernel = false, line_kernel = false, copy = false;
+        bool rows_kernel = false, rows_short = false, line_kernel = false, copy = false;
         if (shatter) {
             ShatterConst k;
             shatter_consts(rs, k);
             const uint32_t dq0 = (uint32_t)dec_len(rs.qs), dt0 = (uint32_t)dec_len(rs.ts);
-            if (!shatter_fits(k) || !shatter_fast_ok(rs, k) || k.lenA > 48 || k.lenB > 48 || k.lenC > 48 || dq0 != (uint32_t)dec_len(rs.qe) ||
+            const bool short_a = shatter_short_a(k); /* k_emit_rows_short writes the rows */
+            if (!shatter_fits(k) || !shatter_fast_ok(rs, k) || (short_a && !shatter_short_ok(k)) || k.lenA > 48 || k.lenB > 48 || k.lenC > 48 || dq0 != (uint32_t)dec_len(rs.qe) ||
                 dt0 != (uint32_t)dec_len(rs.te) || rs.qe - rs.qs >= 0x7fffffffll || rs.te - rs.ts >= 0x7fffffffll || v.n > PAFFY_ROWS_MAX_OPS)
                 break;
             rows = win.rows;
             bytes = (int64_t)win.rows * (int64_t)(k.row_const + 2u * dq0 + 2u * dt0 + 3u) + 3ll * (int64_t)win.extra;
             rows_kernel = true;
+            if (short_a) {
+                rows_short = true;
+                atomicAdd(&P.info->s_count, 1u);
+            }
         } else {
             const uint32_t lenH = header_len(rs, false);
             if (lenH + 8 > PAFFY_TMPL_MAX) break;
@@ -1086,7 +1092,8 @@ __global__ __launch_bounds__(256) void k_flat_lane(FlatSizeParams F) {
         plan->lo = v.lo; plan->n = v.n;
         const bool pieces = rows_kernel && P.row_pieces != nullptr;
         plan->flags = (v.rev ? 1u : 0u) | (v.swp ? 2u : 0u) | (swapped ? 4u : 0u) | 8u | ((uint32_t)rs.type << 8) | (shatter ? 16u : 0u) |
-                      (rows_kernel ? 64u : 0u) | (line_kernel ? 0x10000u : 0u) | 0x40000u | (pieces ? FLAT_F_ROW_PIECES : 0u) | (copy ? FLAT_F_COPY : 0u);
+                      (rows_kernel ? (rows_short ? FLAT_F_ROWS_SHORT : 64u) : 0u) | (line_kernel ? 0x10000u : 0u) | 0x40000u | (pieces ? FLAT_F_ROW_PIECES : 0u) |
+                      (copy ? FLAT_F_COPY : 0u);
         plan->chunk = ((v.n + 63u) / 64u) | 1u;
         for (int w = 0; w < 4; w++) plan->wq[w] = plan->wt[w] = plan->wo[w] = 0;
         if (copy) { /* the stretch of text: from this byte of the cigar, this many */
@@ -1475,7 +1482,7 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
     }
     RecPlan *plan = static_cast<RecPlan *>(P.rec_plan) + rec;
     int64_t bytes, rows;
-    bool rows_kernel = false, line_kernel = false, copy = false;
+    bool rows_kernel = false, rows_short = false, line_kernel = false, copy = false;
     uint32_t row_bytes1 = 0; /* shatter: bytes of a row whose length has one digit */
     const FlatPre win = flat_sub(v.whi, v.wlo);
     if (shatter && !checked && flat_check(s, v)) return flat_leave(F, rec, FLAT_WHY_CHECK); /* every row of a record that passes paf_check passes its own (impl/paf.c:624) */
@@ -1490,7 +1497,10 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
         ShatterConst k;
         shatter_consts(rs, k);
         const uint32_t dq0 = (uint32_t)dec_len(rs.qs), dt0 = (uint32_t)dec_len(rs.ts);
+        rows_short = shatter_short_a(k);
         if (!shatter_fits(k) || !shatter_fast_ok(rs, k) || k.lenA > 48 || k.lenB > 48 || k.lenC > 48) return flat_leave(F, rec, FLAT_WHY_ROW_SHAPE);
+        /* a piece A below 16 bytes: k_emit_rows_short writes the whole record; segments (EmitItem) stay with k_emit_rows and its longer A */
+        if (rows_short && (!shatter_short_ok(k) || v.n > PAFFY_ROWS_MAX_OPS)) return flat_leave(F, rec, FLAT_WHY_ROW_SHAPE);
         if (rs.qe - rs.qs >= 0x7fffffffll || rs.te - rs.ts >= 0x7fffffffll) return flat_leave(F, rec, FLAT_WHY_DIGITS);
         /* a row whose coordinates have the digits of the record's start coordinates and whose length has one */
         row_bytes1 = k.row_const + 2u * dq0 + 2u * dt0 + 3u;
@@ -1547,6 +1557,7 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
     const bool four_waves = !shatter && !line_kernel && !copy;
     if (lane == 0) {
         if (four_waves) atomicAdd(&P.info->g_count, 1u);
+        if (rows_kernel && rows_short) atomicAdd(&P.info->s_count, 1u);
         F.flat_done[rec] = 1;
         P.status[rec] = (uint32_t)KLASS_LDS << 16;
         P.err_aux[rec] = 0;
@@ -1556,7 +1567,8 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
         plan->qs = s.qs; plan->qe = s.qe; plan->ts = s.ts; plan->te = s.te; plan->sub_lo = (int64_t)sub_lo; plan->sub_hi = (int64_t)sub_hi;
         plan->lo = v.lo; plan->n = v.n;
         plan->flags = (v.rev ? 1u : 0u) | (v.swp ? 2u : 0u) | (swapped ? 4u : 0u) | 8u | ((uint32_t)rs.type << 8) | (shatter ? 16u : 0u) |
-                      (rows_kernel ? 64u : 0u) | (line_kernel ? 0x10000u : 0u) | 0x40000u | (itemised ? 0x80000u : 0u) | (copy ? FLAT_F_COPY : 0u);
+                      (rows_kernel ? (rows_short ? FLAT_F_ROWS_SHORT : 64u) : 0u) | (line_kernel ? 0x10000u : 0u) | 0x40000u | (itemised ? 0x80000u : 0u) |
+                      (copy ? FLAT_F_COPY : 0u);
         plan->chunk = four_waves ? (((v.n + 255u) / 256u) | 1u) : (((v.n + 63u) / 64u) | 1u);
         for (int w = 0; w < 4; w++) plan->wq[w] = plan->wt[w] = plan->wo[w] = 0;
         if (copy) {

@@ -3110,6 +3110,8 @@ int paffy_hip_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap) {
     const bool shatter = kp.n_stages > 0 && kp.stages[kp.n_stages - 1].kind == PAFFY_SHATTER;
     if (shatter) {
         LAUNCH(c, "k_emit_rows", k_emit_rows, dim3(kp.n_rec + kp.n_items), dim3(64), PAFFY_ROWS_LDS_BYTES, kp);
+        /* the records whose first row piece is shorter than 16 bytes (names like chr1): none in most batches */
+        if (c->h_info->s_count > 0) LAUNCH(c, "k_emit_rows_short", k_emit_rows_short, dim3(kp.n_rec), dim3(64), PAFFY_ROWS_LDS_BYTES, kp);
         if (c->h_info->g_count > 0) LAUNCH(c, "k_emit_lds", k_emit_lds<true>, dim3(kp.n_rec), dim3(PAFFY_NT), PAFFY_EMIT_LDS_BYTES, kp);
         if (c->h_info->w_count > 0) LAUNCH(c, "k_arena_emit", k_arena_emit<true>, dim3(2048), dim3(PAFFY_NT), PAFFY_EMIT_LDS_BYTES, kp);
     } else {

@@ -2047,8 +2047,10 @@ __device__ __forceinline__ void shatter_emit(const RecState &s, const View<OPS> 
  *
  * Stores are 16 bytes wide whatever the piece's length. The surplus lands on bytes that are written
  * later: the following pieces of the same row, or -- past the row's end -- the first bytes of the next
- * row's piece A, which is why the first 16 bytes of every A are written last, after all rows of the
- * window (lenA >= 16 is the condition for this path).
+ * row, which is why the first 16 bytes of every row are written last, after all rows of the window.
+ * With a piece A of 16 bytes or more these are the wave-uniform first chunk of A; with a shorter one
+ * (SHORT_A: `chr1\t248956422\t` has 15 bytes, `q\t9\t` four) they also hold per-row text and are
+ * composed row by row (RowHead).
  */
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 __attribute__((aligned(1))) u32x4_unaligned;
@@ -2301,8 +2303,9 @@ struct RowPre {
     u32x4 a_rest, b0, b_rest, c0, c1, c_rest; /* rest: the chunk holding a piece's last len % 16 bytes */
 };
 __device__ __forceinline__ bool row_pre_ok(const RowConst &c) { return c.lenA < 32 && c.lenB < 32 && c.lenC < 48; }
+template <bool SHORT_A>
 __device__ __forceinline__ void row_pre_load(const RowConst &c, RowPre &r) {
-    r.a_rest = c.A16[1];
+    r.a_rest = c.A16[SHORT_A ? 0 : 1];
     r.b0 = c.B16[0]; r.b_rest = c.B16[c.lenB >> 4];
     r.c0 = c.C16[0]; r.c1 = c.C16[1]; r.c_rest = c.C16[c.lenC >> 4];
 }
@@ -2314,15 +2317,45 @@ __device__ __forceinline__ void row_pre_load(const RowConst &c, RowPre &r) {
     }
 #define PIECE_REST_CHUNK(PTR, LEN) (c.PTR[(LEN) >> 4])
 
-template <bool NEAR, bool PRE>
-__device__ __forceinline__ void put_row_body(uint8_t *p, const RowConst &c, const DigitBase &bq, const DigitBase &bt, const RowNums &r, bool small) {
+/*
+ * The first 16 bytes of a row whose piece A is shorter than that (4..15 bytes): A, then as much of `q0 \t`, `q1`, B and `t0 \t` as it
+ * takes -- their shortest forms are 4 + 2 + 1 + 7 + 2 = 16 bytes, so the head never reaches beyond t0's tab. put_row_body appends each
+ * text as it formats it; once 16 bytes are in, an append only counts. The head is stored after the bodies of all rows of the window,
+ * 16 bytes that all belong to the row (a row has 34 at least).
+ */
+struct RowHead {
+    uint64_t lo, hi;
+    uint32_t n; /* bytes appended so far (may pass 16) */
+    __device__ __forceinline__ void add(uint64_t tlo, uint64_t thi, uint32_t tn) { /* tn bytes, zero above them */
+        if (n < 16u) {
+            const uint32_t sh = 8u * (n & 7u);
+            if (n < 8u) {
+                lo |= tlo << sh;
+                hi |= (thi << sh) | ((tlo >> 1) >> (63u - sh));
+            } else {
+                hi |= tlo << sh;
+            }
+        }
+        n += tn;
+    }
+};
+template <bool NEAR, bool PRE, bool SHORT_A = false>
+__device__ __forceinline__ void put_row_body(uint8_t *p, const RowConst &c, const DigitBase &bq, const DigitBase &bt, const RowNums &r, bool small,
+                                             RowHead *head = nullptr) {
     RowPre pre;
-    if (PRE) row_pre_load(c, pre); /* before the row's first byte-aligned store */
+    if (PRE) row_pre_load<SHORT_A>(c, pre); /* before the row's first byte-aligned store */
     Txt16 t;
     const uint32_t fullA = c.lenA >> 4, rA = c.lenA & 15u;
-    if (!PRE) PIECE_FULL_CHUNKS(p, A16, c.lenA, 1)
+    if (!PRE && !SHORT_A) PIECE_FULL_CHUNKS(p, A16, c.lenA, 1)
     coord_txt<NEAR>(bq, r.dq, '\t', 1, t);
-    if (c.fuseA) {
+    if (SHORT_A) { /* A is the head's business; `q0 \t` is stored here only where it can reach beyond the head */
+        const u32x4 a = PRE ? pre.a_rest : PIECE_REST_CHUNK(A16, c.lenA);
+        head->lo = a.x | ((uint64_t)a.y << 32);
+        head->hi = a.z | ((uint64_t)a.w << 32);
+        head->n = c.lenA;
+        head->add(t.lo, t.hi, t.n);
+        if (!c.fuseA) store16(p + c.lenA, t.lo, t.hi);
+    } else if (c.fuseA) {
         const u32x4 a = PRE ? pre.a_rest : PIECE_REST_CHUNK(A16, c.lenA);
         store_rest_then(p + 16 * fullA, a.x | ((uint64_t)a.y << 32), a.z | ((uint64_t)a.w << 32), rA, t);
     } else {
@@ -2334,12 +2367,20 @@ __device__ __forceinline__ void put_row_body(uint8_t *p, const RowConst &c, cons
     store16(p, t.lo, t.hi);
     p += t.n;
     const uint32_t fullB = c.lenB >> 4, rB = c.lenB & 15u;
+    if (SHORT_A) {
+        head->add(t.lo, t.hi, t.n);
+        if (head->n < 16u) { /* a very short name: the head takes the beginning of B */
+            const u32x4 b = PRE ? pre.b0 : c.B16[0];
+            head->add(b.x | ((uint64_t)b.y << 32), b.z | ((uint64_t)b.w << 32), fullB ? 16u : rB);
+        }
+    }
     if (PRE) {
         if (fullB) store16(p, pre.b0);
     } else {
         PIECE_FULL_CHUNKS(p, B16, c.lenB, 0)
     }
     coord_txt<NEAR>(bt, r.dt, '\t', 1, t);
+    if (SHORT_A) head->add(t.lo, t.hi, t.n);
     if (c.fuseB) {
         const u32x4 b = PRE ? pre.b_rest : PIECE_REST_CHUNK(B16, c.lenB);
         store_rest_then(p + 16 * fullB, b.x | ((uint64_t)b.y << 32), b.z | ((uint64_t)b.w << 32), rB, t);
@@ -2398,16 +2439,20 @@ __device__ __forceinline__ bool shatter_fast_ok(const RecState &s, const Shatter
        and the cigar's sums equal the spans, so window sums fit 32 bits when the spans do */
     /* the bases of the digit arithmetic are the record's own coordinates: they must be sane themselves (shatter does not
        check its parent: a record with target_start -1 whose first op is a deletion still has valid rows) */
-    return k.lenA >= 16 && k.row_max <= PAFFY_WAVE_RING - 48u - PAFFY_FLUSH_GRAN && s.qlen < 100000000000ll && s.tlen < 100000000000ll && s.qs >= 0 && s.qs <= s.qe && s.qe <= s.qlen && s.ts >= 0 &&
+    return k.row_max <= PAFFY_WAVE_RING - 48u - PAFFY_FLUSH_GRAN && s.qlen < 100000000000ll && s.tlen < 100000000000ll && s.qs >= 0 && s.qs <= s.qe && s.qe <= s.qlen && s.ts >= 0 &&
            s.ts <= s.te && s.te <= s.tlen && s.qe - s.qs < 0x7f000000ll && s.te - s.ts < 0x7f000000ll;
 }
+/* A piece A shorter than 16 bytes is written by the SHORT_A form of the row writer (k_emit_rows_short), whose head needs A, `q0 \t`, `q1`, B
+   and `t0 \t` to make up 16 bytes: true of every record with a name on both sides (A >= 4, B >= 7). */
+__device__ __forceinline__ bool shatter_short_a(const ShatterConst &k) { return k.lenA < 16u; }
+__device__ __forceinline__ bool shatter_short_ok(const ShatterConst &k) { return k.lenA + k.lenB >= 11u; }
 
 /*
  * Same work split as shatter_emit (every wave owns a contiguous share of the ops, its start taken from
  * the sizing pass; windows of up to 128 ops, two per lane; no workgroup barrier), rows written with
  * byte-aligned 16-byte LDS stores, coordinates as 32-bit offsets from a wave-uniform base.
  */
-template <class OPS>
+template <class OPS, bool SHORT_A = false>
 __device__ __forceinline__ void shatter_emit_fast(const RecState &s, const View<OPS> &v, const ShatterConst &k, const u32x4 *A16, const u32x4 *B16,
                                                   const u32x4 *C16, uint32_t wb, uint32_t we, int64_t cq0, int64_t ct0, uint8_t *buf, uint8_t *out,
                                                   uint64_t out_start) {
@@ -2583,6 +2628,7 @@ __device__ __forceinline__ void shatter_emit_fast(const RecState &s, const View<
         em.flush();
         PT_MARK(2)
  /* the previous window: its stores were issued before this window's arithmetic */
+        uint64_t h0lo = 0, h0hi = 0, h1lo = 0, h1hi = 0; /* SHORT_A: the heads of the lane's rows */
 #pragma unroll 1
         for (int r = 0; r < 2; r++) {
             if (r && !any_sec) break;
@@ -2593,7 +2639,18 @@ __device__ __forceinline__ void shatter_emit_fast(const RecState &s, const View<
                 x.len = r ? rn1.len : rn0.len;
                 x.dq = r ? rn1.dq : rn0.dq;
                 x.dt = r ? rn1.dt : rn0.dt;
-                if (pre_ok) {
+                if constexpr (SHORT_A) {
+                    RowHead h;
+                    if (pre_ok) {
+                        if (near) put_row_body<true, true, true>(p, rc, bq, bt, x, small, &h);
+                        else put_row_body<false, true, true>(p, rc, bq, bt, x, small, &h);
+                    } else {
+                        if (near) put_row_body<true, false, true>(p, rc, bq, bt, x, small, &h);
+                        else put_row_body<false, false, true>(p, rc, bq, bt, x, small, &h);
+                    }
+                    if (r) { h1lo = h.lo; h1hi = h.hi; }
+                    else { h0lo = h.lo; h0hi = h.hi; }
+                } else if (pre_ok) {
                     if (near) put_row_body<true, true>(p, rc, bq, bt, x, small);
                     else put_row_body<false, true>(p, rc, bq, bt, x, small);
                 } else {
@@ -2602,8 +2659,13 @@ __device__ __forceinline__ void shatter_emit_fast(const RecState &s, const View<
                 }
             }
         }
-        /* the head of piece A of every row, last: it repairs what the previous row's wide stores spilled */
-        if (prim) {
+        /* the head of every row, last: it repairs what the previous row's wide stores spilled */
+        if constexpr (SHORT_A) { /* each row's own first 16 bytes */
+            if (prim) {
+                store16(em.buf + o, h0lo, h0hi);
+                if (sec) store16(em.buf + o + bytes0, h1lo, h1hi);
+            }
+        } else if (prim) {
             const u32x4 a_head = A16[0];
             store16(em.buf + o, a_head);
             if (sec) store16(em.buf + o + bytes0, a_head);
@@ -3314,12 +3376,13 @@ __device__ __forceinline__ bool size_record(const KParams &P, uint32_t rec, OPS 
     }
     RecPlan *plan = static_cast<RecPlan *>(P.rec_plan) + rec;
     int64_t bytes, rows;
-    bool direct = false, rows_kernel = false, line_kernel = false;
+    bool direct = false, rows_kernel = false, rows_short = false, line_kernel = false;
     if (shatter) {
         ShatterConst k;
         shatter_consts(s, k);
         direct = !shatter_fits(k);
-        rows_kernel = OPS::kNarrow && !direct && shatter_fast_ok(s, k) && k.lenA <= 48 && k.lenB <= 48 && k.lenC <= 48 &&
+        rows_short = shatter_short_a(k); /* a piece A below 16 bytes: k_emit_rows_short in place of k_emit_rows */
+        rows_kernel = OPS::kNarrow && !direct && shatter_fast_ok(s, k) && (!rows_short || shatter_short_ok(k)) && k.lenA <= 48 && k.lenB <= 48 && k.lenC <= 48 &&
                       v.n <= PAFFY_ROWS_MAX_OPS; /* emitted by k_emit_rows; longer records are split over the four waves of k_emit_lds */ /* pieces too long for the LDS staging: the emit pass writes this record's rows straight to HBM */
         int rc = 0;
         bool sized = false;
@@ -3375,13 +3438,14 @@ __device__ __forceinline__ bool size_record(const KParams &P, uint32_t rec, OPS 
     }
     if (threadIdx.x == 0) {
         if (klass == KLASS_LDS && (shatter ? !rows_kernel : !line_kernel)) atomicAdd(&P.info->g_count, 1u);
+        if (klass == KLASS_LDS && rows_kernel && rows_short) atomicAdd(&P.info->s_count, 1u);
         P.status[rec] = klass << 16;
         P.out_len[rec] = bytes;
         P.out_rows[rec] = rows;
         plan->qs = s.qs; plan->qe = s.qe; plan->ts = s.ts; plan->te = s.te; plan->sub_lo = v.sub_lo; plan->sub_hi = v.sub_hi;
         plan->lo = v.lo; plan->n = v.n;
         plan->flags = (v.rev ? 1u : 0u) | (v.swp ? 2u : 0u) | (swapped ? 4u : 0u) | (s.has_cigar ? 8u : 0u) | ((uint32_t)s.type << 8) |
-                      (shatter ? 16u : 0u) | (direct ? 32u : 0u) | (rows_kernel ? 64u : 0u) | (line_kernel ? 0x10000u : 0u) |
+                      (shatter ? 16u : 0u) | (direct ? 32u : 0u) | (rows_kernel ? (rows_short ? 0x800000u : 64u) : 0u) | (line_kernel ? 0x10000u : 0u) |
                       (ops_in_arena ? 0x20000u : 0u) | (mirror16 && !ops_in_arena ? 0x40000u : 0u);
         if (ops_in_arena) P.arena_off[rec] = arena_block;
         plan->chunk = ((v.n + PAFFY_NT - 1) / PAFFY_NT) | 1u; /* = sweep_bounds() */
@@ -3448,7 +3512,7 @@ __device__ __forceinline__ void emit_record(const KParams &P, uint32_t rec, cons
             w.pad_to(((w.n + 31u) & ~15u) < 48u ? 48u : ((w.n + 31u) & ~15u));
         }
         __syncthreads();
-        if (shatter_fast_ok(s, k)) {
+        if (k.lenA >= 16 && shatter_fast_ok(s, k)) { /* (the head of a shorter A: k_emit_rows_short only) */
             const uint64_t span = 64ull * pl.chunk;
             const uint32_t wb = span * wave < v.n ? (uint32_t)(span * wave) : v.n;
             const uint32_t we = span * (wave + 1) < v.n ? (uint32_t)(span * (wave + 1)) : v.n;
@@ -3595,7 +3659,7 @@ __global__ __launch_bounds__(PAFFY_NT, PAFFY_EMIT_OCC) void k_emit_lds(KParams P
     const uint32_t rec = blockIdx.x;
     if (rec >= (uint32_t)(P.info->first_err_key >> 16)) return; /* nothing at or after the first failure */
     if ((P.status[rec] >> 16) != KLASS_LDS) return;
-    if (static_cast<const RecPlan *>(P.rec_plan)[rec].flags & (SHATTER ? (64u | 0x80000u) : (0x10000u | 0x80000u | 0x400000u))) return; /* k_emit_rows / k_emit_line / k_emit_copy has it */
+    if (static_cast<const RecPlan *>(P.rec_plan)[rec].flags & (SHATTER ? (64u | 0x80000u | 0x800000u) : (0x10000u | 0x80000u | 0x400000u))) return; /* k_emit_rows(_short) / k_emit_line / k_emit_copy has it */
     OpsGlobal ops{emit_ops_of(P, rec, P.meta[rec], static_cast<const RecPlan *>(P.rec_plan)[rec]), emit_ops_half(static_cast<const RecPlan *>(P.rec_plan)[rec])};
 #if defined(PAFFY_ABL) && PAFFY_ABL == 22
     const unsigned long long c0 = clock64(), w0 = wall_clock64();
@@ -3727,6 +3791,47 @@ __global__ __launch_bounds__(64, PAFFY_ROWS_OCC) void k_emit_rows(KParams P) {
     if ((blockIdx.x & 16383u) == 99u && threadIdx.x == 0)
         printf("block %u (%u ops): %llu core cycles, %llu wall ticks (100 MHz) -> %.0f MHz\n", blockIdx.x, v.n, c1 - c0, w1 - w0, (double)(c1 - c0) / (double)(w1 - w0) * 100.0);
 #endif
+}
+
+/*
+ * The same kernel for the records whose piece A is shorter than 16 bytes (RecPlan flag bit 23 in place of bit 6: chr1, 2L, q): the same
+ * prologue, pieces and LDS layout, the SHORT_A form of the row writer, which composes every row's first 16 bytes (RowHead). A kernel of
+ * its own so that k_emit_rows stays the code it was; never segments (a long record with such a name leaves the flat pass); launched only
+ * when a sizing kernel counted such a record (DevInfo::s_count).
+ */
+__global__ __launch_bounds__(64, PAFFY_ROWS_OCC) void k_emit_rows_short(KParams P) {
+    extern __shared__ uint4 smem4[];
+    uint8_t *smem = reinterpret_cast<uint8_t *>(smem4);
+    const uint32_t rec = P.emit_order ? P.emit_order[blockIdx.x] : blockIdx.x; /* long records first */
+    if (rec >= (uint32_t)(P.info->first_err_key >> 16)) return; /* nothing at or after the first failure */
+    if ((P.status[rec] >> 16) != KLASS_LDS) return;
+    const RecPlan &pl = static_cast<const RecPlan *>(P.rec_plan)[rec];
+    if (!(pl.flags & 0x800000u)) return;
+    const RecMeta &m = P.meta[rec];
+    RecState s;
+    load_state(m, s);
+    if (pl.flags & 4u) invert_state(s);
+    s.qs = pl.qs; s.qe = pl.qe; s.ts = pl.ts; s.te = pl.te;
+    s.has_cigar = (pl.flags & 8u) != 0;
+    s.type = (uint8_t)(pl.flags >> 8);
+    OpsGlobal ops{emit_ops_of(P, rec, m, pl), emit_ops_half(pl)};
+    View<OpsGlobal> v;
+    v.reset(ops, pl.n);
+    v.lo = pl.lo; v.rev = pl.flags & 1u; v.swp = (pl.flags & 2u) != 0;
+    v.sub_lo = pl.sub_lo; v.sub_hi = pl.sub_hi;
+    ShatterConst k;
+    shatter_consts(s, k);
+    uint8_t *A = smem + PAFFY_WAVE_RING, *B = A + 64, *C = B + 64;
+    if (pl.flags & 0x200000u) { /* the flat sizing pass left the pieces in HBM: 3 x 48 bytes there, 3 x 64 zero filled bytes here */
+        if (threadIdx.x < 48)
+            reinterpret_cast<uint32_t *>(A)[threadIdx.x] =
+                (threadIdx.x & 15u) < 12u ? reinterpret_cast<const uint32_t *>(P.row_pieces + 144ull * rec)[12u * (threadIdx.x >> 4) + (threadIdx.x & 15u)] : 0u;
+    } else {
+        row_pieces_lanes(A, s, P.in);
+    }
+    __builtin_amdgcn_wave_barrier();
+    shatter_emit_fast<OpsGlobal, true>(s, v, k, reinterpret_cast<const u32x4 *>(A), reinterpret_cast<const u32x4 *>(B), reinterpret_cast<const u32x4 *>(C), 0, v.n, 0, 0,
+                                       smem, P.out, (uint64_t)P.out_off[rec]);
 }
 
 /*

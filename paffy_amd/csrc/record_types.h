@@ -60,6 +60,9 @@ struct DevInfo {
     uint32_t n_items; /* EmitItem entries written (segments of the records too long for one wave of the row writer) */
     uint32_t flat_reason[16]; /* why: FLAT_WHY_* of flat_kernel.h (diagnostics, paffy_hip_flat_stats) */
     unsigned long long add_scr_total, add_new_total; /* flat_add_kernel.h: words of scratch / of new ops the batch needs */
+    uint32_t s_count; /* shatter records whose rows k_emit_rows_short writes (RecPlan flag bit 23), bumped by every sizing kernel; a sizing
+                         pass that runs again counts its records again: the host only asks whether it is zero */
+    uint32_t pad2;
 };
 
 /* What the stage list left of a record; written by the sizing pass, read by the emit pass. */
@@ -73,7 +76,9 @@ struct RecPlan {
                        bit19 a long shatter record written as EmitItem segments by k_emit_rows,
                        bit20 the 4-byte ops are words of new_ops[] (flat add_mismatches and flat add_mismatches -a: flat_add_kernel.h, flat_remove_kernel.h), bit21 the row pieces are in row_pieces[],
                        bit22 the line's cigar is a stretch of the input's text: k_emit_copy (wq[0] = first byte from cg_off, wt[0] = bytes;
-                       wq[1] / wt[1] = new length of a first / last op a fixed trim shortened, wq[2] / wt[2] = bytes of that op's text) */
+                       wq[1] / wt[1] = new length of a first / last op a fixed trim shortened, wq[2] / wt[2] = bytes of that op's text),
+                       bit23 rows written by k_emit_rows_short: a shatter record of the one-wave row writer whose first constant row piece
+                       (qname \t qlen \t) is shorter than 16 bytes -- in place of bit6, never both, and never with bit19 */
     uint32_t chunk; /* ops per lane in the sizing sweep: wave w owns view ops [64*w*chunk, 64*(w+1)*chunk) */
     /* shatter: query / target bases consumed and output bytes produced before each wave's range */
     int64_t wq[4], wt[4], wo[4]; /* four waves: the emit workgroups; a one-wave sizing workgroup fills entry 0 and zeroes the rest */

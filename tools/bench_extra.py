@@ -5,7 +5,9 @@ remove_eqx: `add_mismatches -a` on the cfg4 stream as `add_mismatches` wrote it 
 the plain M/I/D stream, where almost nothing merges). view / view_stats_only: what `paffy view` plans on the cfg4 stream -- [ADD_MISMATCHES,
 STATS] and its sums, nothing emitted -- by the default plan and under Engine.stats_only (plan-only rates, inputs resident in HBM).
 view_lines: the sums-only plan, then the per-record stats lines of `paffy view` written into device memory (paffy_hip_plan_view_sizes /
-_view_text, view_line_kernel.h): plan + sizes + text, everything resident."""
+_view_text, view_line_kernel.h): plan + sizes + text, everything resident. shatter / invert_trim_shatter --names short: the cfg3 stream
+with hs.chrN / pt.chrN renamed to chrN (first row pieces of 15 and 16 bytes, half and half): the share of such records, flat_stats and,
+for shatter, the rows each row writer wrote."""
 import argparse
 import json
 import os
@@ -36,7 +38,10 @@ def main():
     ap.add_argument("--mean-ops", type=int, default=2048)
     ap.add_argument("--contigs", type=int, default=24, help="contigs of the synthetic stream (chain: fewer contigs = larger groups)")
     ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "view", "view_stats_only", "view_lines", "dedupe", "bed", "stats", "chain",
-                                                    "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload"])
+                                                    "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload", "invert_trim_shatter"])
+    ap.add_argument("--names", default="std", choices=["std", "short"],
+                    help="shatter, invert_trim_shatter: `short` renames hs.chrN / pt.chrN to chrN on the host (outside the timed region): chr1-chr9 "
+                         "then have a first row piece of 15 bytes, chr10-chr24 one of 16 -- about half and half, like a human assembly")
     ap.add_argument("--genome-gb", type=float, default=3.1, help="faffy_*: bases of the synthetic genome (24 contigs)")
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
     ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome")
@@ -90,6 +95,24 @@ def main():
             buf = eng.to_device(text)
     else:
         buf, nbytes = eng.synth(0x5EED0005, a.mean_ops, 0, a.records, n_contigs=a.contigs)
+    rows_cmd = a.cmd in ("shatter", "invert_trim_shatter")
+    short_share = None
+    if rows_cmd:  # the share of records whose first row piece (name, tab, length, tab) is shorter than 16 bytes, as read and behind an invert
+        text = bytes(buf[:nbytes].cpu().numpy().tobytes())
+        if a.names == "short":
+            text = text.replace(b"hs.chr", b"chr").replace(b"pt.chr", b"chr")
+            nbytes = len(text)
+            buf = eng.to_device(text)
+        n_q = n_t = n = 0
+        m_ops = []  # M ops per record: the rows `shatter` alone writes for it
+        for line in text.split(b"\n")[:-1]:
+            f = line.split(b"\t", 7)
+            n += 1
+            n_q += len(f[0]) + len(f[1]) + 2 < 16
+            n_t += len(f[5]) + len(f[6]) + 2 < 16
+            m_ops.append(line.rsplit(b"cg:Z:", 1)[1].count(b"M"))
+        short_share = {"as_read": round(n_q / max(1, n), 4), "behind_an_invert": round(n_t / max(1, n), 4)}
+        del text
     torch.cuda.synchronize()
     kinds = {"invert": paffy_amd.INVERT, "trim": paffy_amd.TRIM_IDENTITY, "shatter": paffy_amd.SHATTER, "remove": paffy_amd.REMOVE_MISMATCHES, "filter": paffy_amd.FILTER}
     eng.set_filter(min_identity=0.9)
@@ -145,7 +168,10 @@ def main():
             info = eng.dedupe_plan(buf, nbytes, True)
         else:
             st = paffy_amd.stage(paffy_amd.TRIM_FIXED, 0.05, 0.1) if a.cmd == "trimf" else (paffy_amd.stage_dechunk() if a.cmd == "dechunk" else None)
-            info = eng.tile_plan(buf, nbytes) if a.cmd == "tile" else eng.plan([st or paffy_amd.stage(kinds[a.cmd])], buf, nbytes)
+            if a.cmd == "invert_trim_shatter":
+                info = eng.plan([paffy_amd.stage(paffy_amd.INVERT), paffy_amd.stage(paffy_amd.TRIM_IDENTITY), paffy_amd.stage(paffy_amd.SHATTER)], buf, nbytes)
+            else:
+                info = eng.tile_plan(buf, nbytes) if a.cmd == "tile" else eng.plan([st or paffy_amd.stage(kinds[a.cmd])], buf, nbytes)
         out = eng.alloc_out(info.out_bytes)
         eng.emit(out)
         eng.sync()
@@ -157,6 +183,15 @@ def main():
     extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx") or view else {}
     if view:
         extra["sums"] = list(sums)
+    if rows_cmd:
+        left, why = eng.flat_stats()
+        extra.update(names=a.names, piece_a_below_16=short_share, flat_left=left, flat_why=list(why), rows=int(info.n_rows))
+        if a.cmd == "shatter":  # rows per writer, from the records' RecPlan flags (bit 6 k_emit_rows, bit 19 its segments, bit 23 k_emit_rows_short)
+            flags, _ = eng.record_layout(0, len(m_ops))
+            by = {"k_emit_rows": 0, "k_emit_rows_short": 0, "other": 0}
+            for f, r in zip(flags, m_ops):
+                by["k_emit_rows_short" if f & 0x800000 else "k_emit_rows" if f & 0x80040 else "other"] += r
+            extra["rows_by_kernel"] = by
     if a.cmd == "view_lines":
         extra["text_bytes"] = text_bytes
     print(json.dumps({**extra, "cmd": a.cmd, "records": a.records, "mean_ops": a.mean_ops, "in_bytes": nbytes, "out_bytes": int(info.out_bytes),
