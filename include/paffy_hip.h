@@ -707,6 +707,8 @@ int paffy_hip_free(void *d_ptr);
 int paffy_hip_memcpy_h2d(void *d_dst, const void *h_src, int64_t bytes);
 int paffy_hip_memcpy_d2h(void *h_dst, const void *d_src, int64_t bytes);
 int paffy_hip_device_count(void);
+/* device buffers the library owns in this process right now (contexts, their command states, streams); not paffy_hip_malloc's */
+int paffy_hip_device_buffers(int64_t *buffers, int64_t *bytes);
 
 /*
  * Synthetic workload of SURVEY.md section 8d, generated on the device (same bytes as

@@ -41,19 +41,15 @@ struct CovState {
 
 static int ensure_keep(paffy_hip_ctx *c, DevBuf &b, size_t bytes, size_t used) {
     if (bytes <= b.cap) return 0;
-    void *p = nullptr;
-    size_t want = bytes + bytes / 2 + 4096;
-    if (hipMalloc(&p, want) != hipSuccess) { /* no room for the slack: the exact size must still work */
+    DevBuf grown;
+    if (grown.alloc(bytes + bytes / 2 + 4096) != hipSuccess) { /* no room for the slack: the exact size must still work */
         (void)hipGetLastError();
-        p = nullptr;
-        want = bytes;
-        HIPCHK(c, hipMalloc(&p, want));
+        HIPCHK(c, grown.alloc(bytes));
     }
-    if (b.p && used) HIPCHK(c, hipMemcpyAsync(p, b.p, used, hipMemcpyDeviceToDevice, c->stream));
+    if (b.p && used) HIPCHK(c, hipMemcpyAsync(grown.p, b.p, used, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = p;
-    b.cap = want;
+    HIPCHK(c, b.release()); /* the old buffer: a failing free is still reported */
+    b = std::move(grown);
     return 0;
 }
 

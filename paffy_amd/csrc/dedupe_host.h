@@ -24,16 +24,6 @@ struct DedupeState {
     DevBuf chi, clo, idx, idx2, k64, flags, keep, pos, first, tmp;
 };
 
-static void dedupe_free(paffy_hip_ctx *c) {
-    if (!c->dedupe) return;
-    DedupeState &D = *c->dedupe;
-    DevBuf *db[] = {&D.seen_hi, &D.seen_lo, &D.seen_hi2, &D.seen_lo2, &D.chi, &D.clo, &D.idx, &D.idx2, &D.k64, &D.flags, &D.keep, &D.pos, &D.first, &D.tmp};
-    for (DevBuf *b : db)
-        if (b->p) (void)hipFree(b->p);
-    delete c->dedupe;
-    c->dedupe = nullptr;
-}
-
 __device__ __forceinline__ bool dd_less(uint64_t ah, uint64_t al, uint64_t bh, uint64_t bl) { return ah < bh || (ah == bh && al < bl); }
 __device__ __forceinline__ bool dd_seen(const uint64_t *hi, const uint64_t *lo, uint32_t n, uint64_t kh, uint64_t kl) {
     uint32_t b = 0, e = n; /* first element not less than the key */

@@ -255,18 +255,8 @@ struct DedupeParts {
     DevBuf khi, klo, kg, k64a, k64b, idx, va, vb, head, head_of, wflag, wpos, tmp;
 };
 static DedupeParts &dedupe_parts(paffy_hip_ctx *c) {
-    if (!c->dd_parts) c->dd_parts = new DedupeParts();
+    if (!c->dd_parts) c->dd_parts.reset(new DedupeParts());
     return *c->dd_parts;
-}
-static void dedupe_parts_free(paffy_hip_ctx *c) {
-    if (!c->dd_parts) return;
-    DedupeParts &P = *c->dd_parts;
-    DevBuf *db[] = {&P.counts, &P.scanned, &P.starts, &P.first, &P.ent_rec, &P.vloc, &P.keep, &P.pos, &P.mem_hi, &P.mem_lo, &P.mem_or, &P.mem_hi2, &P.mem_lo2, &P.mem_or2,
-                    &P.khi, &P.klo, &P.kg, &P.k64a, &P.k64b, &P.idx, &P.va, &P.vb, &P.head, &P.head_of, &P.wflag, &P.wpos, &P.tmp};
-    for (DevBuf *b : db)
-        if (b->p) (void)hipFree(b->p);
-    delete c->dd_parts;
-    c->dd_parts = nullptr;
 }
 static void dedupe_parts_reset(paffy_hip_ctx *c) {
     c->dd_part_stage = 0;
@@ -497,7 +487,7 @@ int paffy_hip_dedupe_part_plan(paffy_hip_ctx *c, int64_t first_bad_global, paffy
             LAUNCH(c, "k_dedupe_collect", k_dedupe_collect, dim3(grid), dim3(PAFFY_NT), 0, static_cast<const DedupeKey *>(c->dedupe_keys.p), static_cast<const uint32_t *>(keep),
                    static_cast<const uint32_t *>(pos), n, n, 0, static_cast<uint32_t *>(c->tile_order.p), static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), 0u);
     }
-    if (!c->dedupe) c->dedupe = new DedupeState(); /* the scan scratch of the line tail */
+    if (!c->dedupe) c->dedupe.reset(new DedupeState()); /* the scan scratch of the line tail */
     return dedupe_plan_lines(c, P.in, nk, info);
 }
 

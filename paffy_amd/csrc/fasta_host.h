@@ -9,8 +9,10 @@
 #include <map>
 
 struct FastaState {
-    DevBuf starts, tiles, totals, recs, bases, hdr_off, hdr_blob, items, bad;
-    DevBuf seen_names, seen_off, seen; /* paffy_hip_fasta_seen (seqload_host.h): the distinct names and a flag per name */
+    struct Dev { /* all of the state's device memory: fasta_release lets it go while the state lives */
+        DevBuf starts, tiles, totals, recs, bases, hdr_off, hdr_blob, items, bad;
+        DevBuf seen_names, seen_off, seen; /* paffy_hip_fasta_seen (seqload_host.h): the distinct names and a flag per name */
+    } dev;
     const uint8_t *text = nullptr; /* the caller's text: emit reads the header names from it */
     int64_t text_len = 0, n_rec = 0, n_bases = 0;
     bool indexed = false, planned = false;
@@ -23,24 +25,10 @@ struct FastaState {
     int64_t out_bytes = 0;
 };
 
-static void fasta_release(FastaState &F) {
-    DevBuf *bufs[] = {&F.starts, &F.tiles, &F.totals, &F.recs, &F.bases, &F.hdr_off, &F.hdr_blob, &F.items, &F.bad, &F.seen_names, &F.seen_off, &F.seen};
-    for (DevBuf *b : bufs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-}
-
-static void fasta_free(paffy_hip_ctx *c) {
-    if (!c->fasta) return;
-    fasta_release(*c->fasta);
-    delete c->fasta;
-    c->fasta = nullptr;
-}
+static void fasta_release(FastaState &F) { F.dev = FastaState::Dev(); }
 
 static FastaState &fasta_state(paffy_hip_ctx *c) {
-    if (!c->fasta) c->fasta = new FastaState();
+    if (!c->fasta) c->fasta.reset(new FastaState());
     return *c->fasta;
 }
 
@@ -94,8 +82,8 @@ static int fa_plan_end(paffy_hip_ctx *c, paffy_plan_info *info) {
     info->n_rows = (int64_t)F.h_items.size();
     info->out_bytes = F.out_bytes;
     if (!F.h_items.empty()) {
-        if (ensure(c, F.items, sizeof(FaItem) * F.h_items.size())) return PAFFY_E_HIP;
-        HIPCHK(c, hipMemcpyAsync(F.items.p, F.h_items.data(), sizeof(FaItem) * F.h_items.size(), hipMemcpyHostToDevice, c->stream));
+        if (ensure(c, F.dev.items, sizeof(FaItem) * F.h_items.size())) return PAFFY_E_HIP;
+        HIPCHK(c, hipMemcpyAsync(F.dev.items.p, F.h_items.data(), sizeof(FaItem) * F.h_items.size(), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream)); /* h_items may change with the next plan */
     }
     F.planned = true;
@@ -123,40 +111,40 @@ static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t
     const int32_t nf = (int32_t)starts.size();
     const uint32_t n_tiles = (uint32_t)((text_len + FA_TILE - 1) / FA_TILE);
     if (n_tiles) {
-        if (ensure(c, F.starts, sizeof(int64_t) * starts.size())) return PAFFY_E_HIP;
-        if (ensure(c, F.tiles, sizeof(FaTile) * n_tiles)) return PAFFY_E_HIP;
-        if (ensure(c, F.totals, sizeof(int64_t) * 2)) return PAFFY_E_HIP;
-        HIPCHK(c, hipMemcpyAsync(F.starts.p, starts.data(), sizeof(int64_t) * starts.size(), hipMemcpyHostToDevice, c->stream));
-        const int64_t *d_starts = static_cast<const int64_t *>(F.starts.p);
-        FaTile *tiles = static_cast<FaTile *>(F.tiles.p);
+        if (ensure(c, F.dev.starts, sizeof(int64_t) * starts.size())) return PAFFY_E_HIP;
+        if (ensure(c, F.dev.tiles, sizeof(FaTile) * n_tiles)) return PAFFY_E_HIP;
+        if (ensure(c, F.dev.totals, sizeof(int64_t) * 2)) return PAFFY_E_HIP;
+        HIPCHK(c, hipMemcpyAsync(F.dev.starts.p, starts.data(), sizeof(int64_t) * starts.size(), hipMemcpyHostToDevice, c->stream));
+        const int64_t *d_starts = static_cast<const int64_t *>(F.dev.starts.p);
+        FaTile *tiles = static_cast<FaTile *>(F.dev.tiles.p);
         LAUNCH(c, "k_fa_count", k_fa_count, dim3(n_tiles), dim3(FA_NT), 0, F.text, text_len, d_starts, nf, tiles);
-        LAUNCH(c, "k_fa_scan", k_fa_scan, dim3(1), dim3(FA_NT), 0, tiles, n_tiles, static_cast<int64_t *>(F.totals.p));
+        LAUNCH(c, "k_fa_scan", k_fa_scan, dim3(1), dim3(FA_NT), 0, tiles, n_tiles, static_cast<int64_t *>(F.dev.totals.p));
         int64_t tot[2] = {0, 0};
-        HIPCHK(c, hipMemcpyAsync(tot, F.totals.p, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(tot, F.dev.totals.p, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         F.n_rec = tot[0];
         F.n_bases = tot[1];
-        if (ensure(c, F.recs, sizeof(FaRec) * (size_t)(F.n_rec + 1))) return PAFFY_E_HIP;
-        if (with_bases && ensure(c, F.bases, (size_t)F.n_bases + 64)) return PAFFY_E_HIP; /* k_fa_emit reads up to 32 bytes past the last base */
-        LAUNCH(c, "k_fa_write", k_fa_write, dim3(n_tiles), dim3(FA_NT), 0, F.text, text_len, d_starts, nf, static_cast<const FaTile *>(F.tiles.p),
-               with_bases ? static_cast<uint8_t *>(F.bases.p) : nullptr, static_cast<FaRec *>(F.recs.p));
+        if (ensure(c, F.dev.recs, sizeof(FaRec) * (size_t)(F.n_rec + 1))) return PAFFY_E_HIP;
+        if (with_bases && ensure(c, F.dev.bases, (size_t)F.n_bases + 64)) return PAFFY_E_HIP; /* k_fa_emit reads up to 32 bytes past the last base */
+        LAUNCH(c, "k_fa_write", k_fa_write, dim3(n_tiles), dim3(FA_NT), 0, F.text, text_len, d_starts, nf, static_cast<const FaTile *>(F.dev.tiles.p),
+               with_bases ? static_cast<uint8_t *>(F.dev.bases.p) : nullptr, static_cast<FaRec *>(F.dev.recs.p));
         if (F.n_rec) {
             LAUNCH(c, "k_fa_records", k_fa_records, dim3((unsigned)((F.n_rec + FA_NT - 1) / FA_NT)), dim3(FA_NT), 0, F.text, text_len, d_starts, nf,
-                   static_cast<FaRec *>(F.recs.p), F.n_rec, F.n_bases);
+                   static_cast<FaRec *>(F.dev.recs.p), F.n_rec, F.n_bases);
             F.h_recs.resize((size_t)F.n_rec);
-            HIPCHK(c, hipMemcpyAsync(F.h_recs.data(), F.recs.p, sizeof(FaRec) * (size_t)F.n_rec, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(F.h_recs.data(), F.dev.recs.p, sizeof(FaRec) * (size_t)F.n_rec, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             F.h_hdr_at.resize((size_t)F.n_rec + 1);
             for (int64_t r = 0; r < F.n_rec; r++) F.h_hdr_at[r + 1] = F.h_hdr_at[r] + F.h_recs[r].hdr_len;
             const int64_t blob = F.h_hdr_at[F.n_rec];
             F.h_hdr.resize((size_t)blob + 1);
             if (blob) {
-                if (ensure(c, F.hdr_off, sizeof(int64_t) * (size_t)F.n_rec)) return PAFFY_E_HIP;
-                if (ensure(c, F.hdr_blob, (size_t)blob)) return PAFFY_E_HIP;
-                HIPCHK(c, hipMemcpyAsync(F.hdr_off.p, F.h_hdr_at.data(), sizeof(int64_t) * (size_t)F.n_rec, hipMemcpyHostToDevice, c->stream));
+                if (ensure(c, F.dev.hdr_off, sizeof(int64_t) * (size_t)F.n_rec)) return PAFFY_E_HIP;
+                if (ensure(c, F.dev.hdr_blob, (size_t)blob)) return PAFFY_E_HIP;
+                HIPCHK(c, hipMemcpyAsync(F.dev.hdr_off.p, F.h_hdr_at.data(), sizeof(int64_t) * (size_t)F.n_rec, hipMemcpyHostToDevice, c->stream));
                 LAUNCH(c, "k_fa_headers", k_fa_headers, dim3((unsigned)((F.n_rec + FA_NT / 64 - 1) / (FA_NT / 64))), dim3(FA_NT), 0, F.text,
-                       static_cast<const FaRec *>(F.recs.p), F.n_rec, static_cast<const int64_t *>(F.hdr_off.p), static_cast<uint8_t *>(F.hdr_blob.p));
-                HIPCHK(c, hipMemcpyAsync(F.h_hdr.data(), F.hdr_blob.p, (size_t)blob, hipMemcpyDeviceToHost, c->stream));
+                       static_cast<const FaRec *>(F.dev.recs.p), F.n_rec, static_cast<const int64_t *>(F.dev.hdr_off.p), static_cast<uint8_t *>(F.dev.hdr_blob.p));
+                HIPCHK(c, hipMemcpyAsync(F.h_hdr.data(), F.dev.hdr_blob.p, (size_t)blob, hipMemcpyDeviceToHost, c->stream));
             }
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -195,7 +183,7 @@ int64_t paffy_hip_fasta_records(paffy_hip_ctx *c, int64_t first, int64_t cap, pa
 int paffy_hip_fasta_copy_bases(paffy_hip_ctx *c, int64_t first, int64_t n, void *d_dst) {
     if (!c || !c->fasta || !c->fasta->indexed || !c->fasta->with_bases || first < 0 || n < 0 || first + n > c->fasta->n_bases || (n > 0 && !d_dst))
         return PAFFY_E_ARG;
-    if (n) HIPCHK(c, hipMemcpyAsync(d_dst, static_cast<const uint8_t *>(c->fasta->bases.p) + first, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    if (n) HIPCHK(c, hipMemcpyAsync(d_dst, static_cast<const uint8_t *>(c->fasta->dev.bases.p) + first, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -374,14 +362,14 @@ int paffy_hip_faffy_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap, paffy_e
     if (!F.out_bytes) return 0;
     if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u)) return PAFFY_E_ARG;
     if (out_cap < ((F.out_bytes + 15) & ~(int64_t)15)) return PAFFY_E_CAPACITY;
-    if (ensure(c, F.bad, sizeof(unsigned long long))) return PAFFY_E_HIP;
-    HIPCHK(c, hipMemsetAsync(F.bad.p, 0xff, sizeof(unsigned long long), c->stream));
+    if (ensure(c, F.dev.bad, sizeof(unsigned long long))) return PAFFY_E_HIP;
+    HIPCHK(c, hipMemsetAsync(F.dev.bad.p, 0xff, sizeof(unsigned long long), c->stream));
     const int64_t n_win = (F.out_bytes + FA_WIN - 1) / FA_WIN;
     LAUNCH(c, "k_fa_emit", k_fa_emit, dim3((unsigned)((n_win + FA_EMIT_WAVES - 1) / FA_EMIT_WAVES)), dim3(64 * FA_EMIT_WAVES), 0,
-           static_cast<const FaItem *>(F.items.p), (int64_t)F.h_items.size(), F.text, static_cast<const uint8_t *>(F.bases.p),
-           static_cast<uint8_t *>(d_out), F.out_bytes, static_cast<unsigned long long *>(F.bad.p));
+           static_cast<const FaItem *>(F.dev.items.p), (int64_t)F.h_items.size(), F.text, static_cast<const uint8_t *>(F.dev.bases.p),
+           static_cast<uint8_t *>(d_out), F.out_bytes, static_cast<unsigned long long *>(F.dev.bad.p));
     unsigned long long bad = ~0ull;
-    HIPCHK(c, hipMemcpyAsync(&bad, F.bad.p, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&bad, F.dev.bad.p, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->profile) prof_collect(c);
     if (bad != ~0ull && err) {

@@ -19,12 +19,14 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
 #include "../../include/paffy_hip.h"
+#include "device_buffer.h"
 #include "paf_synth_core.h"
 #include "record_groups.h"
 #include "flat_kernel.h"
@@ -1042,11 +1044,6 @@ __global__ __launch_bounds__(PAFFY_NT) void k_synth4_fill(psynth4_cfg cfg, psynt
 /* host side                                                            */
 /* ------------------------------------------------------------------ */
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
 struct ProfEntry {
     std::string name;
     double ms = 0;
@@ -1061,7 +1058,17 @@ enum PlanKind {
     PLAN_BED      /* paffy to_bed: the run lines */
 };
 
+/* the command states the context owns: complete where the context's destructor is defined, at the end of this file */
+struct DedupeState;
+struct DedupeParts;
+struct SplitState;
+struct BedParams;
+struct ChainState;
+struct FastaState;
+struct CovState;
+
 struct paffy_hip_ctx {
+    ~paffy_hip_ctx(); /* teardown order: DESIGN "Who owns device memory" */
     hipStream_t stream = nullptr;
     hipStream_t side = nullptr; /* sizing launches of the long-cigar records run here, beside the main launch */
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -1073,14 +1080,14 @@ struct paffy_hip_ctx {
     psynth4_cfg synth4_cfg = {0, 0, 0, 0, 0};
     paffy_filter filter = {-1, -1, -1.0, -1.0, -1, 0};
     DevBuf dedupe_keys;
-    struct DedupeState *dedupe = nullptr; /* dedupe_host.h: keys of the records written so far (sorted, on the device) and scratch */
+    std::unique_ptr<DedupeState> dedupe; /* dedupe_host.h: keys of the records written so far (sorted, on the device) and scratch */
     /* dedupe in parts (dedupe_parts_kernel.h): how far the round of this context's batch has come -- 0 none, 1 keys sent, 2 verdicts in; any
        planner and anything that indexes another batch puts it back to 0 (the round's state lies in the index buffers) -- and whether a
        round reported a failure since the last paffy_hip_dedupe_reset */
     int dd_part_stage = 0;
     bool dd_part_failed = false;
-    struct DedupeParts *dd_parts = nullptr; /* the round's entry map and verdicts; the owner's memory */
-    struct SplitState *split = nullptr; /* `paffy split_file` (split_host.h): grouping scratch and the files of the run */
+    std::unique_ptr<DedupeParts> dd_parts; /* the round's entry map and verdicts; the owner's memory */
+    std::unique_ptr<SplitState> split; /* `paffy split_file` (split_host.h): grouping scratch and the files of the run */
     DevBuf scan_part, emit_order, order_cnt, tile_keys, tile_order, tile_rank, tile_coff, tile_cbase, tile_cov, tile_level, tile_len, tile_items, tile_slots, tile_parts;
     bool keep_raw = false;    /* paffy_hip_keep_raw_sequences: seq_raw holds the bases as loaded (paf_pretty_print shows their case) */
     bool plan_seq_lookup = false; /* rec_qseq / rec_tseq belong to the current plan */
@@ -1091,12 +1098,12 @@ struct paffy_hip_ctx {
     uint32_t flat_piece_slots = 0;
     DevBuf bed_keys; /* paffy_hip_bed_sequence_keys: the first entry of every sequence, staged for k_bed_seq_keys */
     DevBuf bed_tab, bed_starts, bed_len, bed_off, bed_tiles;
-    struct BedParams *bed_params = nullptr; /* host copy */
+    std::unique_ptr<BedParams> bed_params; /* host copy */
     uint64_t bed_runs = 0;
     const uint8_t *tile_in = nullptr;
-    struct ChainState *chain = nullptr; /* `paffy chain` (chain_host.h) */
-    struct FastaState *fasta = nullptr; /* `faffy chunk | extract | merge`: FASTA index and item plan (fasta_host.h) */
-    struct CovState *cov = nullptr; /* `paffy tile` / `paffy to_bed` over any number of batches (coverage_host.h) */
+    std::unique_ptr<ChainState> chain; /* `paffy chain` (chain_host.h) */
+    std::unique_ptr<FastaState> fasta; /* `faffy chunk | extract | merge`: FASTA index and item plan (fasta_host.h) */
+    std::unique_ptr<CovState> cov; /* `paffy tile` / `paffy to_bed` over any number of batches (coverage_host.h) */
     /* the batch paffy_hip_query_names indexed last: paffy_hip_split_by_owner on the same batch reuses the index (one use) */
     const void *indexed_in = nullptr;
     int64_t indexed_len = 0;
@@ -1104,9 +1111,9 @@ struct paffy_hip_ctx {
     /* the index of batches whose names were asked for (paffy_hip_query_names), kept until the batch is split: a sharded tile asks
        for the names of all its batches before it splits the first one */
     struct KeptIndex {
-        const void *in;
-        int64_t len;
-        uint32_t n, n_seps;
+        const void *in = nullptr;
+        int64_t len = 0;
+        uint32_t n = 0, n_seps = 0;
         DevBuf meta, sep_pos, nl_idx;
     };
     std::vector<KeptIndex> kept_index;
@@ -1148,9 +1155,8 @@ struct paffy_hip_ctx {
     /* device buffers of the two slots of a closed stream (paffy_hip_stream_close), taken again by the next paffy_hip_stream_open: a
        hipMalloc of the tens of GB a slot's output needs takes 16 ms most of the time and 0.5-2.6 s right behind the hipFree of the stream
        before (tools/probes/d2h_pieces.py) */
-    void *kept_slot_buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; /* [slot][0 = input, 1 = output] */
-    size_t kept_slot_cap[2][2] = {{0, 0}, {0, 0}};
-    std::vector<struct paffy_hip_stream *> open_streams; /* streams of this context that are open: paffy_hip_destroy detaches them (a stream closed later frees
+    DevBuf kept_slot[2][2]; /* [slot][0 = input, 1 = output] */
+    std::vector<struct paffy_hip_stream *> open_streams; /* streams of this context that are open: the destructor detaches them (a stream closed later frees
                                                            its buffers itself instead of leaving them with a context that is gone) */
     std::string profile_only; /* when not empty: only launches of this kernel are bracketed (paffy_hip_profile_only) */
     std::vector<hipEvent_t> event_pool;
@@ -1170,17 +1176,12 @@ struct paffy_hip_ctx {
 
 static int ensure(paffy_hip_ctx *c, DevBuf &b, size_t bytes) {
     if (bytes <= b.cap) return 0;
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    size_t want = bytes + bytes / 2 + 256; /* room to grow: a batch a little larger than the last must not cost a free and an allocation */
-    if (hipMalloc(&b.p, want) != hipSuccess) { /* no room for the slack: an input that fits HBM at its exact size must not fail here */
+    HIPCHK(c, b.release());
+    /* room to grow: a batch a little larger than the last must not cost a free and an allocation */
+    if (b.alloc(bytes + bytes / 2 + 256) != hipSuccess) { /* no room for the slack: an input that fits HBM at its exact size must not fail here */
         (void)hipGetLastError();
-        b.p = nullptr;
-        want = bytes;
-        HIPCHK(c, hipMalloc(&b.p, want));
+        HIPCHK(c, b.alloc(bytes));
     }
-    b.cap = want;
     return 0;
 }
 
@@ -1312,49 +1313,8 @@ int paffy_hip_create(paffy_hip_ctx **out, int device) {
     return 0;
 }
 
-static void stream_detach(struct paffy_hip_stream *s);
-static void cov_free(paffy_hip_ctx *c); /* coverage_host.h state */
-static void dedupe_free(paffy_hip_ctx *c); /* dedupe_host.h state */
-static void dedupe_parts_free(paffy_hip_ctx *c); /* dedupe_parts_kernel.h state */
-static void split_free(paffy_hip_ctx *c); /* split_host.h state */
-static void index_drop(paffy_hip_ctx *c, const void *d_in);
-static void index_drop_all(paffy_hip_ctx *c);
-static void chain_free(paffy_hip_ctx *c);
-static void fasta_free(paffy_hip_ctx *c);
-
 void paffy_hip_destroy(paffy_hip_ctx *c) {
     if (!c) return;
-    for (paffy_hip_stream *st : c->open_streams) stream_detach(st); /* streams still open: they close later without this context */
-    c->open_streams.clear();
-    prof_collect(c);
-    for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    c->event_pool.clear();
-    cov_free(c);
-    chain_free(c);
-    fasta_free(c);
-    while (!c->kept_index.empty()) index_drop(c, c->kept_index.back().in);
-    for (paffy_hip_ctx::KeptIndex &k : c->index_pool) {
-        if (k.meta.p) (void)hipFree(k.meta.p);
-        if (k.sep_pos.p) (void)hipFree(k.sep_pos.p);
-        if (k.nl_idx.p) (void)hipFree(k.nl_idx.p);
-    }
-    c->index_pool.clear();
-    if (c->one_batch.p) (void)hipFree(c->one_batch.p);
-    DevBuf *bufs[] = {&c->tile_counts, &c->sep_pos, &c->nl_idx, &c->meta, &c->out_len, &c->out_rows, &c->status, &c->err_aux,
-                      &c->n_ops, &c->arena_off, &c->out_off, &c->w_list, &c->b_list, &c->b_list1, &c->arena, &c->info, &c->synth_sizes, &c->rec_plan, &c->ops_mirror, &c->seq_blob, &c->seq_table, &c->seq_names, &c->seq_name_off, &c->synth4_contigs, &c->synth4_q, &c->synth4_t, &c->seq_comp, &c->seq_raw, &c->pretty_off, &c->pretty_out, &c->pretty_err, &c->host_in, &c->host_out, &c->rec_stats, &c->flat_nd, &c->flat_rec, &c->flat_chunks, &c->flat_sums, &c->flat_done, &c->flat_items, &c->flat_pieces, &c->add_pieces, &c->add_scr_cnt, &c->add_scr_off, &c->add_new_cnt, &c->add_new_off, &c->add_text, &c->add_bad, &c->add_part, &c->add_scratch, &c->add_new_ops, &c->view_sums, &c->view_work, &c->view_layout, &c->view_ranges_dev, &c->bed_keys, &c->bed_tab, &c->bed_starts, &c->bed_len, &c->bed_off, &c->bed_tiles,
-                      &c->rec_qseq, &c->rec_tseq, &c->tile_keys, &c->tile_order, &c->tile_rank, &c->tile_coff, &c->tile_cbase,
-                      &c->tile_cov, &c->tile_level, &c->tile_len, &c->tile_items, &c->tile_slots, &c->tile_parts, &c->scan_part, &c->dedupe_keys, &c->emit_order, &c->order_cnt, &c->up_table, &c->up_names};
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    dedupe_free(c);
-    dedupe_parts_free(c);
-    split_free(c);
-    (void)paffy_hip_stream_trim(c);
-    delete c->bed_params;
-    if (c->h_info) (void)hipHostFree(c->h_info);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     delete c;
 }
 
@@ -1392,8 +1352,14 @@ static void plan_begin(paffy_hip_ctx *c, PlanKind kind, int64_t in_bytes, paffy_
     c->view_laid = false;
 }
 
-/* Separator index + header parse shared by plan and tile_plan. */
+/* the kept indexes (defined with index_keep, behind the kernels they need) */
 static void index_drop(paffy_hip_ctx *c, const void *d_in);
+static void index_drop_all(paffy_hip_ctx *c) {
+    while (!c->kept_index.empty()) index_drop(c, c->kept_index.back().in);
+    c->indexed_in = nullptr;
+}
+
+/* Separator index + header parse shared by plan and tile_plan. */
 static int index_and_parse(paffy_hip_ctx *c, const uint8_t *in, uint32_t len, uint32_t *n_lines_out, uint32_t lvl0_max = PAFFY_OPS_CAP, bool flat = false) {
     index_drop(c, in); /* a kept index of this buffer describes what it held before */
     c->dd_part_stage = 0;
@@ -2054,7 +2020,7 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
 #include "fasta_host.h"
 
 static CovState &cov_state(paffy_hip_ctx *c) {
-    if (!c->cov) c->cov = new CovState();
+    if (!c->cov) c->cov.reset(new CovState());
     return *c->cov;
 }
 static int64_t cov_in_bytes(const CovState &S) {
@@ -2063,33 +2029,8 @@ static int64_t cov_in_bytes(const CovState &S) {
     return n;
 }
 static ChainState &chain_state(paffy_hip_ctx *c) {
-    if (!c->chain) c->chain = new ChainState();
+    if (!c->chain) c->chain.reset(new ChainState());
     return *c->chain;
-}
-static void chain_free(paffy_hip_ctx *c) {
-    if (!c->chain) return;
-    ChainState &H = *c->chain;
-    DevBuf *bufs[] = {&H.qkey, &H.ghash, &H.ord1, &H.ord2, &H.rank, &H.start, &H.gid, &H.idx, &H.prank, &H.pred, &H.neg, &H.taken, &H.is_tail, &H.tail_of, &H.link, &H.total,
-                      &H.chain_of_tail, &H.chain_id, &H.score_key, &H.o1, &H.o2, &H.o3, &H.cls, &H.tag_chain, &H.tag_score, &H.check_key, &H.iota, &H.big_list, &H.n_big, &H.rank_of, &H.claim,
-                      &H.gidx, &H.gperm, &H.grank, &H.ai, &H.tails, &H.words};
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (DevBuf &b : H.i64)
-        if (b.p) (void)hipFree(b.p);
-    delete c->chain;
-    c->chain = nullptr;
-}
-static void cov_free(paffy_hip_ctx *c) {
-    if (!c->cov) return;
-    CovState &S = *c->cov;
-    DevBuf *bufs[] = {&S.meta, &S.batch_ptrs, &S.key_score, &S.key_chain, &S.idx, &S.info, &S.tmp, &S.k64a, &S.k64b, &S.v32a, &S.v32b, &S.order, &S.entries, &S.name_hash,
-                      &S.seq_len, &S.flags, &S.scan32, &S.first_entry, &S.contig_len, &S.contig_cov, &S.contig_slice0, &S.bm_words, &S.n_pairs, &S.bm_off, &S.pair_off,
-                      &S.aligned, &S.bitmap, &S.pairs, &S.pairs2, &S.item_start, &S.item_key, &S.item_idx, &S.item_key2, &S.item_order, &S.slots, &S.arena, &S.arena_used,
-                      &S.cov, &S.backup, &S.level, &S.err_aux, &S.out_len, &S.out_off, &S.names, &S.name_tab};
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    delete c->cov;
-    c->cov = nullptr;
 }
 
 extern "C" {
@@ -2421,11 +2362,12 @@ __global__ __launch_bounds__(PAFFY_NT) void k_scatter_lines(const uint8_t *src, 
 
 #include "bed_parts_kernel.h"
 
-/* the kept indexes (see paffy_hip_ctx::kept_index): copy out after query_names, copy back for split_by_owner */
+/* the kept indexes (see paffy_hip_ctx::kept_index): copy out after query_names, copy back for split_by_owner; an entry owns its buffers
+   and moves between kept_index and index_pool */
 static void index_drop(paffy_hip_ctx *c, const void *d_in) {
     for (size_t i = 0; i < c->kept_index.size(); i++)
         if (c->kept_index[i].in == d_in) {
-            c->index_pool.push_back(c->kept_index[i]); /* the buffers stay allocated for the next batch */
+            c->index_pool.push_back(std::move(c->kept_index[i])); /* the buffers stay allocated for the next batch */
             c->kept_index.erase(c->kept_index.begin() + (long)i);
             return;
         }
@@ -2435,7 +2377,7 @@ static int index_keep(paffy_hip_ctx *c, const void *d_in, int64_t in_len, uint32
     if (c->kept_index.size() >= 64) return 0; /* a caller that never splits: stop keeping */
     paffy_hip_ctx::KeptIndex k;
     if (!c->index_pool.empty()) {
-        k = c->index_pool.back();
+        k = std::move(c->index_pool.back());
         c->index_pool.pop_back();
     }
     k.in = d_in;
@@ -2447,7 +2389,7 @@ static int index_keep(paffy_hip_ctx *c, const void *d_in, int64_t in_len, uint32
     HIPCHK(c, hipMemcpyAsync(k.meta.p, c->meta.p, mb, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(k.sep_pos.p, c->sep_pos.p, sb, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(k.nl_idx.p, c->nl_idx.p, nb, hipMemcpyDeviceToDevice, c->stream));
-    c->kept_index.push_back(k);
+    c->kept_index.push_back(std::move(k));
     return 0;
 }
 /* 0: the index buffers describe d_in again; 1: nothing kept for it */
@@ -2470,10 +2412,6 @@ static int index_restore(paffy_hip_ctx *c, const void *d_in, int64_t in_len, uin
     return 1;
 }
 
-static void index_drop_all(paffy_hip_ctx *c) {
-    while (!c->kept_index.empty()) index_drop(c, c->kept_index.back().in);
-    c->indexed_in = nullptr;
-}
 static int64_t query_names_impl(paffy_hip_ctx *c, const void *d_in, int64_t in_len, int64_t cap, uint64_t *hashes, int64_t *weights, int64_t *records, bool with_target = false) {
     if (!c || !hashes || !weights || cap < 0) return PAFFY_E_ARG;
     if (in_len < 0 || in_len >= (1ll << 31) - 64 || (in_len > 0 && !d_in) || (reinterpret_cast<uintptr_t>(d_in) & 15)) return PAFFY_E_ARG;
@@ -2847,7 +2785,7 @@ static int upconvert_plan(paffy_hip_ctx *c, const void *d_in, int64_t in_len, bo
         LAUNCH(c, "k_line_size", k_line_size, dim3((nk + 1 + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, static_cast<const RecMeta *>(meta),
                static_cast<const uint32_t *>(c->tile_order.p), static_cast<const int64_t *>(c->tile_level.p), (uint64_t)nk, reinterpret_cast<uint64_t *>(lens));
         if (ensure(c, c->out_off, sizeof(int64_t) * ((size_t)nk + 1))) return PAFFY_E_HIP;
-        if (!c->dedupe) c->dedupe = new DedupeState();
+        if (!c->dedupe) c->dedupe.reset(new DedupeState());
         DedupeState &D = *c->dedupe; /* its scratch for the scan */
         size_t bytes = 0;
         RPCHK(c, rocprim::exclusive_scan(nullptr, bytes, lens, static_cast<int64_t *>(c->out_off.p), (int64_t)0, (size_t)nk + 1, rocprim::plus<int64_t>(), c->stream));
@@ -3012,7 +2950,7 @@ static int dedupe_plan_select(paffy_hip_ctx *c, const uint8_t *in, int64_t in_le
     LAUNCH(c, "k_dedupe_keys", k_dedupe_keys, dim3(grid), dim3(PAFFY_NT), 0, in, static_cast<const RecMeta *>(c->meta.p), n,
            static_cast<DedupeKey *>(c->dedupe_keys.p), static_cast<int64_t *>(c->tile_level.p));
     /* the reference's loop, record by record (impl/paf_dedupe.c:117-143): first seen wins -- on the device, dedupe_host.h */
-    if (!c->dedupe) c->dedupe = new DedupeState();
+    if (!c->dedupe) c->dedupe.reset(new DedupeState());
     uint32_t nk = 0, first_bad = n;
     {
         int rc = dedupe_select(c, *c->dedupe, static_cast<const DedupeKey *>(c->dedupe_keys.p), n, check_inverse, static_cast<uint32_t *>(c->tile_order.p), &nk, &first_bad);
@@ -3189,10 +3127,7 @@ int paffy_hip_run_host(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_st
 struct StreamSlot {
     char *h_in = nullptr;
     size_t h_cap = 0;
-    void *d_in = nullptr;
-    size_t d_in_cap = 0;
-    void *d_out = nullptr;
-    size_t d_out_cap = 0;
+    DevBuf d_in, d_out;
     hipEvent_t ev_in = nullptr, ev_emit = nullptr;
     int64_t out_len = 0, read_at = 0; /* bytes of output, bytes already handed to the host */
     bool busy = false;
@@ -3231,11 +3166,7 @@ static void stream_detach(paffy_hip_stream *s) { s->c = nullptr; }
 int paffy_hip_stream_trim(paffy_hip_ctx *c) {
     if (!c) return PAFFY_E_ARG;
     for (int k = 0; k < 2; k++)
-        for (int b = 0; b < 2; b++) {
-            if (c->kept_slot_buf[k][b]) (void)hipFree(c->kept_slot_buf[k][b]);
-            c->kept_slot_buf[k][b] = nullptr;
-            c->kept_slot_cap[k][b] = 0;
-        }
+        for (int b = 0; b < 2; b++) (void)c->kept_slot[k][b].release();
     return 0;
 }
 
@@ -3249,11 +3180,8 @@ int paffy_hip_stream_open(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n
     for (int32_t i = 0; i < n_stages; i++) s->stages[i] = stages[i];
     bool ok = hipStreamCreateWithFlags(&s->s_h2d, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&s->s_d2h, hipStreamNonBlocking) == hipSuccess;
     for (int k = 0; k < 2; k++) { /* the device buffers the stream before left with the context */
-        StreamSlot &sl = s->slot[k];
-        sl.d_in = c->kept_slot_buf[k][0]; sl.d_in_cap = c->kept_slot_cap[k][0];
-        sl.d_out = c->kept_slot_buf[k][1]; sl.d_out_cap = c->kept_slot_cap[k][1];
-        c->kept_slot_buf[k][0] = c->kept_slot_buf[k][1] = nullptr;
-        c->kept_slot_cap[k][0] = c->kept_slot_cap[k][1] = 0;
+        s->slot[k].d_in = std::move(c->kept_slot[k][0]);
+        s->slot[k].d_out = std::move(c->kept_slot[k][1]);
     }
     for (int k = 0; k < 2 && ok; k++) {
         StreamSlot &sl = s->slot[k];
@@ -3287,17 +3215,12 @@ void paffy_hip_stream_close(paffy_hip_stream *s) {
     for (int k = 0; k < 2; k++) {
         StreamSlot &sl = s->slot[k];
         if (sl.h_in) (void)hipHostFree(sl.h_in);
-        /* the device buffers stay with the context for its next stream (freed by paffy_hip_destroy or paffy_hip_stream_trim) */
-        void *bufs[2] = {sl.d_in, sl.d_out};
-        const size_t caps[2] = {sl.d_in_cap, sl.d_out_cap};
-        for (int b = 0; b < 2; b++) {
-            if (!bufs[b]) continue;
-            if (s->c && !s->c->kept_slot_buf[k][b]) {
-                s->c->kept_slot_buf[k][b] = bufs[b];
-                s->c->kept_slot_cap[k][b] = caps[b];
-            } else {
-                (void)hipFree(bufs[b]);
-            }
+        /* the device buffers stay with the context for its next stream (freed with it or by paffy_hip_stream_trim); where the context
+           is gone or holds one already, they go with the stream */
+        if (s->c) {
+            DevBuf(&kept)[2] = s->c->kept_slot[k];
+            if (!kept[0].p) kept[0] = std::move(sl.d_in);
+            if (!kept[1].p) kept[1] = std::move(sl.d_out);
         }
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
         if (sl.ev_emit) (void)hipEventDestroy(sl.ev_emit);
@@ -3335,24 +3258,20 @@ char *paffy_hip_stream_input(paffy_hip_stream *s, int64_t want, int64_t keep, in
 /* stage-in: room for the chunk on the device, its copy on the H2D stream, and the kernels wait for it */
 static int stream_stage_in(paffy_hip_stream *s, StreamSlot &sl, int64_t in_len) {
     paffy_hip_ctx *c = s->c;
-    if ((size_t)in_len + 64 > sl.d_in_cap) {
-        if (sl.d_in) HIPCHK(c, hipFree(sl.d_in));
-        sl.d_in = nullptr;
-        sl.d_in_cap = (size_t)in_len + (size_t)in_len / 4 + 4096;
-        HIPCHK(c, hipMalloc(&sl.d_in, sl.d_in_cap));
+    if ((size_t)in_len + 64 > sl.d_in.cap) {
+        HIPCHK(c, sl.d_in.release());
+        HIPCHK(c, sl.d_in.alloc((size_t)in_len + (size_t)in_len / 4 + 4096));
     }
-    if (in_len > 0) HIPCHK(c, hipMemcpyAsync(sl.d_in, sl.h_in, (size_t)in_len, hipMemcpyHostToDevice, s->s_h2d));
+    if (in_len > 0) HIPCHK(c, hipMemcpyAsync(sl.d_in.p, sl.h_in, (size_t)in_len, hipMemcpyHostToDevice, s->s_h2d));
     HIPCHK(c, hipEventRecord(sl.ev_in, s->s_h2d));
     HIPCHK(c, hipStreamWaitEvent(c->stream, sl.ev_in, 0));
     return 0;
 }
 /* room for `bytes` of output in the slot; slack: a quarter more, so that a chunk a little longer than the last costs no allocation */
 static int stream_out_room(paffy_hip_ctx *c, StreamSlot &sl, int64_t bytes, bool slack) {
-    if ((size_t)bytes + 64 <= sl.d_out_cap) return 0;
-    if (sl.d_out) HIPCHK(c, hipFree(sl.d_out));
-    sl.d_out = nullptr;
-    sl.d_out_cap = (size_t)bytes + (slack ? (size_t)bytes / 4 : 0) + 4096;
-    HIPCHK(c, hipMalloc(&sl.d_out, sl.d_out_cap));
+    if ((size_t)bytes + 64 <= sl.d_out.cap) return 0;
+    HIPCHK(c, sl.d_out.release());
+    HIPCHK(c, sl.d_out.alloc((size_t)bytes + (slack ? (size_t)bytes / 4 : 0) + 4096));
     return 0;
 }
 /* the writers of the slot's output are enqueued: the chunk is the stream's */
@@ -3368,7 +3287,7 @@ static int stream_issue_pieces(paffy_hip_stream *s, StreamSlot &sl) {
     while (s->n_issued < s->n_returned + 2 && s->issued_at < sl.out_len) {
         const int k = s->n_issued % 3;
         const int64_t n = sl.out_len - s->issued_at < (int64_t)s->piece_cap ? sl.out_len - s->issued_at : (int64_t)s->piece_cap;
-        HIPCHK(c, hipMemcpyAsync(s->piece[k], static_cast<char *>(sl.d_out) + s->issued_at, (size_t)n, hipMemcpyDeviceToHost, s->s_d2h));
+        HIPCHK(c, hipMemcpyAsync(s->piece[k], static_cast<char *>(sl.d_out.p) + s->issued_at, (size_t)n, hipMemcpyDeviceToHost, s->s_d2h));
         HIPCHK(c, hipEventRecord(s->ev_piece[k], s->s_d2h));
         s->piece_len[k] = n;
         s->issued_at += n;
@@ -3402,13 +3321,13 @@ int paffy_hip_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_info
     StreamSlot &sl = s->slot[s->fill];
     if (sl.busy || in_len > (int64_t)sl.h_cap) return PAFFY_E_STATE;
     int rc = stream_stage_in(s, sl, in_len);
-    if (!rc) rc = paffy_hip_plan(c, s->stages, s->n_stages, sl.d_in, in_len, info);
+    if (!rc) rc = paffy_hip_plan(c, s->stages, s->n_stages, sl.d_in.p, in_len, info);
     if (rc) return rc;
     sl.out_len = info->out_bytes;
     sl.read_at = 0;
     if (sl.out_len > 0) {
         rc = stream_out_room(c, sl, sl.out_len, true);
-        if (!rc) rc = paffy_hip_emit(c, sl.d_out, (int64_t)sl.d_out_cap);
+        if (!rc) rc = paffy_hip_emit(c, sl.d_out.p, (int64_t)sl.d_out.cap);
         if (rc) return rc;
     }
     return stream_submitted(s, sl);
@@ -3521,7 +3440,7 @@ int paffy_hip_bed_run(paffy_hip_ctx *c, const paffy_bed_opts *opts, paffy_plan_i
     HIPCHK(c, hipMemcpyAsync(d_nlen, name_len.data(), 4 * ns, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint64_t cov_total = S.cov_total;
-    if (!c->bed_params) c->bed_params = new BedParams;
+    if (!c->bed_params) c->bed_params.reset(new BedParams);
     BedParams &B = *c->bed_params;
     memset(&B, 0, sizeof(B));
     B.counts = static_cast<const uint16_t *>(S.cov.p);
@@ -4079,7 +3998,7 @@ static int view_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_in
     }
     if (sl.busy || s->view_open || in_len > (int64_t)sl.h_cap) return PAFFY_E_STATE;
     int rc = stream_stage_in(s, sl, in_len);
-    if (!rc) rc = paffy_hip_plan(c, s->stages, s->n_stages, sl.d_in, in_len, info);
+    if (!rc) rc = paffy_hip_plan(c, s->stages, s->n_stages, sl.d_in.p, in_len, info);
     if (rc) return rc;
     sl.out_len = sl.read_at = 0;
     sl.view_ranges = sl.view_range_at = 0;
@@ -4098,7 +4017,7 @@ static int view_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_in
             if (rc) return rc;
             for (int64_t r = 0; r < nr; r++) longest = std::max(longest, c->view_tab[2 * (size_t)r + 3] - c->view_tab[2 * (size_t)r + 1]);
             rc = stream_out_room(c, sl, longest, nr == 1);
-            if (!rc) rc = view_emit_range(c, 0, sl.d_out, (int64_t)sl.d_out_cap, &sl.out_len, sl.h_verdict);
+            if (!rc) rc = view_emit_range(c, 0, sl.d_out.p, (int64_t)sl.d_out.cap, &sl.out_len, sl.h_verdict);
             if (rc) return rc;
             sl.view_ranges = nr;
             info->out_bytes = total;
@@ -4110,7 +4029,7 @@ static int view_stream_submit(paffy_hip_stream *s, int64_t in_len, paffy_plan_in
            the first record the stages fail on -- the order the reference reads and works in: a plan of the parse alone tells */
         const paffy_stage pass = {PAFFY_PASS, 0.0f, 0.0f};
         paffy_plan_info parsed;
-        if (paffy_hip_plan(c, &pass, 1, sl.d_in, in_len, &parsed) == 0 && parsed.error.code) {
+        if (paffy_hip_plan(c, &pass, 1, sl.d_in.p, in_len, &parsed) == 0 && parsed.error.code) {
             *info = parsed;
             info->out_bytes = 0;
             info->n_rows = 0;
@@ -4148,7 +4067,7 @@ static int view_stream_read(paffy_hip_stream *s, const char **piece, int64_t *le
             sl.view_range_at++;
             s->issued_at = 0;
             sl.verdict_seen = false;
-            rc = view_emit_range(c, sl.view_range_at, sl.d_out, (int64_t)sl.d_out_cap, &sl.out_len, sl.h_verdict);
+            rc = view_emit_range(c, sl.view_range_at, sl.d_out.p, (int64_t)sl.d_out.cap, &sl.out_len, sl.h_verdict);
             if (rc) return rc;
             HIPCHK(c, hipEventRecord(sl.ev_emit, c->stream));
             continue;
@@ -4399,6 +4318,12 @@ int paffy_hip_profile_read(paffy_hip_ctx *c, const char **names, double *total_m
 
 int paffy_hip_malloc(void **p, int64_t bytes) { return hipMalloc(p, (size_t)bytes + 64) == hipSuccess ? 0 : PAFFY_E_HIP; }
 int paffy_hip_free(void *p) { return hipFree(p) == hipSuccess ? 0 : PAFFY_E_HIP; }
+int paffy_hip_device_buffers(int64_t *buffers, int64_t *bytes) {
+    if (!buffers || !bytes) return PAFFY_E_ARG;
+    *buffers = devbuf_held_buffers.load(std::memory_order_relaxed);
+    *bytes = devbuf_held_bytes.load(std::memory_order_relaxed);
+    return 0;
+}
 int paffy_hip_memcpy_h2d(void *d, const void *h, int64_t n) { return hipMemcpy(d, h, (size_t)n, hipMemcpyHostToDevice) == hipSuccess ? 0 : PAFFY_E_HIP; }
 int paffy_hip_memcpy_d2h(void *h, const void *d, int64_t n) { return hipMemcpy(h, d, (size_t)n, hipMemcpyDeviceToHost) == hipSuccess ? 0 : PAFFY_E_HIP; }
 int paffy_hip_device_count(void) {
@@ -4528,3 +4453,18 @@ int paffy_hip_synth4(paffy_hip_ctx *c, uint64_t r0, uint64_t n, void *d_out, int
 
 #include "seqload_kernel.h"
 #include "seqload_host.h"
+
+/* every command state is complete here. Nothing of this context may still be queued when its buffers go: they free themselves after
+   this body, behind the one synchronise (teardown only, on no timed path) */
+paffy_hip_ctx::~paffy_hip_ctx() {
+    for (paffy_hip_stream *st : open_streams) stream_detach(st); /* streams still open: they close later without this context */
+    open_streams.clear();
+    prof_collect(this);
+    for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
+    event_pool.clear();
+    (void)hipDeviceSynchronize();
+    if (side) (void)hipStreamDestroy(side);
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    if (h_info) (void)hipHostFree(h_info);
+}

@@ -46,7 +46,7 @@ static int seq_store_from_index(paffy_hip_ctx *c, FastaState &F) {
     std::vector<uint64_t> blob_off;
     int rc = seq_store_layout(c, n, ptr.data(), lens.data(), blob_off, offs.data());
     if (rc) return rc;
-    std::swap(c->seq_blob, F.bases); /* the compact bases are the store; the old store goes with F */
+    std::swap(c->seq_blob, F.dev.bases); /* the compact bases are the store; the old store goes with F */
     return seq_store_fill(c, F.n_bases);
 }
 
@@ -132,15 +132,15 @@ int paffy_hip_fasta_seen(paffy_hip_ctx *c, const void *d_paf, int64_t paf_len, i
     name_off.push_back((uint32_t)blob.size());
     std::vector<uint8_t> flag((size_t)n_names, 0);
     if (paf_len > 0) {
-        if (ensure(c, F.seen_names, blob.size() + 16) || ensure(c, F.seen_off, sizeof(uint32_t) * name_off.size()) || ensure(c, F.seen, (size_t)n_names))
+        if (ensure(c, F.dev.seen_names, blob.size() + 16) || ensure(c, F.dev.seen_off, sizeof(uint32_t) * name_off.size()) || ensure(c, F.dev.seen, (size_t)n_names))
             return PAFFY_E_HIP;
-        if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(F.seen_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(F.seen_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemsetAsync(F.seen.p, 0, (size_t)n_names, c->stream));
+        if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(F.dev.seen_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(F.dev.seen_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(F.dev.seen.p, 0, (size_t)n_names, c->stream));
         const int64_t blocks = (paf_len + FA_TILE - 1) / FA_TILE;
         LAUNCH(c, "k_fa_seen", k_fa_seen, dim3((unsigned)blocks), dim3(FA_NT), 0, static_cast<const uint8_t *>(d_paf), paf_len, with_target ? 1 : 0,
-               static_cast<const uint8_t *>(F.seen_names.p), static_cast<const uint32_t *>(F.seen_off.p), n_names, static_cast<uint8_t *>(F.seen.p));
-        HIPCHK(c, hipMemcpyAsync(flag.data(), F.seen.p, (size_t)n_names, hipMemcpyDeviceToHost, c->stream));
+               static_cast<const uint8_t *>(F.dev.seen_names.p), static_cast<const uint32_t *>(F.dev.seen_off.p), n_names, static_cast<uint8_t *>(F.dev.seen.p));
+        HIPCHK(c, hipMemcpyAsync(flag.data(), F.dev.seen.p, (size_t)n_names, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->profile) prof_collect(c);
     }

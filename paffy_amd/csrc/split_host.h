@@ -25,16 +25,6 @@ struct SplitState {
     std::vector<paffy_split_group> groups; /* of the current plan, in output order */
 };
 
-static void split_free(paffy_hip_ctx *c) {
-    if (!c->split) return;
-    SplitState &S = *c->split;
-    DevBuf *db[] = {&S.keys, &S.skeys, &S.idx, &S.order, &S.head, &S.head_of, &S.opens, &S.rank, &S.count, &S.start, &S.collide, &S.table, &S.name_len, &S.name_pos, &S.blob, &S.group_of, &S.file_of, &S.first, &S.offs, &S.tmp};
-    for (DevBuf *b : db)
-        if (b->p) (void)hipFree(b->p);
-    delete c->split;
-    c->split = nullptr;
-}
-
 static int split_sort_pairs(paffy_hip_ctx *c, SplitState &S, const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits = 64) {
     size_t bytes = 0;
     RPCHK(c, rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, 0, bits, c->stream));
@@ -146,7 +136,7 @@ static void split_assign_file(SplitState &S, const std::string &name, int64_t co
 
 int paffy_hip_split_begin(paffy_hip_ctx *c, int by_query, int64_t min_length) {
     if (!c) return PAFFY_E_ARG;
-    if (!c->split) c->split = new SplitState();
+    if (!c->split) c->split.reset(new SplitState());
     SplitState &S = *c->split;
     S.begun = true;
     S.by_query = by_query ? 1 : 0;

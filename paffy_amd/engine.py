@@ -201,6 +201,7 @@ def lib():
         L.paffy_hip_synth4_setup.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, i64, i64, C.c_int]
         L.paffy_hip_synth4.argtypes = [vp, C.c_uint64, C.c_uint64, vp, i64, C.POINTER(i64)]
         L.paffy_hip_device_count.restype = C.c_int
+        L.paffy_hip_device_buffers.argtypes = [C.POINTER(i64), C.POINTER(i64)]
         L.paffy_hip_fasta_index.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64)]
         L.paffy_hip_fasta_records.restype = i64
         L.paffy_hip_fasta_records.argtypes = [vp, i64, i64, C.POINTER(FastaRecord)]
@@ -232,6 +233,15 @@ def lib():
         L.paffy_hip_stream_view_status.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(_Error)]
         _lib = L
     return _lib
+
+
+def device_buffers():
+    """(buffers, bytes) of device memory the library owns in this process right now: contexts, their command states, streams."""
+    n, b = C.c_int64(), C.c_int64()
+    rc = lib().paffy_hip_device_buffers(C.byref(n), C.byref(b))
+    if rc:
+        raise RuntimeError(f"paffy_hip_device_buffers failed ({rc})")
+    return n.value, b.value
 
 
 def _pad16(n):
