@@ -487,6 +487,12 @@ int paffy_hip_plan_stats(paffy_hip_ctx *ctx, int64_t sums[6]);
  * (paffy_amd/csrc/flat_kernel.h); *left = the records it left to the record kernels (-1: the plan did not take the flat pass),
  * reasons[k] = how many for reason k (FLAT_WHY_* there). The outputs do not depend on who sized a record; the tests use this to
  * know that the pass under test really ran.
+ * Stage lists with PAFFY_ADD_MISMATCHES: the flat pass takes the list that consists of it alone, [PAFFY_ADD_MISMATCHES, PAFFY_STATS]
+ * under paffy_hip_stats_only, and -- `paffy add_mismatches | paffy trim -r | paffy filter` -- [PAFFY_ADD_MISMATCHES, PAFFY_TRIM_IDENTITY],
+ * [PAFFY_ADD_MISMATCHES, PAFFY_FILTER] and [PAFFY_ADD_MISMATCHES, PAFFY_TRIM_IDENTITY, PAFFY_FILTER] (paffy_amd/csrc/flat_add_pipe_kernel.h:
+ * *left >= 0; reasons[11], FLAT_WHY_ENCODER, counts the records the encoder on the pieces did not keep -- a missing or short sequence, an
+ * irregular cigar, no cigar at all, a failing paf_check). Any other list with PAFFY_ADD_MISMATCHES and a further stage, and any
+ * PAFFY_NO_CHECK form, is sized by the record kernels (*left = -1).
  */
 int paffy_hip_flat_stats(paffy_hip_ctx *ctx, int64_t *left, int64_t reasons[16]);
 /* The same six sums for every record of the batch (6 * n_records values, record by record): the numbers of the per-alignment line of

@@ -22,6 +22,9 @@
  *
  * A record anything of this does not take (what the flat pass leaves, a sequence that is missing or too short, sums beyond 2^30, more
  * than 62 passed-through ops in a row) is left to the record kernels, which report what there is to report.
+ *
+ * With an identity trim, a filter or both behind the command the same kernels run up to the second scan; k_add_fill and k_add_final are
+ * then replaced by the two kernels of flat_add_pipe_kernel.h (add_fill_pieces<true> below is the hook).
  */
 #ifndef PAFFY_FLAT_ADD_KERNEL_H_
 #define PAFFY_FLAT_ADD_KERNEL_H_
@@ -172,25 +175,41 @@ __global__ __launch_bounds__(64 * ADD_WAVES) void k_add_count(AddParams A) {
     }
 }
 
-/* walk 2, one wave per piece */
-__global__ __launch_bounds__(64 * ADD_WAVES) void k_add_fill(AddParams A) {
-    __shared__ uint32_t s_slots[ADD_WAVES][PAFFY_FILL_SLOTS];
-    const KParams &P = A.P;
+/* walk 2, one wave per piece. SUMS (flat_add_pipe_kernel.h): the piece's new ops summed where they are written, a PieceSum per slot in
+   nsums[] -- cnt the new ops (all 32 bits: one piece of 8191M ops on alternating columns becomes far more than 65 535), m the bases of
+   the = ops, x those of the X, I and D ops, text the bytes of their text; the bases of a piece do not change with the encoding, so x is
+   what is left of the parsed piece's m + x, and ins / del are the parsed ones */
+template <bool SUMS>
+__device__ __forceinline__ void add_fill_pieces(const AddParams &A, uint32_t (*s_slots)[PAFFY_FILL_SLOTS], PieceSum *nsums) {
     const uint32_t n_waves = gridDim.x * ADD_WAVES, wave = uni(threadIdx.x >> 6);
     for (uint32_t slot = uni(blockIdx.x * ADD_WAVES + (threadIdx.x >> 6)); slot < A.n_piece_slots; slot += n_waves) {
         const uint32_t rec = uni(A.pieces[slot].rec);
         if (rec == FLAT_NO_CHUNK) continue;
         const uint32_t cnt = uni(A.sums[slot].cnt) & 0xffffu, n_items = uni(A.sums[slot].extra), n_nm = cnt - uni(A.sums[slot].rows);
-        uint32_t text = 0;
+        uint32_t text = 0, eq = 0;
+        bool filled = false;
         const uint64_t at = A.new_off[slot];
         if (cnt && !uni(A.rec_bad[rec]) && at + uni(A.new_cnt[slot]) <= A.new_cap && A.scr_off[slot] + uni(A.scr_cnt[slot]) <= A.scr_cap) {
             const uint32_t *items = A.scratch + A.scr_off[slot];
-            text = mismatch_fill_wave(items, n_items, items + n_items, n_nm, 0u, A.new_ops + at, s_slots[wave]);
+            if (SUMS) text = mismatch_fill_wave<true>(items, n_items, items + n_items, n_nm, 0u, A.new_ops + at, s_slots[wave], &eq);
+            else text = mismatch_fill_wave(items, n_items, items + n_items, n_nm, 0u, A.new_ops + at, s_slots[wave]);
+            filled = true;
         }
-        if ((threadIdx.x & 63u) == 0) A.text_cnt[slot] = text;
+        if ((threadIdx.x & 63u) == 0) {
+            A.text_cnt[slot] = text;
+            if (SUMS) {
+                const uint32_t all = uni(A.sums[slot].m) + uni(A.sums[slot].x);
+                uint4 *o = reinterpret_cast<uint4 *>(nsums + slot);
+                o[0] = make_uint4(filled ? uni(A.new_cnt[slot]) : 0u, filled ? eq : 0u, filled ? all - eq : 0u, filled ? uni(A.sums[slot].ins) : 0u);
+                o[1] = make_uint4(filled ? uni(A.sums[slot].del) : 0u, 0u, 0u, text);
+            }
+        }
         __builtin_amdgcn_wave_barrier();
     }
-    (void)P;
+}
+__global__ __launch_bounds__(64 * ADD_WAVES) void k_add_fill(AddParams A) {
+    __shared__ uint32_t s_slots[ADD_WAVES][PAFFY_FILL_SLOTS];
+    add_fill_pieces<false>(A, s_slots, nullptr);
 }
 
 /* one lane per record: the line's length and the plan for the line writers */

@@ -25,7 +25,9 @@
  *
  * The two mismatch commands, each as a pipe of its own, use k_flat_parse and the pieces with kernels of their own in place of the sizing
  * kernels: `add_mismatches` the encoder on the pieces (flat_add_kernel.h), `add_mismatches -a` the merge of the M/=/X runs across the
- * pieces (flat_remove_kernel.h; = and X ops are its normal input, so FLAT_F_NONPLAIN does not send a record away there).
+ * pieces (flat_remove_kernel.h; = and X ops are its normal input, so FLAT_F_NONPLAIN does not send a record away there). `add_mismatches` in
+ * front of an identity trim, a filter or both runs the encoder and then this file's trim and filter on summaries of the NEW ops
+ * (flat_add_pipe_kernel.h: FlatRecT and flat_trim_prefix are templates over the op word for its sake).
  */
 #ifndef PAFFY_FLAT_KERNEL_H_
 #define PAFFY_FLAT_KERNEL_H_
@@ -308,13 +310,15 @@ __device__ __forceinline__ FlatPre flat_sub(const FlatPre &a, const FlatPre &b) 
 /* a word another lane of this wave has just stored: read past the L1 */
 __device__ __forceinline__ uint32_t flat_ld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-/* One record's pieces: their inclusive prefix sums, lane p = piece p for records of at most 64 pieces, in HBM (scanned in place) for longer ones. */
-struct FlatRec {
+/* One record's pieces: their inclusive prefix sums, lane p = piece p for records of at most 64 pieces, in HBM (scanned in place) for longer ones.
+   OPW: the word an op takes where the walks read it -- the 2-byte mirror here, the 4-byte new ops of the encoder in flat_add_pipe_kernel.h */
+template <typename OPW>
+struct FlatRecT {
     const PieceSum *ps;
     uint32_t np, n_ops;
     bool in_regs;
     FlatPre inc; /* in_regs: lane p holds the sums of pieces [0, p] */
-    const uint16_t *ops;
+    const OPW *ops;
     bool want_text;
     bool extra_icount; /* PieceSum::extra counts I ops (a pipe with a stats stage), not digits */
 
@@ -376,6 +380,7 @@ struct FlatRec {
         return a;
     }
 };
+typedef FlatRecT<uint16_t> FlatRec;
 
 /* The window of raw ops a record's view is, with the prefix sums at its two ends. */
 struct FlatView {
@@ -478,7 +483,8 @@ __device__ __forceinline__ bool flat_ratio_ge(uint32_t num, uint32_t den, float 
  * hold a hit (float32 conversions and the divide are off by less than 2e-7 relative) and is not looked at, the others are walked by
  * the wave, one op per lane, from the mirror.
  */
-__device__ __forceinline__ void flat_trim_prefix(const FlatRec &R, FlatState &s, FlatView &v, float thr_f, float id_f, int64_t max_trim) {
+template <typename REC>
+__device__ __forceinline__ void flat_trim_prefix(const REC &R, FlatState &s, FlatView &v, float thr_f, float id_f, int64_t max_trim) {
     const double thr = (double)thr_f, idd = (double)id_f;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w_end = v.lo + v.n;
@@ -1272,7 +1278,8 @@ __device__ __forceinline__ bool flat_find_aligned(const FlatRec &R, const FlatVi
 
 /* what the record kernels take instead: nothing is written for the record but its mark */
 enum { FLAT_WHY_HEADER = 0, FLAT_WHY_IRREG = 1, FLAT_WHY_SUMS = 2, FLAT_WHY_EMPTY = 3, FLAT_WHY_CHECK = 4, FLAT_WHY_TRIM_ASSERT = 5, FLAT_WHY_STAGE = 6,
-       FLAT_WHY_NONPLAIN = 7, FLAT_WHY_ROW_SHAPE = 8, FLAT_WHY_DIGITS = 9, FLAT_WHY_HEADER_LEN = 10 };
+       FLAT_WHY_NONPLAIN = 7, FLAT_WHY_ROW_SHAPE = 8, FLAT_WHY_DIGITS = 9, FLAT_WHY_HEADER_LEN = 10,
+       FLAT_WHY_ENCODER = 11 /* flat_add_pipe_kernel.h: the encoder on the pieces did not keep the record (what FLAT_MODE_ADD leaves) */ };
 __device__ __forceinline__ void flat_leave(const FlatSizeParams &F, uint32_t rec, int why) {
     if ((threadIdx.x & 63u) == 0) {
         atomicAdd(&F.P.info->flat_reason[why], 1u);

@@ -33,6 +33,7 @@
 #include "flat_add_kernel.h"
 #include "flat_remove_kernel.h"
 #include "flat_view_kernel.h"
+#include "flat_add_pipe_kernel.h"
 #include "coverage_kernel.h"
 #include "bed_kernel.h"
 #include "fasta_kernel.h"
@@ -1143,6 +1144,7 @@ struct paffy_hip_ctx {
     bool plan_stats_only = false; /* the last plan took FLAT_MODE_VIEW: it has sums, no ops and no line plan */
     bool plan_split = false;      /* the last plan is paffy_hip_split_plan's: a line plan with a group table (paffy_hip_split_groups) */
     DevBuf view_sums;             /* flat_view_kernel.h: six sums per piece slot */
+    DevBuf add_nsums;             /* flat_add_pipe_kernel.h: a PieceSum of the new ops per piece slot */
     DevBuf view_work;             /* view_line_kernel.h: sizes, row offsets and the offsets' verdict of a paffy_hip_plan_view_* call */
     /* paffy_hip_plan_view_layout: the sizes of the batch's blocks, their running sums, the rows' bytes and offsets and the verdict of a range
        (view_layout), the ranges the cut kernel wrote (view_ranges_dev) and their copy on the host (view_tab: n_ranges + 1 entries) */
@@ -1455,7 +1457,9 @@ enum FlatMode {
     FLAT_MODE_PASS, /* the flat pass (flat_kernel.h); what it leaves goes to the record kernels */
     FLAT_MODE_ADD,  /* `paffy add_mismatches` alone: the flat parse and the encoder on its pieces (flat_add_kernel.h) */
     FLAT_MODE_REMOVE, /* `paffy add_mismatches -a` alone: the flat parse and the merge of the M/=/X runs on its pieces (flat_remove_kernel.h) */
-    FLAT_MODE_VIEW  /* `paffy view` without rows, under paffy_hip_stats_only: the flat parse and the count walk alone (flat_view_kernel.h) */
+    FLAT_MODE_VIEW, /* `paffy view` without rows, under paffy_hip_stats_only: the flat parse and the count walk alone (flat_view_kernel.h) */
+    FLAT_MODE_ADD_PIPE /* `paffy add_mismatches` in front of an identity trim, a filter or both: the encoder on the pieces, then trim and filter
+                          on the summaries of the new ops (flat_add_pipe_kernel.h) */
 };
 struct StageClass {
     paffy_stage stages[PAFFY_MAX_STAGES]; /* kinds without the PAFFY_NO_CHECK flag; a leading dechunk is its paf_check */
@@ -1532,6 +1536,13 @@ static int classify_stages(paffy_hip_ctx *c, const paffy_stage *stages, int32_t 
        has said so -- without the setting [ADD, STATS] leaves ops and a line plan behind, and goes through the record kernels */
     else if (c->stats_only && n_stages == 2 && norm[0].kind == PAFFY_ADD_MISMATCHES && norm[1].kind == PAFFY_STATS && s.nocheck_mask == 0 && !flat_off && c->n_seqs > 0)
         s.flat = FLAT_MODE_VIEW;
+    /* [ADD, TRIM_IDENTITY], [ADD, FILTER], [ADD, TRIM_IDENTITY, FILTER] (`paffy add_mismatches | paffy trim -r | paffy filter`): the encoder on
+       the pieces, the trim and the filter on the summaries of the new ops (flat_add_pipe_kernel.h); every other list with add_mismatches and
+       a further stage stays with the record kernels */
+    else if (norm[0].kind == PAFFY_ADD_MISMATCHES && s.nocheck_mask == 0 && !flat_off && c->n_seqs > 0 &&
+             ((n_stages == 2 && (norm[1].kind == PAFFY_TRIM_IDENTITY || norm[1].kind == PAFFY_FILTER)) ||
+              (n_stages == 3 && norm[1].kind == PAFFY_TRIM_IDENTITY && norm[2].kind == PAFFY_FILTER)))
+        s.flat = FLAT_MODE_ADD_PIPE;
     else if (lean_or_filter && s.nocheck_mask == 0 && !flat_off) s.flat = FLAT_MODE_PASS;
     /* the first instantiation that knows every stage kind: the lean kinds; them and add_mismatches (the encoder wants the registers); them
        with filter / trim -f / stats / check; no stage of the kinds that came with the encoder; all */
@@ -1629,8 +1640,9 @@ static FlatParams flat_params(const paffy_hip_ctx *c, uint32_t items_mode) {
 }
 
 /* `paffy add_mismatches` alone: the flat parse, then the encoder on its pieces, repeated with more scratch while a batch asks for more.
-   *need_records: the encoder left records to the record kernels. */
-static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records) {
+   pipe: stages stand behind it (FLAT_MODE_ADD_PIPE) -- the same tries, with the two kernels of flat_add_pipe_kernel.h in the place of
+   k_add_fill and k_add_final. *need_records: the encoder left records to the record kernels. */
+static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records, bool pipe = false) {
     KParams &kp = c->kp;
     const uint32_t len = kp.in_len;
     const FlatParams fp = flat_params(c, 1u);
@@ -1641,6 +1653,7 @@ static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records)
         ensure(c, c->add_new_off, sizeof(uint64_t) * (size_t)n_slots) || ensure(c, c->add_text, sizeof(uint32_t) * (size_t)n_slots) ||
         ensure(c, c->add_bad, sizeof(uint32_t) * (size_t)(n_lines + 1)) || ensure(c, c->add_part, sizeof(uint64_t) * (size_t)(n_sblocks + 1)))
         return PAFFY_E_HIP;
+    if (pipe && ensure(c, c->add_nsums, sizeof(PieceSum) * (size_t)n_slots)) return PAFFY_E_HIP;
     /* item words + passed-through ops, and the new 4-byte ops: about 2.4 and 2.9 bytes per byte of text for 2 %-divergent sequences; a
        batch that needs more is encoded again with what it asked for (the totals come back with the plan's one synchronisation) */
     size_t scr_words = std::max<size_t>(c->add_scratch.cap / 4, (size_t)len + ((size_t)1 << 20)), new_words = std::max<size_t>(c->add_new_ops.cap / 4, (size_t)len + ((size_t)1 << 20));
@@ -1687,8 +1700,16 @@ static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records)
         LAUNCH(c, "k_scan32_part", k_scan32_part, dim3(n_sblocks), dim3(256), 0, ap.new_cnt, n_slots, static_cast<uint64_t *>(c->add_new_off.p), static_cast<uint64_t *>(c->add_part.p));
         LAUNCH(c, "k_scan32_fix", k_scan32_fix, dim3(n_sblocks), dim3(256), 0, n_slots, n_sblocks, static_cast<uint64_t *>(c->add_new_off.p), static_cast<const uint64_t *>(c->add_part.p),
                reinterpret_cast<uint64_t *>(&static_cast<DevInfo *>(c->info.p)->add_new_total));
-        LAUNCH(c, "k_add_fill", k_add_fill, dim3(2048), dim3(64 * ADD_WAVES), 0, ap);
-        LAUNCH(c, "k_add_final", k_add_final, dim3((n_lines + 255) / 256), dim3(256), 0, ap);
+        if (pipe) {
+            AddPipeParams pp;
+            pp.A = ap;
+            pp.nsums = static_cast<PieceSum *>(c->add_nsums.p);
+            LAUNCH(c, "k_addp_fill", k_addp_fill, dim3(2048), dim3(64 * ADD_WAVES), 0, pp);
+            LAUNCH(c, "k_addp_size", k_addp_size, dim3(std::min<uint32_t>(2048u, (n_lines + ADDP_SIZE_WAVES - 1) / ADDP_SIZE_WAVES)), dim3(64 * ADDP_SIZE_WAVES), 0, pp);
+        } else {
+            LAUNCH(c, "k_add_fill", k_add_fill, dim3(2048), dim3(64 * ADD_WAVES), 0, ap);
+            LAUNCH(c, "k_add_final", k_add_final, dim3((n_lines + 255) / 256), dim3(256), 0, ap);
+        }
         kp.new_ops = ap.new_ops;
         if (post_scans(c, n_lines)) return PAFFY_E_HIP;
         if (fetch_info(c)) return PAFFY_E_HIP;
@@ -1709,6 +1730,8 @@ static int plan_flat_add(paffy_hip_ctx *c, uint32_t n_lines, bool *need_records)
     }
     *need_records = c->h_info->flat_legacy > 0;
     c->flat_left = c->h_info->flat_legacy;
+    if (pipe)
+        for (int k = 0; k < 16; k++) c->flat_reasons[k] = c->h_info->flat_reason[k];
     kp.flat_done = static_cast<const uint8_t *>(c->flat_done.p);
     return 0;
 }
@@ -1995,6 +2018,7 @@ int paffy_hip_plan(paffy_hip_ctx *c, const paffy_stage *stages, int32_t n_stages
         bool need_records = true;
         uint32_t flat_g_count = 0;
         if (s.flat == FLAT_MODE_ADD) rc = plan_flat_add(c, n_lines, &need_records);
+        else if (s.flat == FLAT_MODE_ADD_PIPE) rc = plan_flat_add(c, n_lines, &need_records, true);
         else if (s.flat == FLAT_MODE_REMOVE) rc = plan_flat_remove(c, n_lines, &need_records);
         else if (s.flat == FLAT_MODE_VIEW) rc = plan_flat_view(c, n_lines, &need_records);
         else if (s.flat == FLAT_MODE_PASS) rc = plan_flat(c, s, n_lines, &need_records, &flat_g_count);

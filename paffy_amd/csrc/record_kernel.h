@@ -1321,10 +1321,14 @@ __device__ __forceinline__ void wait_all_but_newest(uint32_t n, uint32_t a, uint
  *               16-31 passed-through ops in front of the run, counted from the batch's first
  */
 #define PAFFY_FILL_SLOTS 256u /* starts per pass: 1 KiB of the wave's text staging area */
+/* EQ: *eq_out = the bases of the = ops written (the match bits of the items' used columns and the = ops passed through): the summaries of
+   flat_add_pipe_kernel.h; the other callers' instantiation carries none of it */
+template <bool EQ = false>
 __device__ __forceinline__ uint32_t mismatch_fill_wave(const uint32_t *items, uint32_t n_items, const uint32_t *nm_list, uint32_t n_nm, uint32_t out_base, uint32_t *blk,
-                                                        uint32_t *slots) {
+                                                        uint32_t *slots, uint32_t *eq_out = nullptr) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t text = 0; /* bytes of cigar text of the ops this lane wrote (digits + letter) */
+    uint32_t eq = 0;   /* EQ: bases of the = ops this lane accounts for */
     uint32_t done = out_base; /* ops placed so far (the pending run included), the passed-through ones too; wave-uniform */
     uint32_t nm_done = 0;     /* ops of nm_list placed so far; wave-uniform */
     uint32_t carry_w = 0;     /* word of the last item of the iteration before */
@@ -1349,6 +1353,7 @@ __device__ __forceinline__ uint32_t mismatch_fill_wave(const uint32_t *items, ui
         const bool first = (w >> 24) & 1u;
         const uint32_t gap = first ? w >> 26 : 0u;
         const uint32_t ginc = wave_incl_scan_u32(gap), gtot = wave_last_u32(ginc);
+        if (EQ) eq += (uint32_t)__popc(m & ((1u << nb) - 1u));
         /* the words of the iteration after this one, before any store of this one */
         since = 0;
         w_next = 0;
@@ -1374,6 +1379,7 @@ __device__ __forceinline__ uint32_t mismatch_fill_wave(const uint32_t *items, ui
                 if (t < gap) {
                     blk[done + rex + ginc - gap + t] = ow;
                     text += dec_len_short(ow >> 3) + 1u;
+                    if (EQ) eq += (ow & 7u) == (uint32_t)OP_EQ ? ow >> 3 : 0u;
                 }
                 since++;
             }
@@ -1382,6 +1388,7 @@ __device__ __forceinline__ uint32_t mismatch_fill_wave(const uint32_t *items, ui
                 const uint32_t ow = __hip_atomic_load(nm_list + nm_done + ginc - gap + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 blk[done + rex + ginc - gap + t] = ow;
                 text += dec_len_short(ow >> 3) + 1u;
+                if (EQ) eq += (ow & 7u) == (uint32_t)OP_EQ ? ow >> 3 : 0u;
             }
         }
         nm_done += gtot;
@@ -1445,7 +1452,9 @@ __device__ __forceinline__ uint32_t mismatch_fill_wave(const uint32_t *items, ui
         const uint32_t ow = __hip_atomic_load(nm_list + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         blk[done + (t - nm_done)] = ow;
         text += dec_len_short(ow >> 3) + 1u;
+        if (EQ) eq += (ow & 7u) == (uint32_t)OP_EQ ? ow >> 3 : 0u;
     }
+    if (EQ) *eq_out = wave_last_u32(wave_incl_scan_u32(eq));
     return wave_last_u32(wave_incl_scan_u32(text));
 }
 
@@ -3630,7 +3639,7 @@ __global__ __launch_bounds__(PAFFY_NT, PAFFY_SIZE_OCC) void k_size_lds(KParams P
     if ((P.meta[rec].cg_len >> 1) > P.lvl0_max && P.meta[rec].err == 0) return;
     /* short cigars belong to the one-wave build of this kernel (g64, launched first), everything else -- and what did not fit the
        wave's op store, marked in n_ops -- to the four-wave build */
-    const bool is_short = P.meta[rec].cg_len <= P.wave_max_bytes;
+    const bool is_short = P.wave_max_bytes != 0 && P.meta[rec].cg_len <= P.wave_max_bytes; /* (no one-wave build is launched for a bound of 0: a record without a cigar is the four-wave build's then) */
     if (PAFFY_NWAVE == 1 ? !is_short : (is_short && P.n_ops[rec] != 0xffffffffu)) return;
     size_lds_one<MASK>(P, rec, ops_lds, L);
 }

@@ -58,7 +58,8 @@ struct DevInfo {
     uint32_t flat_legacy;
     uint32_t flat_defer; /* records k_flat_lane handed on to k_flat_size */
     uint32_t n_items; /* EmitItem entries written (segments of the records too long for one wave of the row writer) */
-    uint32_t flat_reason[16]; /* why: FLAT_WHY_* of flat_kernel.h (diagnostics, paffy_hip_flat_stats) */
+    uint32_t flat_reason[16]; /* why: FLAT_WHY_* of flat_kernel.h (diagnostics, paffy_hip_flat_stats); 11 = FLAT_WHY_ENCODER: under [ADD_MISMATCHES, TRIM_IDENTITY /
+                                 FILTER] the encoder on the pieces did not keep the record (flat_add_pipe_kernel.h) */
     unsigned long long add_scr_total, add_new_total; /* flat_add_kernel.h: words of scratch / of new ops the batch needs */
     uint32_t s_count; /* shatter records whose rows k_emit_rows_short writes (RecPlan flag bit 23), bumped by every sizing kernel; a sizing
                          pass that runs again counts its records again: the host only asks whether it is zero */
@@ -74,7 +75,9 @@ struct RecPlan {
                        bit17 the 4-byte ops live in the arena block arena_off[rec] (rebuilt by add_mismatches), not in the mirror,
                        bit18 the mirror holds 2-byte words (every length below 8192),
                        bit19 a long shatter record written as EmitItem segments by k_emit_rows,
-                       bit20 the 4-byte ops are words of new_ops[] (flat add_mismatches and flat add_mismatches -a: flat_add_kernel.h, flat_remove_kernel.h), bit21 the row pieces are in row_pieces[],
+                       bit20 the 4-byte ops are words of new_ops[] (flat add_mismatches and flat add_mismatches -a: flat_add_kernel.h, flat_remove_kernel.h; behind
+                       add_mismatches + identity trim / filter, flat_add_pipe_kernel.h, arena_off[rec] names the first op of the trimmed window and lo stays 0),
+                       bit21 the row pieces are in row_pieces[],
                        bit22 the line's cigar is a stretch of the input's text: k_emit_copy (wq[0] = first byte from cg_off, wt[0] = bytes;
                        wq[1] / wt[1] = new length of a first / last op a fixed trim shortened, wq[2] / wt[2] = bytes of that op's text),
                        bit23 rows written by k_emit_rows_short: a shatter record of the one-wave row writer whose first constant row piece

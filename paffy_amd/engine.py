@@ -64,6 +64,9 @@ class PafError(RuntimeError):
         self.exit_status = exit_status
 
 
+FLAT_WHY_ENCODER = 11  # flat_stats(): under [ADD_MISMATCHES, TRIM_IDENTITY / FILTER] the encoder on the pieces did not keep the record
+
+
 def stage(kind, trim_identity=0.05, trim_fraction=1.0):
     """One command of a pipe. trim_identity = `paffy trim -r`, trim_fraction = `-t` (impl/paf_trim.c:14-16)."""
     return Stage(kind, trim_identity, trim_fraction)
@@ -817,7 +820,8 @@ class Engine:
         return out, info
 
     def flat_stats(self):
-        """(records the flat sizing pass left to the record kernels in the last plan, or -1 when the plan did not take it; counts per reason)"""
+        """(records the flat sizing pass left to the record kernels in the last plan, or -1 when the plan did not take it; counts per reason:
+        FLAT_WHY_* of csrc/flat_kernel.h, e.g. FLAT_WHY_ENCODER)"""
         left, why = C.c_int64(), (C.c_int64 * 16)()
         self._check(lib().paffy_hip_flat_stats(self._ctx, C.byref(left), why), "paffy_hip_flat_stats")
         return left.value, list(why)

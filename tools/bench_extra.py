@@ -7,7 +7,11 @@ STATS] and its sums, nothing emitted -- by the default plan and under Engine.sta
 view_lines: the sums-only plan, then the per-record stats lines of `paffy view` written into device memory (paffy_hip_plan_view_sizes /
 _view_text, view_line_kernel.h): plan + sizes + text, everything resident. shatter / invert_trim_shatter --names short: the cfg3 stream
 with hs.chrN / pt.chrN renamed to chrN (first row pieces of 15 and 16 bytes, half and half): the share of such records, flat_stats and,
-for shatter, the rows each row writer wrote."""
+for shatter, the rows each row writer wrote. add_trim / add_filter: `paffy add_mismatches | paffy trim -r` and `| paffy filter -u 0.9`
+as the fused stage lists [ADD_MISMATCHES, TRIM_IDENTITY] and [ADD_MISMATCHES, FILTER] on the cfg4 stream (flat_add_pipe_kernel.h), sequences
+resident: the plan alone and plan + emit per repetition (the first two warm up and are not counted), median and spread (largest - smallest)
+of the others, flat_stats, the per-kernel times, and with --sha the SHA-256 of the output (to compare two builds of the library, chosen by
+PAFFY_HIP_LIB, byte for byte before their times)."""
 import argparse
 import json
 import os
@@ -37,7 +41,7 @@ def main():
     ap.add_argument("--records", type=int, default=200000)
     ap.add_argument("--mean-ops", type=int, default=2048)
     ap.add_argument("--contigs", type=int, default=24, help="contigs of the synthetic stream (chain: fewer contigs = larger groups)")
-    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "view", "view_stats_only", "view_lines", "dedupe", "bed", "stats", "chain",
+    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "add_trim", "add_filter", "view", "view_stats_only", "view_lines", "dedupe", "bed", "stats", "chain",
                                                     "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload", "invert_trim_shatter"])
     ap.add_argument("--names", default="std", choices=["std", "short"],
                     help="shatter, invert_trim_shatter: `short` renames hs.chrN / pt.chrN to chrN on the host (outside the timed region): chr1-chr9 "
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
     ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome")
     ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the plan (the smallest counts)")
+    ap.add_argument("--sha", action="store_true", help="add_trim, add_filter: copy the last repetition's output to the host and print its SHA-256")
     ap.add_argument("--parts", type=int, default=0, help="chain: chain in parts -- this many contexts on the one GPU, taken in turn (0: the plain one-context run)")
     a = ap.parse_args()
     if a.cmd == "chain" and a.parts > 0:
@@ -60,7 +65,8 @@ def main():
 
     eng = paffy_amd.Engine()
     view = a.cmd in ("view", "view_stats_only", "view_lines")
-    if a.cmd in ("add", "remove_eqx") or view:
+    add_pipe = {"add_trim": [paffy_amd.ADD_MISMATCHES, paffy_amd.TRIM_IDENTITY], "add_filter": [paffy_amd.ADD_MISMATCHES, paffy_amd.FILTER]}.get(a.cmd)
+    if a.cmd in ("add", "remove_eqx") or view or add_pipe:
         # cfg4: 24 + 24 contigs of 50-250 Mb generated on the device, records on homologous bases (2 % substitutions)
         t0 = time.perf_counter()
         if os.environ.get("PAFFY_X_SMALL_GENOME"):  # experiment: genomes small enough to stay in the caches
@@ -127,8 +133,23 @@ def main():
         eng.stats_only(True)
     sums = None
     text_out, text_bytes = None, 0
-    for rep in range(a.repeats):
+    plan_s = []
+    for rep in range(a.repeats + (2 if add_pipe else 0)):
         t0 = time.perf_counter()
+        if add_pipe:  # the plan alone (it synchronises on its own), then the emit; no events round the launches while the clock runs
+            eng.profile(False)
+            info = eng.plan([paffy_amd.stage(k) for k in add_pipe], buf, nbytes)
+            t1 = time.perf_counter()
+            out = eng.alloc_out(info.out_bytes)
+            eng.emit(out)
+            eng.sync()
+            dt = time.perf_counter() - t0
+            assert info.error.code == 0
+            if rep < 2:  # warm-up: buffers grown, the second try of the encoder and the allocator's first blocks behind it
+                continue
+            plan_s.append(t1 - t0)
+            res.append(dt)
+            continue
         if view:  # the plan and its sums; nothing is emitted (the plan synchronises on its own)
             info = eng.plan([paffy_amd.stage(paffy_amd.ADD_MISMATCHES), paffy_amd.stage(paffy_amd.STATS)], buf, nbytes)
             sums = eng.plan_stats()
@@ -179,6 +200,11 @@ def main():
         assert info.error.code == 0
         res.append(dt)
     dt = min(res)
+    if add_pipe:  # the per-kernel times: one more repetition, with events
+        eng.profile(True)
+        eng.plan([paffy_amd.stage(k) for k in add_pipe], buf, nbytes)
+        eng.emit(out)
+        eng.sync()
     prof = {k: round(v[0] / max(1, v[1]), 3) for k, v in eng.profile_read().items()}
     extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx") or view else {}
     if view:
@@ -194,6 +220,17 @@ def main():
             extra["rows_by_kernel"] = by
     if a.cmd == "view_lines":
         extra["text_bytes"] = text_bytes
+    if add_pipe:
+        import statistics
+
+        left, why = eng.flat_stats()
+        extra.update(flat_left=left, flat_why=list(why), median_s=round(statistics.median(res), 5), spread_s=round(max(res) - min(res), 5),
+                     plan_median_s=round(statistics.median(plan_s), 5), plan_spread_s=round(max(plan_s) - min(plan_s), 5), plan_repeats=[round(x, 5) for x in plan_s],
+                     lib=os.path.basename(os.path.dirname(paffy_amd.engine.library_path())) + "/" + os.path.basename(paffy_amd.engine.library_path()))
+        if a.sha:
+            import hashlib
+
+            extra["out_sha256"] = hashlib.sha256(out[:info.out_bytes].cpu().numpy().tobytes()).hexdigest()
     print(json.dumps({**extra, "cmd": a.cmd, "records": a.records, "mean_ops": a.mean_ops, "in_bytes": nbytes, "out_bytes": int(info.out_bytes),
                       "seconds": round(dt, 4), "repeats": [round(x, 4) for x in res], "records_per_s": round(a.records / dt, 1),
                       "GBps": round((nbytes + info.out_bytes) / dt / 1e9, 1), "kernel_ms": prof}))
