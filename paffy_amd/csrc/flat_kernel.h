@@ -396,6 +396,46 @@ struct FlatView {
     __device__ __forceinline__ int64_t tt() const { return (int64_t)tm() + (int64_t)tx() - (int64_t)ins_v(); }
 };
 
+/* The end ops of a window that fixed trims have shortened, in RAW order (lo: the window's raw first op, hi: its raw last one; both the same
+   op in a window of one), so that an invert or a reversed pass moves nothing: the view's front is hi when v.rev. sub = bases cut, len = the
+   op's raw length (1 while nothing is cut), x = it is an X op (its bases count in FlatView::cut_x, else in cut_m). */
+struct FlatCuts {
+    uint32_t sub_lo = 0, sub_hi = 0, len_lo = 1, len_hi = 1;
+    bool x_lo = false, x_hi = false;
+    __device__ __forceinline__ uint32_t near_sub(bool rev) const { return rev ? sub_hi : sub_lo; }
+    __device__ __forceinline__ uint32_t far_sub(bool rev) const { return rev ? sub_lo : sub_hi; }
+    __device__ __forceinline__ uint32_t near_len(bool rev) const { return rev ? len_hi : len_lo; }
+    __device__ __forceinline__ uint32_t far_len(bool rev) const { return rev ? len_lo : len_hi; }
+    __device__ __forceinline__ bool near_x(bool rev) const { return rev ? x_hi : x_lo; }
+    /* the view's front op: `sub` bases cut of an op of raw length `len` */
+    __device__ __forceinline__ void set_near(bool rev, uint32_t sub, uint32_t len, bool x) {
+        if (rev) { sub_hi = sub; len_hi = len; x_hi = x; }
+        else { sub_lo = sub; len_lo = len; x_lo = x; }
+    }
+    __device__ __forceinline__ void set_far(bool rev, uint32_t sub, uint32_t len, bool x) { set_near(!rev, sub, len, x); }
+    /* the sums the view subtracts */
+    __device__ __forceinline__ void apply(FlatView &v) const {
+        v.cut_m = (x_lo ? 0u : sub_lo) + (x_hi ? 0u : sub_hi);
+        v.cut_x = (x_lo ? sub_lo : 0u) + (x_hi ? sub_hi : 0u);
+    }
+};
+/* what a sizing kernel carries of them: nothing where no fixed trim can stand in the pipe */
+struct FlatNoCuts {
+    static constexpr uint32_t sub_lo = 0, sub_hi = 0;
+    __device__ __forceinline__ uint32_t near_sub(bool) const { return 0u; }
+    __device__ __forceinline__ uint32_t far_sub(bool) const { return 0u; }
+    __device__ __forceinline__ uint32_t near_len(bool) const { return 1u; }
+    __device__ __forceinline__ uint32_t far_len(bool) const { return 1u; }
+    __device__ __forceinline__ void set_near(bool, uint32_t, uint32_t, bool) const {}
+    __device__ __forceinline__ void apply(FlatView &) const {}
+    __device__ __forceinline__ FlatCuts *ptr() { return nullptr; }
+};
+struct FlatHasCuts : FlatCuts {
+    __device__ __forceinline__ FlatCuts *ptr() { return this; }
+};
+template <bool ON> struct FlatCutsOf { typedef FlatNoCuts type; };
+template <> struct FlatCutsOf<true> { typedef FlatHasCuts type; };
+
 /* what the transforms touch of a record: the rest of its fields is read again when the output is sized */
 struct FlatState {
     int64_t qlen, qs, qe, tlen, ts, te;
@@ -482,12 +522,22 @@ __device__ __forceinline__ bool flat_ratio_ge(uint32_t num, uint32_t den, float 
  * record_kernel.h with the record's pieces as the chunks: a piece whose best-case prefix identity clears the threshold by 1e-5 cannot
  * hold a hit (float32 conversions and the divide are off by less than 2e-7 relative) and is not looked at, the others are walked by
  * the wave, one op per lane, from the mirror.
+ * CUTS (behind a fixed trim, *C): the view's first and last op count with their shortened lengths, and every cumulative sum in front of a
+ * piece past the first op is smaller by the front cut; the pieces' own mismatch sums are then too large by at most the cuts, so the bounds
+ * stay bounds. A trim that removes the shortened front op forgets its cut: the window's new first op is whole.
  */
-template <typename REC>
-__device__ __forceinline__ void flat_trim_prefix(const REC &R, FlatState &s, FlatView &v, float thr_f, float id_f, int64_t max_trim) {
+template <typename REC, bool CUTS = false>
+__device__ __forceinline__ void flat_trim_prefix(const REC &R, FlatState &s, FlatView &v, float thr_f, float id_f, int64_t max_trim, FlatCuts *C = nullptr) {
     const double thr = (double)thr_f, idd = (double)id_f;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w_end = v.lo + v.n;
+    uint32_t near_m = 0, near_x = 0, near = 0, far = 0; /* bases missing in the view's first (M / = or X) and last op */
+    if (CUTS) {
+        near = C->near_sub(v.rev);
+        far = C->far_sub(v.rev);
+        near_m = C->near_x(v.rev) ? 0u : near;
+        near_x = near - near_m;
+    }
     const uint32_t nb = (R.np + 63u) >> 6;
     /* last view index with cumulative <= max_trim and prefix identity < threshold (impl/paf.c:820-838): pieces in descending view order */
     int32_t trim_idx = -1;
@@ -517,7 +567,11 @@ __device__ __forceinline__ void flat_trim_prefix(const REC &R, FlatState &s, Fla
         if (b_cnt > w_end) { b_cnt = w_end; b_m = v.whi.m; b_x = v.whi.x; }
         const bool live = p < R.np && b_cnt > a_cnt;
         /* cumulative sums in front of the piece, in view order */
-        const uint32_t c_m = v.rev ? v.whi.m - b_m : a_m - v.wlo.m, c_x = v.rev ? v.whi.x - b_x : a_x - v.wlo.x;
+        uint32_t c_m = v.rev ? v.whi.m - b_m : a_m - v.wlo.m, c_x = v.rev ? v.whi.x - b_x : a_x - v.wlo.x;
+        if (CUTS && (v.rev ? b_cnt < w_end : a_cnt > v.lo)) { /* the view's first op lies in front of the piece */
+            c_m -= near_m;
+            c_x -= near_x;
+        }
         const uint32_t chunk_x = b_x - a_x;
         const bool may_hit = live && !(c_m > 0 && (double)c_m >= thr * 1.00001 * (double)(c_m + c_x + chunk_x)) &&
                              !(max_trim >= 0 && (int64_t)c_m + (int64_t)c_x > max_trim);
@@ -541,6 +595,7 @@ __device__ __forceinline__ void flat_trim_prefix(const REC &R, FlatState &s, Fla
                     const uint32_t w = R.ops[v.rev ? w_end - 1u - i : v.lo + i];
                     len = w >> 3;
                     code = w & 7u;
+                    if (CUTS) len -= (i == 0u ? near : 0u) + (i == v.n - 1u ? far : 0u);
                 }
                 const uint32_t is_m = 0u - ((0x9u >> code) & 1u);
                 const uint32_t im = wave_incl_scan_u32(len & is_m), ix = wave_incl_scan_u32(len & ~is_m);
@@ -574,6 +629,7 @@ __device__ __forceinline__ void flat_trim_prefix(const REC &R, FlatState &s, Fla
                 const uint32_t w = R.ops[v.rev ? w_end - 1u - i : v.lo + i];
                 len = w >> 3;
                 code = w & 7u;
+                if (CUTS) len -= (i == 0u ? near : 0u) + (i == v.n - 1u ? far : 0u);
             }
             const uint32_t is_m = 0u - ((0x9u >> code) & 1u);
             const uint32_t vm = len & is_m, vx = len & ~is_m;
@@ -600,6 +656,11 @@ __device__ __forceinline__ void flat_trim_prefix(const REC &R, FlatState &s, Fla
         }
     }
     v.n -= count;
+    if (CUTS) { /* the shortened first op is gone and its cut with it (both cuts when nothing is left) */
+        C->set_near(v.rev, 0u, 1u, false);
+        if (v.n == 0) C->set_far(v.rev, 0u, 1u, false);
+        C->apply(v);
+    }
     const int64_t d_t = old_tt - v.tt(), d_q = old_tq - v.tq();
     s.ts += d_t;
     if (s.same) s.qs += d_q;
@@ -1211,11 +1272,15 @@ __device__ __forceinline__ void flat_find(const FlatRec &R, const FlatView &v, b
  * reversed view): ops are popped while the front op is an indel or fewer than `end` aligned bases (M, =, X) are gone, i.e. up to the first
  * aligned op whose inclusive sum of aligned bases exceeds `end` -- that op stays, shortened by what is missing. Found like flat_find():
  * the piece by the summaries, the op by a walk of the piece. The view's LAST op counts `far_cut` bases less (the cut the other end has
- * made already; the summaries do not know it, so the last piece may be walked in vain). Returns false when no op stops the trim (it
- * takes everything); else *idx = the op's view index, *tb = the aligned bases in front of it, *len its length (less far_cut), *code.
+ * made already; the summaries do not know it, so the last piece may be walked in vain). Its FIRST op counts `near_cut` bases less (an
+ * earlier fixed trim's cut at this end): every inclusive sum from that op on is smaller by near_cut, so the search runs on the raw sums
+ * for end + near_cut and stops at the same op. Returns false when no op stops the trim (it takes everything); else *idx = the op's view
+ * index, *tb = the RAW aligned bases in front of it (near_cut too many when idx > 0), *len its length (less far_cut when it is the view's
+ * last op, raw otherwise), *code.
  */
-__device__ __forceinline__ bool flat_find_aligned(const FlatRec &R, const FlatView &v, uint32_t end, uint32_t far_cut, uint32_t &idx, uint32_t &tb, uint32_t &len_out,
-                                                   uint32_t &code_out) {
+__device__ __forceinline__ bool flat_find_aligned(const FlatRec &R, const FlatView &v, uint32_t end_cut, uint32_t near_cut, uint32_t far_cut, uint32_t &idx, uint32_t &tb,
+                                                   uint32_t &len_out, uint32_t &code_out) {
+    const uint32_t end = end_cut + near_cut;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w_end = v.lo + v.n;
     const uint32_t nb = (R.np + 63u) >> 6;
@@ -1315,8 +1380,11 @@ __device__ __forceinline__ uint32_t flat_cut_digits(const uint32_t *len, const u
     const uint32_t a = dl(len[0]) - dl(len[0] - amt[0]);
     return first_only ? a : a + dl(len[1]) - dl(len[1] - amt[1]);
 }
-/* FIXED: the instantiation for pipes that end with a fixed trim (`paffy trim -f`); the others do not carry its code */
-template <bool FIXED>
+/* FIXED: the instantiations for pipes with a fixed trim (`paffy trim -f`) and no shatter; the others do not carry its code. 1: one fixed
+   trim, the pipe's last stage (`trim -f` alone, `invert | trim -f`): nothing looks at the shortened end ops but the sizing below. 2: a fixed
+   trim at any place, any number of times: the stages behind it must know the shortened end ops (FlatCuts), which costs `trim -f` alone a
+   few per cent of this kernel's time -- so it keeps its own instantiation */
+template <int FIXED>
 __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t rec, uint32_t (*cross)[3]) {
     const KParams &P = F.P;
     const uint32_t lane = threadIdx.x & 63u;
@@ -1383,8 +1451,9 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
     v.wlo = R.piece_prefix(0);
     v.whi = R.piece_prefix(R.np);
     bool swapped = false, shatter = false, checked = false, rewritten = false;
-    uint32_t fx_amt[2] = {0, 0}, fx_len[2] = {1, 1}; /* fixed trim: bases cut from the op it stops at and that op's length, front / back of the view */
+    uint32_t fx_amt[2] = {0, 0}, fx_len[2] = {1, 1}; /* fixed trim: bases cut from the view's first / last op and that op's raw length (one length for both in a window of one op) */
     uint32_t sub_lo = 0, sub_hi = 0;                 /* ... as the writers want them: cut from the window's raw first / last op */
+    typename FlatCutsOf<FIXED == 2>::type C;            /* both are taken from this when the stages are done: what the fixed trims have cut from the window's end ops */
     for (int32_t si = 0; si < P.n_stages; si++) {
         const paffy_stage st = P.stages[si];
         if (si > 0) { /* what `paf_write | paf_parse` between two processes does to the record */
@@ -1399,9 +1468,10 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
             swapped = !swapped;
             rc = flat_check(s, v);
         } else if (FIXED && st.kind == PAFFY_TRIM_FIXED) {
-            /* paf_trim_end_fraction + paf_trim_ends (impl/paf.c:578-598), the pipe's last stage (the host sees to that): half of the fraction of
-               the aligned bases goes at either end. The ops in front of the op a cut stops at leave the window as in the identity trim; the op
-               itself stays, shorter (FlatView::cut_m / cut_x for the sums, sub_lo / sub_hi for the writers) */
+            /* paf_trim_end_fraction + paf_trim_ends (impl/paf.c:578-598), at any place of the pipe: half of the fraction of the aligned bases
+               goes at either end. The ops in front of the op a cut stops at leave the window as in the identity trim; the op itself stays,
+               shorter (FlatCuts; FlatView::cut_m / cut_x for the sums). A cut that stops in an op an earlier trim has shortened adds to
+               that op's cut; one that goes past it starts afresh in the op it stops in */
             const float pct = st.p1;
             if (!(pct >= 0.0f && pct <= 1.0f)) return flat_leave(F, rec, FLAT_WHY_STAGE); /* the record kernels report the assert */
             const int64_t aligned = (int64_t)v.tm() + (int64_t)v.tx() - (int64_t)(v.whi.ins - v.wlo.ins) - (int64_t)(v.whi.del - v.wlo.del);
@@ -1410,9 +1480,12 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
             for (int pass = 0; pass < 2; pass++) {
                 if (pass == 1) v.rev = !v.rev; /* the back is the front of the reversed view */
                 uint32_t idx = 0, tb = 0, len = 1, code = 0;
-                if (!flat_find_aligned(R, v, end, pass == 1 ? fx_amt[0] : 0u, idx, tb, len, code)) return flat_leave(F, rec, FLAT_WHY_EMPTY); /* nothing is left */
+                const uint32_t near = C.near_sub(v.rev), far = FIXED == 2 ? C.far_sub(v.rev) : (pass == 1 ? fx_amt[0] : 0u);
+                if (!flat_find_aligned(R, v, end, near, far, idx, tb, len, code)) return flat_leave(F, rec, FLAT_WHY_EMPTY); /* nothing is left */
+                if (FIXED == 2 && idx) tb -= near;
                 const uint32_t amt = tb < end ? end - tb : 0u;
                 const int64_t old_tt = v.tt(), old_tq = v.tq();
+                if (FIXED == 2) C.set_near(v.rev, idx ? amt : near + amt, len + (idx == v.n - 1u ? far : 0u), code == (uint32_t)OP_X);
                 if (idx) {
                     const FlatPre cut = R.raw_prefix(v.rev ? v.lo + v.n - idx : v.lo + idx);
                     if (v.rev) {
@@ -1423,10 +1496,16 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
                     }
                     v.n -= idx;
                 }
-                if (code == (uint32_t)OP_X) v.cut_x += amt;
-                else v.cut_m += amt;
-                if (v.rev) sub_hi += amt;
-                else sub_lo += amt;
+                if (FIXED == 2) {
+                    C.apply(v);
+                } else { /* the one cut of this end */
+                    if (code == (uint32_t)OP_X) v.cut_x += amt;
+                    else v.cut_m += amt;
+                    if (v.rev) sub_hi += amt;
+                    else sub_lo += amt;
+                    fx_amt[pass] = amt;
+                    fx_len[pass] = len;
+                }
                 const int64_t d_t = old_tt - v.tt(), d_q = old_tq - v.tq();
                 if (pass == 0) {
                     s.ts += d_t;
@@ -1437,8 +1516,6 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
                     if (s.same) s.qe -= d_q;
                     else s.qs += d_q;
                 }
-                fx_amt[pass] = amt;
-                fx_len[pass] = len;
             }
             v.rev = !v.rev;
             rc = flat_check(s, v);
@@ -1457,7 +1534,8 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
                     v.swp = !v.swp;
                     if (!s.same) v.rev = !v.rev;
                 }
-                flat_trim_prefix(R, s, v, thr_f, id_f, max_trim);
+                if (FIXED == 2) flat_trim_prefix<FlatRec, true>(R, s, v, thr_f, id_f, max_trim, C.ptr()); /* the end ops may be shortened */
+                else flat_trim_prefix(R, s, v, thr_f, id_f, max_trim);
                 if (pass == 1) {
                     flat_invert(s);
                     v.swp = !v.swp;
@@ -1486,6 +1564,12 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
         }
         if (rc) return flat_leave(F, rec, FLAT_WHY_CHECK);
         if (st.kind != PAFFY_STATS) checked = st.kind != PAFFY_PASS && st.kind != PAFFY_FILTER;
+    }
+    if (FIXED == 2) {
+        sub_lo = C.sub_lo; sub_hi = C.sub_hi;
+        fx_amt[0] = C.near_sub(v.rev); fx_amt[1] = C.far_sub(v.rev);
+        fx_len[0] = C.near_len(v.rev); fx_len[1] = C.far_len(v.rev);
+        if (v.n == 1u) fx_len[0] = fx_len[1] = fx_amt[0] ? fx_len[0] : fx_len[1];
     }
     RecPlan *plan = static_cast<RecPlan *>(P.rec_plan) + rec;
     int64_t bytes, rows;
@@ -1634,7 +1718,7 @@ __device__ __forceinline__ void flat_size_one(const FlatSizeParams &F, uint32_t 
     }
 }
 
-template <bool FIXED>
+template <int FIXED>
 __global__ __launch_bounds__(64 * FLAT_SIZE_WAVES) void k_flat_size(FlatSizeParams F) {
     __shared__ uint32_t s_cross[FLAT_SIZE_WAVES][FLAT_MAX_CROSS][3]; /* per wave: the powers of ten inside a record's coordinate ranges (flat_find) */
     /* the records k_flat_lane handed on, one wave each (what derives from the wave's number is wave-uniform: told to the compiler, it

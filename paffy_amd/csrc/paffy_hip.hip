@@ -1466,7 +1466,9 @@ struct StageClass {
     int32_t n_stages;
     uint32_t nocheck_mask, fix_query, fix_target;
     bool upconvert; /* `paffy upconvert`: a plan of its own */
-    bool need_seqs, add_not_last, has_stats, has_shatter, fixed_last;
+    bool need_seqs, add_not_last, has_stats, has_shatter;
+    bool has_fixed;   /* FLAT_MODE_PASS with a fixed trim at any place: every record takes the wave kernel (k_flat_size<1> or <2>) */
+    bool fixed_inner; /* ... and a stage behind a fixed trim: the instantiation whose stages know the shortened end ops */
     FlatMode flat;
     uint32_t size_mask; /* the instantiation of the sizing kernels: PAFFY_MASK_LEAN / ADD / SEL / PLAIN / ALL */
 };
@@ -1520,13 +1522,15 @@ static int classify_stages(paffy_hip_ctx *c, const paffy_stage *stages, int32_t 
        record on the chunks' summaries; what it leaves (FLAT_F_IRREG and friends) goes through the record kernels as before. It also
        knows `paffy filter` (a predicate on the sums it keeps anyway), the stats stage of `paffy view -s` (paf_stats_calc,
        impl/paf.c:236-260: sums the pieces' summaries hold, with the I ops counted where a shatter pipe counts the digits of its rows --
-       so not both in one pipe), and a fixed trim (`paffy trim -f`) as the pipe's last stage: the wave kernel finds the two ops it stops
-       at (flat_find_aligned) */
-    s.fixed_last = n_stages > 0 && norm[n_stages - 1].kind == PAFFY_TRIM_FIXED;
-    const uint32_t flat_kinds = PAFFY_MASK_LEAN | (1u << PAFFY_FILTER) | (s.has_shatter ? 0u : 1u << PAFFY_STATS) | (dechunk ? 1u << PAFFY_CHECK : 0u);
+       so not both in one pipe), and a fixed trim (`paffy trim -f`) at any place and any number of times in a pipe without a shatter: the
+       wave kernel finds the two ops it stops at (flat_find_aligned), and the stages behind it count those ops with their shortened
+       lengths (FlatCuts). A pipe with a fixed trim and a shatter stays with the record kernels: the one-wave row writer does not
+       write shortened end ops */
+    s.has_fixed = ((kinds >> PAFFY_TRIM_FIXED) & 1u) && !s.has_shatter;
+    const uint32_t flat_kinds = PAFFY_MASK_LEAN | (1u << PAFFY_FILTER) | (s.has_shatter ? 0u : 1u << PAFFY_STATS) | (dechunk ? 1u << PAFFY_CHECK : 0u) |
+                                (s.has_fixed ? 1u << PAFFY_TRIM_FIXED : 0u);
     bool lean_or_filter = n_stages > 0;
-    for (int32_t i = 0; i < n_stages; i++)
-        lean_or_filter = lean_or_filter && (((flat_kinds >> norm[i].kind) & 1u) || (s.fixed_last && i == n_stages - 1));
+    for (int32_t i = 0; i < n_stages; i++) lean_or_filter = lean_or_filter && ((flat_kinds >> norm[i].kind) & 1u);
     static const bool flat_off = getenv("PAFFY_NO_FLAT") != nullptr;
     /* `paffy add_mismatches` alone (BASELINE cfg4): the same parse, the encoder on the pieces (flat_add_kernel.h) */
     if (n_stages == 1 && norm[0].kind == PAFFY_ADD_MISMATCHES && s.nocheck_mask == 0 && !flat_off && c->n_seqs > 0) s.flat = FLAT_MODE_ADD;
@@ -1544,6 +1548,8 @@ static int classify_stages(paffy_hip_ctx *c, const paffy_stage *stages, int32_t 
               (n_stages == 3 && norm[1].kind == PAFFY_TRIM_IDENTITY && norm[2].kind == PAFFY_FILTER)))
         s.flat = FLAT_MODE_ADD_PIPE;
     else if (lean_or_filter && s.nocheck_mask == 0 && !flat_off) s.flat = FLAT_MODE_PASS;
+    s.has_fixed = s.has_fixed && s.flat == FLAT_MODE_PASS;
+    for (int32_t i = 0; i + 1 < n_stages; i++) s.fixed_inner = s.fixed_inner || (s.has_fixed && norm[i].kind == PAFFY_TRIM_FIXED);
     /* the first instantiation that knows every stage kind: the lean kinds; them and add_mismatches (the encoder wants the registers); them
        with filter / trim -f / stats / check; no stage of the kinds that came with the encoder; all */
     s.size_mask = PAFFY_MASK_ALL;
@@ -1858,11 +1864,12 @@ static int plan_flat(paffy_hip_ctx *c, const StageClass &s, uint32_t n_lines, bo
     if (ensure(c, c->flat_rec, sizeof(uint32_t) * (size_t)(n_lines + 1))) return PAFFY_E_HIP;
     fs.defer = static_cast<uint32_t *>(c->flat_rec.p);
     /* one lane per record for the records that need little, one wave per record for the rest (a list whose length only the device knows) */
-    if (s.fixed_last) { /* one wave per record for all of them */
-        LAUNCH(c, "k_flat_size", k_flat_size<true>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
+    if (s.has_fixed) { /* one wave per record for all of them */
+        if (s.fixed_inner) LAUNCH(c, "k_flat_size", k_flat_size<2>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
+        else LAUNCH(c, "k_flat_size", k_flat_size<1>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
     } else {
         LAUNCH(c, "k_flat_lane", k_flat_lane, dim3((n_lines + 255) / 256), dim3(256), 0, fs);
-        LAUNCH(c, "k_flat_size", k_flat_size<false>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
+        LAUNCH(c, "k_flat_size", k_flat_size<0>, dim3(std::min<uint32_t>(2048u, (n_lines + FLAT_SIZE_WAVES - 1) / FLAT_SIZE_WAVES)), dim3(64 * FLAT_SIZE_WAVES), 0, fs);
     }
     if (post_scans(c, n_lines)) return PAFFY_E_HIP;
     if (fetch_info(c)) return PAFFY_E_HIP;

@@ -41,7 +41,7 @@ def main():
     ap.add_argument("--records", type=int, default=200000)
     ap.add_argument("--mean-ops", type=int, default=2048)
     ap.add_argument("--contigs", type=int, default=24, help="contigs of the synthetic stream (chain: fewer contigs = larger groups)")
-    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "shatter", "remove", "remove_eqx", "filter", "add", "add_trim", "add_filter", "view", "view_stats_only", "view_lines", "dedupe", "bed", "stats", "chain",
+    ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "trimf_invert", "trimf_filter", "trimf_stats", "shatter", "remove", "remove_eqx", "filter", "add", "add_trim", "add_filter", "view", "view_stats_only", "view_lines", "dedupe", "bed", "stats", "chain",
                                                     "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload", "invert_trim_shatter"])
     ap.add_argument("--names", default="std", choices=["std", "short"],
                     help="shatter, invert_trim_shatter: `short` renames hs.chrN / pt.chrN to chrN on the host (outside the timed region): chr1-chr9 "
@@ -127,6 +127,8 @@ def main():
     kinds["stats"] = paffy_amd.STATS
     kinds["pass"] = paffy_amd.PASS
     kinds["upconvert"] = paffy_amd.UPCONVERT
+    # a fixed trim in front of another stage, on the stream of `trimf`: sized by the flat pass's wave kernel (flat_left 0), by the record kernels before (-1)
+    fixed_pipe = {"trimf_invert": paffy_amd.INVERT, "trimf_filter": paffy_amd.FILTER, "trimf_stats": paffy_amd.STATS}.get(a.cmd)
     res = []
     eng.profile(True)
     if a.cmd in ("view_stats_only", "view_lines"):
@@ -191,6 +193,8 @@ def main():
             st = paffy_amd.stage(paffy_amd.TRIM_FIXED, 0.05, 0.1) if a.cmd == "trimf" else (paffy_amd.stage_dechunk() if a.cmd == "dechunk" else None)
             if a.cmd == "invert_trim_shatter":
                 info = eng.plan([paffy_amd.stage(paffy_amd.INVERT), paffy_amd.stage(paffy_amd.TRIM_IDENTITY), paffy_amd.stage(paffy_amd.SHATTER)], buf, nbytes)
+            elif fixed_pipe:
+                info = eng.plan([paffy_amd.stage(paffy_amd.TRIM_FIXED, 0.05, 0.1), paffy_amd.stage(fixed_pipe)], buf, nbytes)
             else:
                 info = eng.tile_plan(buf, nbytes) if a.cmd == "tile" else eng.plan([st or paffy_amd.stage(kinds[a.cmd])], buf, nbytes)
         out = eng.alloc_out(info.out_bytes)
@@ -206,7 +210,7 @@ def main():
         eng.emit(out)
         eng.sync()
     prof = {k: round(v[0] / max(1, v[1]), 3) for k, v in eng.profile_read().items()}
-    extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx") or view else {}
+    extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx", "trimf") or fixed_pipe or view else {}
     if view:
         extra["sums"] = list(sums)
     if rows_cmd:
