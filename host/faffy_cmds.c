@@ -1,6 +1,6 @@
 /*
  * faffy_cmds.c -- `faffy chunk | extract | merge` over the C-ABI. Each command reads its whole input into host memory, copies the
- * FASTA text to the device, indexes it (paffy_hip_fasta_index), plans its items on the host, emits them on the device and writes the
+ * FASTA text to the device, indexes it (paffy_hip_fasta_index), plans its items (chunk, merge: on the host; extract: on the device, from the BED text), emits them on the device and writes the
  * bytes. Nothing is written when the plan or the base check fails: the process ends as the reference's would (status 1 for a missing
  * sequence, SIGABRT -- status 134 -- for its asserts). Files that cannot be opened give "faffy <cmd>: cannot open <path>", status 1
  * (the reference crashes instead).

@@ -665,12 +665,18 @@ int paffy_hip_fasta_seen(paffy_hip_ctx *ctx, const void *d_paf, int64_t paf_len,
  * record (chunk, merge), the BED line (extract: missing name, short line) or the sorted interval (extract bounds)).
  * chunk: PAFFY_E_ARG where chunk_size > overlap but chunk_size <= 0 or chunk_size + overlap < 0 (the reference loops forever / takes
  * negative lengths); the output files are byte ranges of the output, paffy_hip_faffy_chunk_files gives their ends.
- * extract: bed is host text; duplicate FASTA names: the last record wins.
+ * extract: duplicate FASTA names: the last record wins. The plan runs on the device: lines, tokens, atol, the name lookup, the sort by
+ * (name, start, end) and the merge of overlapping intervals. paffy_hip_faffy_extract_plan_device takes the BED text in device memory
+ * (16-byte aligned, readable to the next multiple of 16; a misaligned or NULL pointer with bed_len > 0: PAFFY_E_ARG) and keeps nothing
+ * of it: d_bed may be freed on return. paffy_hip_faffy_extract_plan takes host text and is one copy to the device plus that call.
+ * bed_len == 0: an empty plan. More than 2^31 - 1 lines: PAFFY_E_UNSUPPORTED.
  */
 int paffy_hip_faffy_chunk_plan(paffy_hip_ctx *ctx, int64_t chunk_size, int64_t overlap, paffy_plan_info *info);
 int64_t paffy_hip_faffy_chunk_files(paffy_hip_ctx *ctx, int64_t cap, int64_t *file_end);
 int paffy_hip_faffy_extract_plan(paffy_hip_ctx *ctx, const char *bed, int64_t bed_len, int64_t flank, int64_t min_size, int skip_missing,
                                  paffy_plan_info *info);
+int paffy_hip_faffy_extract_plan_device(paffy_hip_ctx *ctx, const void *d_bed, int64_t bed_len, int64_t flank, int64_t min_size, int skip_missing,
+                                        paffy_plan_info *info);
 int paffy_hip_faffy_merge_plan(paffy_hip_ctx *ctx, paffy_plan_info *info);
 /* the planned bytes to d_out (16-byte aligned, out_cap >= out_bytes rounded up to 16); err->code = PAFFY_ERR_FAFFY_BASE, err->record =
    the first item with a bad base (chunk, extract): the output is then not to be written */

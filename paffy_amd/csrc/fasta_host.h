@@ -1,6 +1,7 @@
 /*
  * fasta_host.h -- host side of `faffy chunk | extract | merge` (include/paffy_hip.h): the device FASTA index of
- * fasta_kernel.h, the item plans of the three commands (small host logic over the record table) and the emit.
+ * fasta_kernel.h, the item plans of chunk and merge (small host logic over the record table), the device plan of extract
+ * (fasta_extract_kernel.h) and the emit.
  * Included by paffy_hip.hip behind the context.
  */
 #pragma once
@@ -8,10 +9,16 @@
 #include <climits>
 #include <map>
 
+#include "fasta_extract_kernel.h"
+
 struct FastaState {
     struct Dev { /* all of the state's device memory: fasta_release lets it go while the state lives */
         DevBuf starts, tiles, totals, recs, bases, hdr_off, hdr_blob, items, bad;
-        DevBuf seen_names, seen_off, seen; /* paffy_hip_fasta_seen (seqload_host.h): the distinct names and a flag per name */
+        DevBuf seen_names, seen_off, seen; /* the distinct names (fa_name_table) and paffy_hip_fasta_seen's flag per name */
+        DevBuf name_rec;                   /* per distinct name: the record a BED line of that name means */
+        /* the extract plan (fasta_extract_kernel.h): the host form's copy of the BED text, per slice, per line, per kept interval */
+        DevBuf bed, bed_count, bed_first, bed_iv, bed_sorted, bed_keep, bed_pos, bed_lo, bed_hi, bed_rank, bed_clo, bed_chi, bed_max, bed_run, bed_scan,
+            bed_stat, bed_tmp;
     } dev;
     const uint8_t *text = nullptr; /* the caller's text: emit reads the header names from it */
     int64_t text_len = 0, n_rec = 0, n_bases = 0;
@@ -20,12 +27,19 @@ struct FastaState {
     std::vector<FaRec> h_recs;
     std::vector<char> h_hdr;       /* all headers back to back */
     std::vector<int64_t> h_hdr_at; /* record r's header is h_hdr[h_hdr_at[r] .. h_hdr_at[r + 1]) */
-    std::vector<FaItem> h_items;
+    std::vector<FaItem> h_items;   /* chunk, merge: the items as the host plans them (extract writes dev.items itself) */
+    int64_t n_items = 0;           /* items of the plan in dev.items */
+    bool names_ready = false;      /* fa_name_table has run for this index */
+    int32_t n_names = 0;
+    std::vector<int64_t> name_of;  /* record r's name in the table */
     std::vector<int64_t> file_ends; /* chunk: end of each output file in the output */
     int64_t out_bytes = 0;
 };
 
-static void fasta_release(FastaState &F) { F.dev = FastaState::Dev(); }
+static void fasta_release(FastaState &F) {
+    F.dev = FastaState::Dev();
+    F.names_ready = false;
+}
 
 static FastaState &fasta_state(paffy_hip_ctx *c) {
     if (!c->fasta) c->fasta.reset(new FastaState());
@@ -65,6 +79,7 @@ static int fa_plan_begin(paffy_hip_ctx *c, paffy_plan_info *info) {
     memset(info, 0, sizeof(*info));
     F.planned = false;
     F.h_items.clear();
+    F.n_items = 0;
     F.file_ends.clear();
     F.out_bytes = 0;
     return 0;
@@ -79,7 +94,8 @@ static int fa_plan_end(paffy_hip_ctx *c, paffy_plan_info *info) {
         F.file_ends.clear();
         F.out_bytes = 0;
     }
-    info->n_rows = (int64_t)F.h_items.size();
+    F.n_items = (int64_t)F.h_items.size();
+    info->n_rows = F.n_items;
     info->out_bytes = F.out_bytes;
     if (!F.h_items.empty()) {
         if (ensure(c, F.dev.items, sizeof(FaItem) * F.h_items.size())) return PAFFY_E_HIP;
@@ -100,7 +116,7 @@ static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t
     if (starts[0] != 0) return PAFFY_E_ARG;
     for (size_t k = 1; k < starts.size(); k++)
         if (starts[k] < starts[k - 1] || starts[k] > text_len) return PAFFY_E_ARG;
-    F.indexed = F.planned = false;
+    F.indexed = F.planned = F.names_ready = false;
     F.with_bases = with_bases;
     F.text = static_cast<const uint8_t *>(d_text);
     F.text_len = text_len;
@@ -151,6 +167,212 @@ static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t
         if (c->profile) prof_collect(c);
     }
     F.indexed = true;
+    return 0;
+}
+
+/* record r's header as host/paffy_cmds.c's former fasta_read keyed it: a C string, so up to its first NUL byte */
+static std::string fa_key(const FastaState &F, int64_t r) {
+    const char *h = F.h_hdr.data() + F.h_hdr_at[r];
+    return std::string(h, strnlen(h, (size_t)(F.h_hdr_at[r + 1] - F.h_hdr_at[r])));
+}
+
+/*
+ * The table of the index's distinct names, once per index: dev.seen_names / dev.seen_off hold them sorted as find_seq expects (bytes,
+ * then the shorter first), so a name's index is its strcmp rank; F.name_of[r] is record r's name. dev.name_rec[k] is the record a BED
+ * line named k means: the last record whose whole header is that name (a header with a NUL byte is keyed up to it for to_bed -q, but
+ * no BED token equals it), -1 where there is none. The sort is per FASTA record and stays on the host.
+ */
+static int fa_name_table(paffy_hip_ctx *c, FastaState &F) {
+    if (F.names_ready) return 0;
+    const int64_t n = F.n_rec;
+    if (n >= (1ll << 31) - 1) {
+        c->last_error = "the FASTA index has more than 2^31 - 2 records: no name table";
+        return PAFFY_E_UNSUPPORTED;
+    }
+    std::vector<std::string> key((size_t)n);
+    std::vector<int64_t> order((size_t)n);
+    F.name_of.assign((size_t)n, 0);
+    for (int64_t r = 0; r < n; r++) {
+        key[(size_t)r] = fa_key(F, r);
+        order[(size_t)r] = r;
+    }
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        const std::string &x = key[(size_t)a], &y = key[(size_t)b];
+        const int d = memcmp(x.data(), y.data(), x.size() < y.size() ? x.size() : y.size());
+        if (d) return d < 0;
+        if (x.size() != y.size()) return x.size() < y.size();
+        return a < b; /* records of one name in input order: the last one is the last written below */
+    });
+    std::string blob;
+    std::vector<uint32_t> name_off;
+    std::vector<int64_t> name_rec;
+    for (int64_t k = 0; k < n; k++) {
+        const int64_t r = order[(size_t)k];
+        if (k == 0 || key[(size_t)r] != key[(size_t)order[(size_t)k - 1]]) {
+            name_off.push_back((uint32_t)blob.size());
+            name_rec.push_back(-1);
+            blob += key[(size_t)r];
+            if (blob.size() >= 0xffffffffull) {
+                c->last_error = "the FASTA names pass 4 GiB";
+                return PAFFY_E_ARG;
+            }
+        }
+        F.name_of[(size_t)r] = (int64_t)name_off.size() - 1;
+        if ((int64_t)key[(size_t)r].size() == F.h_hdr_at[r + 1] - F.h_hdr_at[r]) name_rec.back() = r;
+    }
+    F.n_names = (int32_t)name_off.size();
+    name_off.push_back((uint32_t)blob.size());
+    if (ensure(c, F.dev.seen_names, blob.size() + 16) || ensure(c, F.dev.seen_off, sizeof(uint32_t) * name_off.size()) ||
+        ensure(c, F.dev.name_rec, sizeof(int64_t) * (name_rec.size() + 1)))
+        return PAFFY_E_HIP;
+    if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(F.dev.seen_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(F.dev.seen_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, c->stream));
+    if (!name_rec.empty()) HIPCHK(c, hipMemcpyAsync(F.dev.name_rec.p, name_rec.data(), sizeof(int64_t) * name_rec.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* the copies read this frame's vectors */
+    F.names_ready = true;
+    return 0;
+}
+
+template <typename T, typename Op>
+static int fa_inclusive_scan(paffy_hip_ctx *c, FastaState &F, const T *in, T *out, size_t n, Op op) {
+    size_t bytes = 0;
+    RPCHK(c, rocprim::inclusive_scan(nullptr, bytes, in, out, n, op, c->stream));
+    if (ensure(c, F.dev.bed_tmp, bytes + 16)) return PAFFY_E_HIP;
+    RPCHK(c, rocprim::inclusive_scan(F.dev.bed_tmp.p, bytes, in, out, n, op, c->stream));
+    return 0;
+}
+template <typename T>
+static int fa_exclusive_sum(paffy_hip_ctx *c, FastaState &F, const T *in, T *out, size_t n) {
+    size_t bytes = 0;
+    RPCHK(c, rocprim::exclusive_scan(nullptr, bytes, in, out, (T)0, n, rocprim::plus<T>(), c->stream));
+    if (ensure(c, F.dev.bed_tmp, bytes + 16)) return PAFFY_E_HIP;
+    RPCHK(c, rocprim::exclusive_scan(F.dev.bed_tmp.p, bytes, in, out, (T)0, n, rocprim::plus<T>(), c->stream));
+    return 0;
+}
+static int fa_fetch(paffy_hip_ctx *c, void *dst, const void *src, size_t bytes) {
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+/*
+ * The extract plan over BED text in device memory (fasta_extract_kernel.h): line index, parse, sort, bounds, merge by prefix maximum,
+ * items. The host sees four numbers on the way: the lines, the first failing line or interval, the kept intervals, the items with
+ * their bytes. info->error is set as the reference fails; F.n_items / F.out_bytes and dev.items hold the plan.
+ */
+static int fa_extract_plan(paffy_hip_ctx *c, FastaState &F, const uint8_t *bed, int64_t bed_len, int64_t flank, int64_t min_size, int skip_missing,
+                           paffy_plan_info *info) {
+    if (bed_len == 0) return 0;
+    int rc = fa_name_table(c, F);
+    if (rc) return rc;
+    FastaState::Dev &D = F.dev;
+    const dim3 block(FA_NT);
+    auto grid_of = [](int64_t n) { return dim3((unsigned)((n + FA_NT - 1) / FA_NT)); };
+    const uint8_t *names = static_cast<const uint8_t *>(D.seen_names.p);
+    const uint32_t *name_off = static_cast<const uint32_t *>(D.seen_off.p);
+    const int64_t *name_rec = static_cast<const int64_t *>(D.name_rec.p);
+    const FaRec *recs = static_cast<const FaRec *>(D.recs.p);
+
+    /* 1. lines */
+    const int64_t n_slices = (bed_len + FA_PER - 1) / FA_PER;
+    if (n_slices + FA_NT > (int64_t)0xffffffffll * FA_NT / 2) { /* the grid */
+        c->last_error = "faffy extract: a BED text of this size is not supported";
+        return PAFFY_E_UNSUPPORTED;
+    }
+    if (ensure(c, D.bed_count, sizeof(int64_t) * (size_t)(n_slices + 1)) || ensure(c, D.bed_first, sizeof(int64_t) * (size_t)(n_slices + 1)) ||
+        ensure(c, D.bed_stat, sizeof(BedStat)))
+        return PAFFY_E_HIP;
+    int64_t *count = static_cast<int64_t *>(D.bed_count.p), *first = static_cast<int64_t *>(D.bed_first.p);
+    BedStat *stat = static_cast<BedStat *>(D.bed_stat.p);
+    HIPCHK(c, hipMemsetAsync(count + n_slices, 0, sizeof(int64_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(stat, 0xff, sizeof(BedStat), c->stream));
+    LAUNCH(c, "k_bed_index", k_bed_index, grid_of(n_slices), block, 0, bed, bed_len, count);
+    if (fa_exclusive_sum(c, F, static_cast<const int64_t *>(count), first, (size_t)n_slices + 1)) return PAFFY_E_HIP;
+    int64_t n = 0;
+    if (fa_fetch(c, &n, first + n_slices, sizeof(n))) return PAFFY_E_HIP;
+    if (n > (int64_t)INT32_MAX) {
+        c->last_error = "faffy extract: more than 2^31 - 1 BED lines";
+        return PAFFY_E_UNSUPPORTED;
+    }
+
+    /* 2. parse, 3. sort */
+    if (ensure(c, D.bed_iv, sizeof(BedIv) * (size_t)n) || ensure(c, D.bed_sorted, sizeof(BedIv) * (size_t)n)) return PAFFY_E_HIP;
+    BedIv *iv = static_cast<BedIv *>(D.bed_iv.p), *sorted = static_cast<BedIv *>(D.bed_sorted.p);
+    LAUNCH(c, "k_bed_parse", k_bed_parse, grid_of(n_slices), block, 0, bed, bed_len, static_cast<const int64_t *>(first), names, name_off, name_rec, F.n_names,
+           skip_missing ? 1 : 0, iv, stat);
+    {
+        size_t bytes = 0;
+        RPCHK(c, rocprim::merge_sort(nullptr, bytes, iv, sorted, (size_t)n, BedIvLess(), c->stream));
+        if (ensure(c, D.bed_tmp, bytes + 16)) return PAFFY_E_HIP;
+        RPCHK(c, rocprim::merge_sort(D.bed_tmp.p, bytes, iv, sorted, (size_t)n, BedIvLess(), c->stream));
+    }
+
+    /* 4. bounds, the kept intervals side by side */
+    if (ensure(c, D.bed_keep, sizeof(uint32_t) * (size_t)(n + 1)) || ensure(c, D.bed_pos, sizeof(uint32_t) * (size_t)(n + 1)) ||
+        ensure(c, D.bed_lo, sizeof(int64_t) * (size_t)n) || ensure(c, D.bed_hi, sizeof(int64_t) * (size_t)n))
+        return PAFFY_E_HIP;
+    uint32_t *keep = static_cast<uint32_t *>(D.bed_keep.p), *pos = static_cast<uint32_t *>(D.bed_pos.p);
+    int64_t *lo = static_cast<int64_t *>(D.bed_lo.p), *hi = static_cast<int64_t *>(D.bed_hi.p);
+    LAUNCH(c, "k_bed_bounds", k_bed_bounds, grid_of(n + 1), block, 0, static_cast<const BedIv *>(sorted), n, name_rec, recs, F.n_names, flank, min_size, keep,
+           lo, hi, stat);
+    if (fa_exclusive_sum(c, F, static_cast<const uint32_t *>(keep), pos, (size_t)n + 1)) return PAFFY_E_HIP;
+    BedStat h_stat;
+    uint32_t m = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, c->stream));
+    if (fa_fetch(c, &m, pos + n, sizeof(m))) return PAFFY_E_HIP;
+    if (h_stat.parse_err != ~0ull) { /* the first failing line decides, whichever kind it is */
+        fa_fail(info, (h_stat.parse_err & 1ull) == BED_KIND_MISSING ? PAFFY_ERR_FAFFY_MISSING_SEQ : PAFFY_ERR_FAFFY_ASSERT, (int64_t)(h_stat.parse_err >> 1));
+        return 0;
+    }
+    if (h_stat.bounds_err != ~0ull) {
+        fa_fail(info, PAFFY_ERR_FAFFY_ASSERT, (int64_t)h_stat.bounds_err);
+        return 0;
+    }
+    if (m == 0) return 0;
+    if (ensure(c, D.bed_rank, sizeof(uint32_t) * (size_t)m) || ensure(c, D.bed_clo, sizeof(int64_t) * (size_t)m) || ensure(c, D.bed_chi, sizeof(int64_t) * (size_t)m) ||
+        ensure(c, D.bed_max, sizeof(int64_t) * (size_t)m) || ensure(c, D.bed_run, sizeof(BedRun) * (size_t)m) || ensure(c, D.bed_scan, sizeof(BedRun) * (size_t)m))
+        return PAFFY_E_HIP;
+    uint32_t *c_rank = static_cast<uint32_t *>(D.bed_rank.p);
+    int64_t *c_lo = static_cast<int64_t *>(D.bed_clo.p), *c_hi = static_cast<int64_t *>(D.bed_chi.p), *c_max = static_cast<int64_t *>(D.bed_max.p);
+    BedRun *run = static_cast<BedRun *>(D.bed_run.p), *scan = static_cast<BedRun *>(D.bed_scan.p);
+    LAUNCH(c, "k_bed_compact", k_bed_compact, grid_of(n), block, 0, static_cast<const BedIv *>(sorted), n, static_cast<const uint32_t *>(keep),
+           static_cast<const uint32_t *>(pos), static_cast<const int64_t *>(lo), static_cast<const int64_t *>(hi), c_rank, c_lo, c_hi);
+
+    /* 5. the merge: prefix maximum of the ends by name, then items, bytes and item starts in one scan */
+    {
+        size_t bytes = 0;
+        const uint32_t *kin = c_rank;
+        const int64_t *vin = c_hi;
+        RPCHK(c, rocprim::inclusive_scan_by_key(nullptr, bytes, kin, vin, c_max, (size_t)m, BedMax64(), rocprim::equal_to<uint32_t>(), c->stream));
+        if (ensure(c, D.bed_tmp, bytes + 16)) return PAFFY_E_HIP;
+        RPCHK(c, rocprim::inclusive_scan_by_key(D.bed_tmp.p, bytes, kin, vin, c_max, (size_t)m, BedMax64(), rocprim::equal_to<uint32_t>(), c->stream));
+    }
+    LAUNCH(c, "k_bed_heads", k_bed_heads, grid_of(m), block, 0, static_cast<const uint32_t *>(c_rank), static_cast<const int64_t *>(c_lo),
+           static_cast<const int64_t *>(c_max), (int64_t)m, name_rec, recs, run);
+    if (fa_inclusive_scan(c, F, static_cast<const BedRun *>(run), scan, (size_t)m, BedRunPlus())) return PAFFY_E_HIP;
+    BedRun total;
+    if (fa_fetch(c, &total, scan + (m - 1), sizeof(total))) return PAFFY_E_HIP;
+
+    /* 6. items */
+    if (ensure(c, D.items, sizeof(FaItem) * (size_t)total.items)) return PAFFY_E_HIP;
+    LAUNCH(c, "k_bed_items", k_bed_items, grid_of(m), block, 0, static_cast<const uint32_t *>(c_rank), static_cast<const int64_t *>(c_lo),
+           static_cast<const int64_t *>(c_max), (int64_t)m, name_rec, recs, static_cast<const BedRun *>(scan), static_cast<FaItem *>(D.items.p));
+    F.n_items = (int64_t)total.items;
+    F.out_bytes = total.bytes;
+    return 0;
+}
+
+/* the end of a plan whose items are in dev.items already */
+static int fa_plan_end_device(paffy_hip_ctx *c, paffy_plan_info *info) {
+    FastaState &F = *c->fasta;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* the caller may free the BED text */
+    if (c->profile) prof_collect(c);
+    info->n_records = F.n_rec;
+    info->in_bytes = F.text_len;
+    if (info->error.code) F.n_items = F.out_bytes = 0; /* nothing is written after an error of the plan */
+    info->n_rows = F.n_items;
+    info->out_bytes = F.out_bytes;
+    F.planned = true;
     return 0;
 }
 
@@ -228,77 +450,27 @@ int64_t paffy_hip_faffy_chunk_files(paffy_hip_ctx *c, int64_t cap, int64_t *file
     return (int64_t)F.file_ends.size();
 }
 
+int paffy_hip_faffy_extract_plan_device(paffy_hip_ctx *c, const void *d_bed, int64_t bed_len, int64_t flank, int64_t min_size, int skip_missing,
+                                        paffy_plan_info *info) {
+    int rc = fa_plan_begin(c, info);
+    if (rc) return rc;
+    if (bed_len < 0 || (bed_len > 0 && (!d_bed || (reinterpret_cast<uintptr_t>(d_bed) & 15u)))) return PAFFY_E_ARG;
+    rc = fa_extract_plan(c, *c->fasta, static_cast<const uint8_t *>(d_bed), bed_len, flank, min_size, skip_missing, info);
+    if (rc) return rc;
+    return fa_plan_end_device(c, info);
+}
+
+/* host text: one copy to the device, then the plan above */
 int paffy_hip_faffy_extract_plan(paffy_hip_ctx *c, const char *bed, int64_t bed_len, int64_t flank, int64_t min_size, int skip_missing, paffy_plan_info *info) {
     int rc = fa_plan_begin(c, info);
     if (rc) return rc;
     if (bed_len < 0 || (bed_len > 0 && !bed)) return PAFFY_E_ARG;
     FastaState &F = *c->fasta;
-    std::unordered_map<std::string, int64_t> by_name; /* duplicate names: the last record wins */
-    by_name.reserve((size_t)F.n_rec * 2);
-    for (int64_t r = 0; r < F.n_rec; r++) by_name[fa_header(F, r)] = r;
-    struct Iv {
-        const std::string *name;
-        int64_t rec, start, end;
-    };
-    std::vector<Iv> ivs;
-    /* BED lines (stFile_getLineFromFile): split on white space, atol of tokens 1 and 2 */
-    int64_t line_no = 0;
-    for (int64_t p = 0; p < bed_len; line_no++) {
-        int64_t e = p;
-        while (e < bed_len && bed[e] != '\n') e++;
-        std::string tok[3];
-        int nt = 0;
-        for (int64_t q = p; q < e && nt < 3;) {
-            while (q < e && isspace((unsigned char)bed[q])) q++;
-            if (q >= e) break;
-            int64_t t = q;
-            while (t < e && !isspace((unsigned char)bed[t])) t++;
-            tok[nt++].assign(bed + q, (size_t)(t - q));
-            q = t;
-        }
-        p = e + 1;
-        if (nt < 3) { /* stList_get past the end of the tokens: an assert */
-            fa_fail(info, PAFFY_ERR_FAFFY_ASSERT, line_no);
-            return fa_plan_end(c, info);
-        }
-        auto it = by_name.find(tok[0]);
-        if (it == by_name.end()) {
-            if (skip_missing) continue;
-            fa_fail(info, PAFFY_ERR_FAFFY_MISSING_SEQ, line_no);
-            return fa_plan_end(c, info);
-        }
-        ivs.push_back(Iv{&it->first, it->second, (int64_t)atol(tok[1].c_str()), (int64_t)atol(tok[2].c_str())});
+    if (bed_len > 0) {
+        if (ensure(c, F.dev.bed, (size_t)bed_len + 16)) return PAFFY_E_HIP;
+        HIPCHK(c, hipMemcpyAsync(F.dev.bed.p, bed, (size_t)bed_len, hipMemcpyHostToDevice, c->stream));
     }
-    std::sort(ivs.begin(), ivs.end(), [](const Iv &a, const Iv &b) {
-        const int k = strcmp(a.name->c_str(), b.name->c_str());
-        if (k) return k < 0;
-        if (a.start != b.start) return a.start < b.start;
-        return a.end < b.end;
-    });
-    int64_t p_rec = -1, p_start = -1, p_end = -1;
-    for (size_t k = 0; k < ivs.size(); k++) {
-        const Iv &iv = ivs[k];
-        if ((int64_t)((uint64_t)iv.end - (uint64_t)iv.start) < min_size) continue; /* int64 arithmetic as the reference's (wrapping) */
-        const int64_t len = F.h_recs[iv.rec].seq_len;
-        const int64_t sf = (int64_t)((uint64_t)iv.start - (uint64_t)flank), ef = (int64_t)((uint64_t)iv.end + (uint64_t)flank);
-        const int64_t i = sf > 0 ? sf : 0, j = ef <= len ? ef : len;
-        if (!(0 <= i && i <= iv.start && iv.start <= iv.end && iv.end <= j && j <= len)) { /* impl/fasta_extract.c:211 */
-            fa_fail(info, PAFFY_ERR_FAFFY_ASSERT, (int64_t)k);
-            return fa_plan_end(c, info);
-        }
-        if (p_rec >= 0) {
-            if (p_rec == iv.rec && p_end >= i) {
-                p_end = p_end > j ? p_end : j;
-                continue;
-            }
-            fa_push(F, p_rec, 0, (int32_t)F.h_recs[p_rec].hdr_len, F.h_recs[p_rec].seq_len, p_start, p_start, p_end, true);
-        }
-        p_rec = iv.rec;
-        p_start = i;
-        p_end = j;
-    }
-    if (p_rec >= 0) fa_push(F, p_rec, 0, (int32_t)F.h_recs[p_rec].hdr_len, F.h_recs[p_rec].seq_len, p_start, p_start, p_end, true);
-    return fa_plan_end(c, info);
+    return paffy_hip_faffy_extract_plan_device(c, F.dev.bed.p, bed_len, flank, min_size, skip_missing, info);
 }
 
 int paffy_hip_faffy_merge_plan(paffy_hip_ctx *c, paffy_plan_info *info) {
@@ -366,7 +538,7 @@ int paffy_hip_faffy_emit(paffy_hip_ctx *c, void *d_out, int64_t out_cap, paffy_e
     HIPCHK(c, hipMemsetAsync(F.dev.bad.p, 0xff, sizeof(unsigned long long), c->stream));
     const int64_t n_win = (F.out_bytes + FA_WIN - 1) / FA_WIN;
     LAUNCH(c, "k_fa_emit", k_fa_emit, dim3((unsigned)((n_win + FA_EMIT_WAVES - 1) / FA_EMIT_WAVES)), dim3(64 * FA_EMIT_WAVES), 0,
-           static_cast<const FaItem *>(F.dev.items.p), (int64_t)F.h_items.size(), F.text, static_cast<const uint8_t *>(F.dev.bases.p),
+           static_cast<const FaItem *>(F.dev.items.p), F.n_items, F.text, static_cast<const uint8_t *>(F.dev.bases.p),
            static_cast<uint8_t *>(d_out), F.out_bytes, static_cast<unsigned long long *>(F.dev.bad.p));
     unsigned long long bad = ~0ull;
     HIPCHK(c, hipMemcpyAsync(&bad, F.dev.bad.p, sizeof(bad), hipMemcpyDeviceToHost, c->stream));

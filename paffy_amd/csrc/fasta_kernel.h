@@ -39,7 +39,7 @@ struct FaRec {
     int64_t hdr_off, hdr_len, seq_off, seq_len;
 };
 
-/* one item of the output (host plan, fasta_host.h) */
+/* one item of the output (chunk, merge: planned on the host, fasta_host.h; extract: written by k_bed_items, fasta_extract_kernel.h) */
 struct FaItem {
     int64_t out_off;          /* first output byte */
     int64_t name_off;         /* header name: a slice of the text */

@@ -5,12 +5,6 @@
  */
 #pragma once
 
-/* record r's header as host/paffy_cmds.c's former fasta_read keyed it: a C string, so up to its first NUL byte */
-static std::string fa_key(const FastaState &F, int64_t r) {
-    const char *h = F.h_hdr.data() + F.h_hdr_at[r];
-    return std::string(h, strnlen(h, (size_t)(F.h_hdr_at[r + 1] - F.h_hdr_at[r])));
-}
-
 /* seq_blob holds the bases (input order) from n_bases on: upper case, complement and the raw copy in one pass */
 static int seq_store_fill(paffy_hip_ctx *c, int64_t n_bases) {
     uint64_t n16 = ((uint64_t)n_bases + 64 + 15) / 16; /* the bases and the 64 bytes past them that seq_store_layout keeps too */
@@ -102,40 +96,15 @@ int paffy_hip_fasta_seen(paffy_hip_ctx *c, const void *d_paf, int64_t paf_len, i
     const int64_t n = F.n_rec;
     if (n == 0) return 0;
     if (!seen) return PAFFY_E_ARG;
-    /* the distinct names, sorted as find_seq expects (bytes, then the shorter first); uid[r] = record r's name */
-    std::vector<std::string> key((size_t)n);
-    std::vector<int64_t> order((size_t)n), uid((size_t)n);
-    for (int64_t r = 0; r < n; r++) {
-        key[(size_t)r] = fa_key(F, r);
-        order[(size_t)r] = r;
+    /* the distinct names, sorted as find_seq expects: the index's name table (fasta_host.h), built once per index */
+    {
+        const int rc = fa_name_table(c, F);
+        if (rc) return rc;
     }
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        const std::string &x = key[(size_t)a], &y = key[(size_t)b];
-        const int d = memcmp(x.data(), y.data(), x.size() < y.size() ? x.size() : y.size());
-        return d ? d < 0 : x.size() < y.size();
-    });
-    std::string blob;
-    std::vector<uint32_t> name_off;
-    for (int64_t k = 0; k < n; k++) {
-        const int64_t r = order[(size_t)k];
-        if (k == 0 || key[(size_t)r] != key[(size_t)order[(size_t)k - 1]]) {
-            name_off.push_back((uint32_t)blob.size());
-            blob += key[(size_t)r];
-            if (blob.size() >= 0xffffffffull) {
-                c->last_error = "fasta_seen: the names pass 4 GiB";
-                return PAFFY_E_ARG;
-            }
-        }
-        uid[(size_t)r] = (int64_t)name_off.size() - 1;
-    }
-    const int32_t n_names = (int32_t)name_off.size();
-    name_off.push_back((uint32_t)blob.size());
+    const int32_t n_names = F.n_names;
     std::vector<uint8_t> flag((size_t)n_names, 0);
     if (paf_len > 0) {
-        if (ensure(c, F.dev.seen_names, blob.size() + 16) || ensure(c, F.dev.seen_off, sizeof(uint32_t) * name_off.size()) || ensure(c, F.dev.seen, (size_t)n_names))
-            return PAFFY_E_HIP;
-        if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(F.dev.seen_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(F.dev.seen_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, c->stream));
+        if (ensure(c, F.dev.seen, (size_t)n_names)) return PAFFY_E_HIP;
         HIPCHK(c, hipMemsetAsync(F.dev.seen.p, 0, (size_t)n_names, c->stream));
         const int64_t blocks = (paf_len + FA_TILE - 1) / FA_TILE;
         LAUNCH(c, "k_fa_seen", k_fa_seen, dim3((unsigned)blocks), dim3(FA_NT), 0, static_cast<const uint8_t *>(d_paf), paf_len, with_target ? 1 : 0,
@@ -144,7 +113,7 @@ int paffy_hip_fasta_seen(paffy_hip_ctx *c, const void *d_paf, int64_t paf_len, i
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->profile) prof_collect(c);
     }
-    for (int64_t r = 0; r < n; r++) seen[r] = flag[(size_t)uid[(size_t)r]];
+    for (int64_t r = 0; r < n; r++) seen[r] = flag[(size_t)F.name_of[(size_t)r]];
     return 0;
 }
 

@@ -213,6 +213,8 @@ def lib():
         L.paffy_hip_faffy_chunk_files.restype = i64
         L.paffy_hip_faffy_chunk_files.argtypes = [vp, i64, C.POINTER(i64)]
         L.paffy_hip_faffy_extract_plan.argtypes = [vp, C.c_char_p, i64, i64, i64, C.c_int, C.POINTER(PlanInfo)]
+        if hasattr(L, "paffy_hip_faffy_extract_plan_device"):  # an older library under PAFFY_HIP_LIB has none: the call then raises
+            L.paffy_hip_faffy_extract_plan_device.argtypes = [vp, vp, i64, i64, i64, C.c_int, C.POINTER(PlanInfo)]
         L.paffy_hip_faffy_merge_plan.argtypes = [vp, C.POINTER(PlanInfo)]
         L.paffy_hip_faffy_emit.argtypes = [vp, vp, i64, C.POINTER(_Error)]
         L.paffy_hip_set_sequences_fasta.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64)]
@@ -1215,6 +1217,22 @@ class Engine:
         info = PlanInfo()
         self._check(lib().paffy_hip_faffy_extract_plan(self._ctx, bed, len(bed), flank, min_size, 1 if skip_missing else 0, C.byref(info)),
                     "paffy_hip_faffy_extract_plan")
+        out = self._faffy_emit(info)
+        del d_text
+        return out
+
+    def faffy_extract_device(self, files, d_bed, bed_len=None, flank=10, min_size=100, skip_missing=False):
+        """faffy_extract with the BED text in device memory: d_bed is a uint8 device tensor (for example the buffer a to_bed run emitted
+        into), bed_len the bytes of it that are text (default: all). Its allocation must be readable up to the next multiple of 16
+        past bed_len, as to_device's and alloc_out's are. The plan keeps nothing of d_bed."""
+        bed_len = d_bed.numel() if bed_len is None else int(bed_len)
+        if bed_len < 0 or bed_len > d_bed.numel():
+            raise ValueError(f"bed_len {bed_len} outside the tensor of {d_bed.numel()} bytes")
+        d_text = self._files(files)
+        info = PlanInfo()
+        ptr = C.c_void_p(d_bed.data_ptr() if bed_len else None)
+        self._check(lib().paffy_hip_faffy_extract_plan_device(self._ctx, ptr, bed_len, flank, min_size, 1 if skip_missing else 0, C.byref(info)),
+                    "paffy_hip_faffy_extract_plan_device")
         out = self._faffy_emit(info)
         del d_text
         return out

@@ -48,6 +48,7 @@ def main():
                          "then have a first row piece of 15 bytes, chr10-chr24 one of 16 -- about half and half, like a human assembly")
     ap.add_argument("--genome-gb", type=float, default=3.1, help="faffy_*: bases of the synthetic genome (24 contigs)")
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
+    ap.add_argument("--sha256", action="store_true", help="faffy_*: copy the last repetition's output to the host and print its SHA-256")
     ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome")
     ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the plan (the smallest counts)")
     ap.add_argument("--sha", action="store_true", help="add_trim, add_filter: copy the last repetition's output to the host and print its SHA-256")
@@ -323,7 +324,8 @@ def synth_genome(torch, dev, gb, n_contigs=24, seed=0x5EED00FA):
 
 def faffy_bench(a):
     """faffy chunk / extract / merge with the text resident in HBM: index + plan + emit per repetition, kernel times by HIP events.
-    The CLI itself is bound by its disk reads and writes; these figures are the device part."""
+    seconds_plan is a host clock round the plan call alone, which ends in a synchronise (extract: the BED is host text, so the plan
+    includes its copy to the device). The CLI itself is bound by its disk reads and writes; these figures are the device part."""
     import ctypes as C
 
     import numpy as np
@@ -361,7 +363,7 @@ def faffy_bench(a):
         bed = b"".join(b"%s\t%d\t%d\n" % (contigs[x][0], s, s + z) for x, s, z in zip(k.tolist(), st.tolist(), size.tolist()))
     torch.cuda.synchronize()
     print(f"{a.cmd}: input of {nbytes / 1e9:.2f} GB resident in HBM ({time.perf_counter() - t0:.1f} s to generate)", file=sys.stderr)
-    res = []
+    res, plan = [], []
     out = None
     for rep in range(3):
         if rep == 1:
@@ -369,12 +371,14 @@ def faffy_bench(a):
         t0 = time.perf_counter()
         n_rec, n_bases = eng.fasta_index(text, nbytes, starts)
         info = E.PlanInfo()
+        t1 = time.perf_counter()  # the plan call alone: it ends in a synchronise
         if a.cmd == "faffy_chunk":
             rc = L.paffy_hip_faffy_chunk_plan(eng._ctx, 1000000, 10000, C.byref(info))
         elif a.cmd == "faffy_extract":
             rc = L.paffy_hip_faffy_extract_plan(eng._ctx, bed, len(bed), 10, 100, 1, C.byref(info))
         else:
             rc = L.paffy_hip_faffy_merge_plan(eng._ctx, C.byref(info))
+        plan.append(time.perf_counter() - t1)
         assert rc == 0 and info.error.code == 0, (rc, info.error.code)
         if out is None or out.numel() < info.out_bytes + 16:
             out = eng.alloc_out(info.out_bytes)
@@ -386,8 +390,18 @@ def faffy_bench(a):
     kernel_ms = {k: round(ms / max(1, cnt), 3) for k, (ms, cnt) in prof.items()}
     total_ms = sum(kernel_ms.values())
     moved = nbytes + int(info.out_bytes)
+    extra = {}
+    if a.sha256:
+        import hashlib
+
+        h = hashlib.sha256()
+        for at in range(0, int(info.out_bytes), 1 << 28):
+            h.update(out[at:min(at + (1 << 28), int(info.out_bytes))].cpu().numpy().tobytes())
+        extra["out_sha256"] = h.hexdigest()
     print(json.dumps({"cmd": a.cmd, "in_bytes": nbytes, "out_bytes": int(info.out_bytes), "records": n_rec, "bases": n_bases, "items": int(info.n_rows),
-                      "seconds_index_plan_emit": round(min(res[1:]), 4), "kernel_ms": kernel_ms, "kernel_ms_total": round(total_ms, 3),
+                      "seconds_index_plan_emit": round(min(res[1:]), 4), "seconds_plan": round(min(plan[1:]), 5),
+                      "seconds_index_plan_emit_all": [round(x, 4) for x in res], "seconds_plan_all": [round(x, 5) for x in plan], **extra,
+                      "kernel_ms": kernel_ms, "kernel_ms_total": round(total_ms, 3),
                       "GBps_text_in_out_over_kernel_time": round(moved / (total_ms / 1e3) / 1e9, 1),
                       "fraction_of_8TBps": round(moved / (total_ms / 1e3) / 8e12, 3)}))
     eng.close()
