@@ -85,6 +85,19 @@ def consistent_record(rng, qn, qlen, tn, tlen, n_ops, lens, alphabet="MID", stra
     return f"{qn}\t{qlen}\t{qs}\t{qs + q}\t{strand or rng.choice('+-')}\t{tn}\t{tlen}\t{ts}\t{ts + t}\t{q}\t{q}\t60\t" + "\t".join(tags + ["cg:Z:" + "".join(ops)]) + "\n"
 
 
+def odd_record(rng, qn, qlen, tn, tlen):
+    """now and then a record of tests/cov_edges_lib.py: digitless ops, numbers with leading zeros and of eight and more digits, cigars for
+    either shape of the bitmap kernel, a tag of 0 to 15 bytes in front of the cigar (it moves cg_off & 15); None when it does not fit"""
+    import cov_edges_lib
+
+    cg, q, t = cov_edges_lib.odd_cigar(rng)
+    if q >= qlen - 2 or t >= tlen - 2:
+        return None
+    qs, ts = rng.randrange(0, qlen - q), rng.randrange(0, tlen - t)
+    tags = [f"AS:i:{rng.choice([5, 5, 40, 900])}", "zz:Z:" + "x" * rng.randrange(16), "cg:Z:" + cg]
+    return f"{qn}\t{qlen}\t{qs}\t{qs + q}\t{rng.choice('+-')}\t{tn}\t{tlen}\t{ts}\t{ts + t}\t{q}\t{q}\t60\t" + "\t".join(tags) + "\n"
+
+
 def fuzz_tile(eng, rng, budget):
     t0, rounds = time.time(), 0
     while time.time() - t0 < budget:
@@ -92,7 +105,8 @@ def fuzz_tile(eng, rng, budget):
         recs = []
         for _ in range(rng.choice([1, 10, 200, 1500])):
             qn, qlen = rng.choice(contigs)
-            recs.append(consistent_record(rng, qn, qlen, "t", 4000000, rng.choice([1, 5, 60, 900]), rng.choice([[1, 3], [5, 50, 300], [1000, 20000]])))
+            odd = odd_record(rng, qn, qlen, "t", 4000000) if rng.random() < 0.1 else None
+            recs.append(odd or consistent_record(rng, qn, qlen, "t", 4000000, rng.choice([1, 5, 60, 900]), rng.choice([[1, 3], [5, 50, 300], [1000, 20000]])))
         data = "".join(recs).encode()
         want, werr = O.tile(data)
         got, info = eng.tile(data, raise_on_error=False)
@@ -114,7 +128,8 @@ def fuzz_bed(eng, rng, budget):
         for _ in range(rng.choice([1, 10, 200, 1200])):
             qn, qlen = rng.choice(contigs)
             tn, tlen = rng.choice(contigs) if rng.random() < 0.3 else ("t", 4000000)
-            recs.append(consistent_record(rng, qn, qlen, tn, tlen, rng.choice([1, 5, 60, 900]), rng.choice([[1, 3], [5, 50, 300], [1000, 20000]])))
+            odd = odd_record(rng, qn, qlen, tn, tlen) if rng.random() < 0.1 else None
+            recs.append(odd or consistent_record(rng, qn, qlen, tn, tlen, rng.choice([1, 5, 60, 900]), rng.choice([[1, 3], [5, 50, 300], [1000, 20000]])))
         if rng.random() < 0.1:  # a record that breaks an assert somewhere in the middle
             f = recs[len(recs) // 2].split("\t")
             f[3] = str(int(f[3]) + 1)
