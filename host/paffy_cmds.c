@@ -388,6 +388,10 @@ int paffy_tile_main(int argc, char *argv[]) {
  * impl/paf_chain.c:47-153: the records are chained per (query, target, strand) with the affine gap cost of :36-45; every record
  * gets the id (cn) and the score (s1) of its chain and the output is ordered by descending alignment score.
  */
+int host_chain_fresh_walk(void) {
+    const char *v = getenv("PAFFY_CHAIN_FRESH_WALK");
+    return v && atoi(v) != 0;
+}
 int paffy_chain_main(int argc, char *argv[]) {
     static struct option opts[] = {{"logLevel", required_argument, 0, 'l'}, {"inputFile", required_argument, 0, 'i'}, {"outputFile", required_argument, 0, 'o'},
                                    {"maxGapLength", required_argument, 0, 'g'}, {"trimFraction", required_argument, 0, 't'}, {"chainGapOpen", required_argument, 0, 'd'},
@@ -422,6 +426,7 @@ int paffy_chain_main(int argc, char *argv[]) {
     host_set_log_level(o.log_level);
     host_log_info("Input file string : %s\nOutput file string : %s\nMaximum gap length : %lld\nChain gap open : %lld\nChain gap extend : %lld\n", o.in_path, o.out_path,
                   (long long)c.max_gap_length, (long long)c.gap_open, (long long)c.gap_extend);
+    if (host_chain_fresh_walk()) host_log_info("PAFFY_CHAIN_FRESH_WALK: the walk from a fresh iterator is restated\n");
     FILE *in = host_open_input(o.in_path);
     FILE *out = o.out_path ? fopen(o.out_path, "w") : stdout;
     if (!in || !out) {

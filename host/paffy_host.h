@@ -81,6 +81,7 @@ void host_set_bed_tail(const fasta_text *t);
  * <part>.tails, the chain numbers come from <part>.ids, the line keys go to <part>.lkeys, and a failure is reported up the pipe and
  * printed only when the launcher says that it is the one the whole run ends with (host/paffy_stream.c, host/paffy_launch.c). */
 int host_chain(FILE *in, FILE *out, const paffy_chain_opts *opts);
+int host_chain_fresh_walk(void); /* PAFFY_CHAIN_FRESH_WALK=1: chain restates the reference's walk from a fresh iterator */
 /* paffy split_file: normalised lines (cigar text verbatim) routed to "<prefix><contig>.paf" / "<prefix>small_<k>.paf" */
 int host_split_file(FILE *in, const char *prefix, int by_query, int64_t min_length);
 

@@ -1500,6 +1500,14 @@ int main(int argc, char **argv) {
             else close(fd);
         }
     }
+    if (shard && is_chain && getenv("PAFFY_CHAIN_FRESH_WALK") && atoi(getenv("PAFFY_CHAIN_FRESH_WALK")) != 0) {
+        /* the walk from a fresh iterator depends on a strand's leading single-group run, a property of the whole input and not of a part
+           (DESIGN 3): one worker chains it, as for the commands that are not cut */
+        for (int i = 0; i + 1 < cl.n_opts; i++)
+            if (!strcmp(cl.opts[i], "-l") && (!strcasecmp(cl.opts[i + 1], "INFO") || !strcasecmp(cl.opts[i + 1], "DEBUG")))
+                fprintf(stderr, "paffy chain: PAFFY_CHAIN_FRESH_WALK is set: chain in parts does not restate the fresh-iterator walk, running on one worker (PAFFY_GPUS=%d ignored)\n", n);
+        shard = 0;
+    }
     if (!shard) { /* one GPU (or a command that does not shard): this process becomes the worker; it has not touched a GPU */
         free(cl.copy);
         argv[0] = g_worker;

@@ -956,6 +956,7 @@ static int whole_file(FILE *in, FILE *out, const paffy_bed_opts *bed, const paff
         fprintf(stderr, "paffy %s: out of memory\n", what);
         return 1;
     }
+    if (chain && host_chain_fresh_walk() && paffy_hip_chain_fresh_walk(ctx, 1) != 0) rc = 1; /* a part under it is refused by the run */
     if ((bed ? paffy_hip_bed_begin(ctx, bed) : (chain ? paffy_hip_chain_begin(ctx) : paffy_hip_tile_begin(ctx))) != 0) rc = 1;
     while (!rc && (!eof || have > 0)) {
         if (!eof) {

@@ -399,6 +399,17 @@ int paffy_hip_chain_add(paffy_hip_ctx *ctx, const void *d_in, int64_t in_len);
 int paffy_hip_chain_run(paffy_hip_ctx *ctx, const paffy_chain_opts *opts, paffy_plan_info *info);
 int64_t paffy_hip_chain_tags(paffy_hip_ctx *ctx, int64_t cap, int64_t *chain_id, int64_t *chain_score);
 /*
+ * The reference's walk from a fresh iterator (impl/chaining.c:71-86): when its search finds no active chain <= the search key it walks
+ * the whole set from the top, so an alignment that abuts the record exactly on both sequences but stands later in the input is chained
+ * after all. Off (the default) paffy_hip_chain_run leaves that walk out; on, it restates it exactly: a context switch in the
+ * manner of paffy_hip_stats_only, read by paffy_hip_chain_run. paffy_hip_chain_run_part returns PAFFY_E_UNSUPPORTED and changes nothing
+ * while it is on. fresh_stats, of the last run: out[0] the records of the strands' leading runs that the flag kernel processed (0: it was
+ * not launched), out[1] how many of them it flagged fresh, out[2] the links of the result that join a record to such an alignment,
+ * out[3] how many such candidates the first recurrence skipped. All zero with the switch off.
+ */
+int paffy_hip_chain_fresh_walk(paffy_hip_ctx *ctx, int on);
+int paffy_hip_chain_fresh_stats(paffy_hip_ctx *ctx, int64_t out[4]);
+/*
  * Chain in parts: `paffy chain` sharded by query sequence. The recurrence is independent per (query, target, strand), so
  * a context that holds ALL records of some query names (the partition of paffy_hip_query_names_counts / paffy_hip_split_to) finds the
  * links, chain scores and cuts one process would. Three things are global -- the chain numbers (cn), the place of every line, the

@@ -14,6 +14,9 @@ struct ChainState {
     /* chain in parts: the records' global input numbers (one int64 per record once a batch came with them), the records ordered and
        ranked by them (grank per record, ai per position), the chain ends in local chain order, a few words of counters */
     DevBuf gidx, gperm, grank, ai, tails, words;
+    /* the walk from a fresh iterator (paffy_hip_chain_fresh_walk): the leading runs, one byte per position, the flag kernel's live lists */
+    DevBuf lead, fresh, slots;
+    int64_t fresh_stats[4] = {0, 0, 0, 0}; /* of the last run: records the flag kernel took, flagged fresh, links it gave, candidates skipped */
     bool indexed = false;    /* a batch was added with global numbers: gidx holds one per record */
     bool part_ready = false; /* chain_part ran without error: tail keys can be read, chain_finish may follow */
     uint32_t n_chains = 0;
@@ -65,10 +68,11 @@ static int chain_report(paffy_hip_ctx *c, unsigned long long key, paffy_error *e
  * their numbering inside this context -- by (strand, chain-end score desc, processing key desc, input number desc). chain_finish: output
  * order, tags, paf_check, with the chain numbers chain_part gave or the ones a caller installed in between (paffy_hip_chain_renumber).
  */
-static int chain_part(paffy_hip_ctx *c, const ChainOpts &o, bool count_chains, paffy_error *err) {
+static int chain_part(paffy_hip_ctx *c, const ChainOpts &o, bool count_chains, paffy_error *err, bool fresh_walk = false) {
     CovState &S = cov_state(c);
     ChainState &H = chain_state(c);
     memset(err, 0, sizeof(*err));
+    memset(H.fresh_stats, 0, sizeof(H.fresh_stats));
     H.n_out = 0;
     H.n_chains = 0;
     H.part_ready = false;
@@ -162,9 +166,46 @@ static int chain_part(paffy_hip_ctx *c, const ChainOpts &o, bool count_chains, p
     HIPCHK(c, hipMemsetAsync(H.n_big.p, 0, sizeof(uint32_t), c->stream));
     LAUNCH(c, "k_chain_big_list", k_chain_big_list, dim3((n_groups + PAFFY_NT - 1) / PAFFY_NT), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(U32(H.start)), n_groups,
            U32(H.big_list), U32(H.n_big));
-    LAUNCH(c, "k_chain_dp", k_chain_dp, dim3(wgrid), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(U32(H.start)), n_groups, o, Q);
+    ChainLead *lead = nullptr;
+    if (fresh_walk) { /* the strands' leading runs: the first recurrence counts what it skips inside them */
+        if (ensure(c, H.lead, sizeof(ChainLead))) return PAFFY_E_HIP;
+        lead = static_cast<ChainLead *>(H.lead.p);
+        HIPCHK(c, hipMemsetAsync(lead, 0xff, sizeof(ChainLead), c->stream));
+        const uint32_t ggrid = (n_groups + PAFFY_NT - 1) / PAFFY_NT;
+        for (int phase = 0; phase < 3; phase++)
+            LAUNCH(c, "k_chain_lead_runs", k_chain_lead_runs, dim3(phase < 2 ? ggrid : 1u), dim3(PAFFY_NT), 0, phase, static_cast<const uint32_t *>(U32(H.start)), n_groups, Q, lead);
+    }
+    LAUNCH(c, "k_chain_dp", k_chain_dp, dim3(wgrid), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(U32(H.start)), n_groups, o, Q, static_cast<const uint8_t *>(nullptr), lead);
     LAUNCH(c, "k_chain_dp_big", k_chain_dp_big, dim3(256), dim3(CHAIN_BIG_NT), 0, static_cast<const uint32_t *>(U32(H.start)), static_cast<const uint32_t *>(U32(H.big_list)),
-           static_cast<const uint32_t *>(U32(H.n_big)), o, Q);
+           static_cast<const uint32_t *>(U32(H.n_big)), o, Q, static_cast<const uint8_t *>(nullptr), lead);
+    bool flagged = false;
+    if (fresh_walk) {
+        ChainLead hl;
+        if (cov_fetch(c, &hl, lead, sizeof(hl))) return PAFFY_E_HIP;
+        H.fresh_stats[3] = (int64_t)(hl.skipped[0] + hl.skipped[1]);
+        if (hl.skipped[0] + hl.skipped[1]) {
+            /* some search of a leading run skipped a candidate: which searches were fresh, and those one or two groups again */
+            const size_t per_run = ((size_t)n + 63) / 64 * 64 + 64;
+            if (ensure(c, H.fresh, n1) || ensure(c, H.slots, (2 * sizeof(int64_t) + sizeof(uint32_t)) * 2 * per_run)) return PAFFY_E_HIP;
+            HIPCHK(c, hipMemsetAsync(H.fresh.p, 0, n1, c->stream));
+            int64_t *live = static_cast<int64_t *>(H.slots.p);
+            const ChainLive V{live, live + 2 * per_run, reinterpret_cast<uint32_t *>(live + 4 * per_run), per_run};
+            LAUNCH(c, "k_chain_fresh_flags", k_chain_fresh_flags, dim3(2), dim3(64), 0, o, Q, lead, V, U8(H.fresh));
+            const uint8_t *fresh = U8(H.fresh);
+            for (int s = 0; s < 2; s++) {
+                if (!hl.skipped[s]) continue;
+                H.fresh_stats[0] += (int64_t)(hl.last[s] - hl.g0[s]) + 1;
+                uint32_t ends[2];
+                if (cov_fetch(c, ends, U32(H.start) + hl.g[s], sizeof(ends))) return PAFFY_E_HIP;
+                if (ends[1] - ends[0] > CHAIN_BIG_GROUP)
+                    LAUNCH(c, "k_chain_dp_big", k_chain_dp_big, dim3(1), dim3(CHAIN_BIG_NT), 0, static_cast<const uint32_t *>(U32(H.start)), static_cast<const uint32_t *>(&lead->g[s]),
+                           static_cast<const uint32_t *>(&lead->one), o, Q, fresh, static_cast<ChainLead *>(nullptr));
+                else
+                    LAUNCH(c, "k_chain_dp", k_chain_dp, dim3(1), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(U32(H.start)) + hl.g[s], 1u, o, Q, fresh, static_cast<ChainLead *>(nullptr));
+            }
+            flagged = true;
+        }
+    }
     /* (chain score desc, processing index desc): least significant key first, stable sorts */
     LAUNCH(c, "k_chain_not", k_chain_not, dim3(grid), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(U32(H.prank)), n, U32(S.v32a));
     if (cov_sort_pairs32(c, S, U32(S.v32a), U32(S.v32b), U32(H.iota), U32(H.o1), n)) return PAFFY_E_HIP;
@@ -184,6 +225,13 @@ static int chain_part(paffy_hip_ctx *c, const ChainOpts &o, bool count_chains, p
     if (cov_sort_pairs32(c, S, U32(H.cls), U32(S.v32b), U32(H.o2), U32(H.o1), n)) return PAFFY_E_HIP;
     LAUNCH(c, "k_chain_number", k_chain_number, dim3(grid), dim3(PAFFY_NT), 0, static_cast<const uint32_t *>(U32(H.o1)), static_cast<const uint8_t *>(U8(H.is_tail)), n,
            U32(H.chain_of_tail), U32(H.tails));
+    if (flagged) {
+        ChainLead hl;
+        LAUNCH(c, "k_chain_fresh_links", k_chain_fresh_links, dim3(grid), dim3(PAFFY_NT), 0, Q, n, lead);
+        if (cov_fetch(c, &hl, lead, sizeof(hl))) return PAFFY_E_HIP;
+        H.fresh_stats[1] = (int64_t)hl.n_fresh;
+        H.fresh_stats[2] = (int64_t)hl.n_links;
+    }
     if (count_chains) {
         uint32_t *n_chains = reinterpret_cast<uint32_t *>(static_cast<unsigned long long *>(H.words.p) + 2);
         HIPCHK(c, hipMemsetAsync(n_chains, 0, sizeof(uint32_t), c->stream));
@@ -237,8 +285,8 @@ static int chain_finish(paffy_hip_ctx *c, paffy_error *err) {
     return 0;
 }
 
-static int chain_run(paffy_hip_ctx *c, const ChainOpts &o, paffy_error *err) {
-    int rc = chain_part(c, o, false, err);
+static int chain_run(paffy_hip_ctx *c, const ChainOpts &o, paffy_error *err, bool fresh_walk) {
+    int rc = chain_part(c, o, false, err, fresh_walk);
     if (rc || err->code || (uint32_t)cov_state(c).n_rec == 0) return rc;
     return chain_finish(c, err);
 }

@@ -178,10 +178,181 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_prefix_max(const uint32_t *s
 }
 
 /*
+ * The walk from a fresh iterator (impl/chaining.c:71-86), behind paffy_hip_chain_fresh_walk. When the search of record i finds no
+ * active chain <= (ts_i, qs_i, address_i) the reference walks the whole set from its top. That shows it one kind of candidate more: an
+ * earlier-processed p of i's group with te_p == ts_i, qe_p == qs_i and a later address. The search can only come out empty while
+ * every record processed so far in the strand is of i's own group (a group with smaller names sorts below every key, one with greater
+ * names sits on top and ends the walk at once, and a group never empties: the record that removes is inserted itself) -- the strand's
+ * leading single-group run -- and when no record of the run that is still in the set sorts <= the key. What is still in the set is a
+ * function of the coordinates alone (k_chain_fresh_flags). With one byte per position -- fresh or not -- the recurrence is the one
+ * below with "sorts after the search key" reading "... and i is not fresh"; the walk is a full descending scan, so the choice among
+ * equal scores stays the largest (te, qe, address).
+ */
+struct ChainLead {
+    unsigned long long first[2];   /* per strand: (processing rank << 32 | group) of its first record; all ones: no record */
+    uint32_t other[2];             /* processing rank of the strand's first record of another group; all ones: none */
+    uint32_t g[2], g0[2], end[2];  /* the leading run: its group, its positions [g0, end) */
+    uint32_t last[2];              /* the last position of the run whose search skipped such a candidate */
+    unsigned long long skipped[2]; /* how many the recurrence skipped inside the run */
+    unsigned long long n_fresh, n_links;
+    uint32_t one;                  /* 1: the length of the list {g[s]} for k_chain_dp_big */
+};
+/* phase 0: the group a strand begins with; phase 1: where another group's first record stands; phase 2: the run's positions */
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_lead_runs(int phase, const uint32_t *start, uint32_t n_groups, ChainPos Q, ChainLead *L) {
+    const uint32_t g = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (phase < 2) {
+        if (g >= n_groups) return;
+        const uint32_t h = start[g], s = Q.neg[h] ? 1u : 0u; /* a group's first position has its lowest rank */
+        if (phase == 0) atomicMin(&L->first[s], ((unsigned long long)Q.rank[h] << 32) | g);
+        else if (g != (uint32_t)L->first[s]) atomicMin(&L->other[s], Q.rank[h]);
+        return;
+    }
+    if (g >= 2) return;
+    const uint32_t s = g;
+    L->last[s] = 0;
+    L->skipped[s] = 0;
+    if (s == 0) {
+        L->n_fresh = L->n_links = 0;
+        L->one = 1;
+    }
+    if (L->first[s] == ~0ull) {
+        L->g[s] = L->g0[s] = L->end[s] = 0;
+        return;
+    }
+    const uint32_t lg = (uint32_t)L->first[s], other = L->other[s];
+    uint32_t lo = start[lg], hi = start[lg + 1]; /* ranks grow inside a group: the first position whose rank is past `other` */
+    L->g[s] = lg;
+    L->g0[s] = lo;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (Q.rank[mid] < other) lo = mid + 1;
+        else hi = mid;
+    }
+    L->end[s] = lo;
+}
+__device__ __forceinline__ void chain_note_skip(ChainLead *L, uint32_t i) {
+    for (uint32_t s = 0; s < 2; s++)
+        if (i >= L->g0[s] && i < L->end[s]) {
+            atomicAdd(&L->skipped[s], 1ull);
+            atomicMax(&L->last[s], i);
+        }
+}
+/*
+ * Which searches of a leading run come out empty: one wave per run, the records in order up to the last one that skipped a candidate.
+ * The set is kept as the keys (te, qe, address) still in it, lane l holding those it was given (every 64th record of the run, in
+ * order), 64 entries to a row: a lane reads and compacts only what it wrote, so the wave needs no fence, and a walk costs live / 64
+ * steps, four loads in flight.
+ * Per record (impl/chaining.c:164-183): any live e <= key? If none the walk visits everything; else the live e <= key from the top
+ * down to the first one within max_gap on the query and beyond it on the target (the breaker: the largest such). What it visits and
+ * finds more than max_gap behind on the query leaves the set once the record is in.
+ */
+__device__ __forceinline__ bool chain_key_gt(int64_t te, int64_t qe, uint32_t ai, int64_t te2, int64_t qe2, uint32_t ai2) {
+    return te > te2 || (te == te2 && (qe > qe2 || (qe == qe2 && ai > ai2)));
+}
+struct ChainLive { /* the flag kernel's live lists: the keys themselves, so that a walk is one level of loads */
+    int64_t *te, *qe;
+    uint32_t *ai;
+    size_t per_run; /* entries per run: 64 more than the records, rounded up to whole rows */
+};
+#define CHAIN_LIVE_FLIGHT 4
+__global__ __launch_bounds__(64) void k_chain_fresh_flags(ChainOpts o, ChainPos Q, ChainLead *L, ChainLive V, uint8_t *fresh) {
+    const uint32_t s = blockIdx.x, lane = threadIdx.x;
+    if (L->skipped[s] == 0) return;
+    const uint32_t g0 = L->g0[s], last = L->last[s];
+    int64_t *m_te = V.te + s * V.per_run + lane, *m_qe = V.qe + s * V.per_run + lane;
+    uint32_t *m_ai = V.ai + s * V.per_run + lane;
+    uint32_t cnt = 0, n_fresh = 0;
+    for (uint32_t i = g0; i <= last; i++) {
+        const int64_t qs_i = Q.qs[i], ts_i = Q.ts[i];
+        const uint32_t ai_i = Q.ai[i];
+        bool any_le = false, dead_any = false, dead_le = false, has_b = false;
+        int64_t b_te = 0, b_qe = 0;
+        uint32_t b_ai = 0;
+        for (uint32_t k0 = 0; k0 < cnt; k0 += CHAIN_LIVE_FLIGHT) {
+            int64_t te4[CHAIN_LIVE_FLIGHT], qe4[CHAIN_LIVE_FLIGHT];
+            uint32_t ai4[CHAIN_LIVE_FLIGHT];
+#pragma unroll
+            for (int u = 0; u < CHAIN_LIVE_FLIGHT; u++) {
+                const bool in = k0 + u < cnt;
+                const size_t at = (size_t)(k0 + u) * 64;
+                te4[u] = in ? m_te[at] : INT64_MAX; /* above every key, not behind the record: counts for nothing */
+                qe4[u] = in ? m_qe[at] : INT64_MAX;
+                ai4[u] = in ? m_ai[at] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < CHAIN_LIVE_FLIGHT; u++) {
+                const int64_t te = te4[u], qe = qe4[u];
+                const uint32_t ai = ai4[u];
+                const bool le = !chain_key_gt(te, qe, ai, ts_i, qs_i, ai_i);
+                const bool behind = qs_i >= qe, dead = behind && qs_i - qe > o.max_gap;
+                any_le |= le;
+                dead_any |= dead;
+                dead_le |= dead && le;
+                if (le && behind && !dead && ts_i - te > o.max_gap && (!has_b || chain_key_gt(te, qe, ai, b_te, b_qe, b_ai))) {
+                    has_b = true; b_te = te; b_qe = qe; b_ai = ai;
+                }
+            }
+        }
+        const bool is_fresh = __ballot(any_le) == 0;
+        if (is_fresh) n_fresh++;
+        if (lane == 0) fresh[i] = is_fresh ? 1 : 0;
+        if (__ballot(is_fresh ? dead_any : dead_le) != 0) {
+            if (!is_fresh && __ballot(has_b) != 0) /* the breaker of the wave: the largest of the lanes' */
+                for (int msk = 32; msk >= 1; msk >>= 1) {
+                    const int64_t o_te = wave_shfl_xor64(b_te, msk), o_qe = wave_shfl_xor64(b_qe, msk);
+                    const uint32_t o_ai = (uint32_t)__shfl_xor((int)b_ai, msk);
+                    const bool o_has = __shfl_xor((int)has_b, msk) != 0;
+                    if (o_has && (!has_b || chain_key_gt(o_te, o_qe, o_ai, b_te, b_qe, b_ai))) {
+                        has_b = true; b_te = o_te; b_qe = o_qe; b_ai = o_ai;
+                    }
+                }
+            uint32_t w = 0; /* compact in place: what is written stands in front of what is still to be read */
+            for (uint32_t k0 = 0; k0 < cnt; k0 += CHAIN_LIVE_FLIGHT) {
+                int64_t te4[CHAIN_LIVE_FLIGHT], qe4[CHAIN_LIVE_FLIGHT];
+                uint32_t ai4[CHAIN_LIVE_FLIGHT];
+#pragma unroll
+                for (int u = 0; u < CHAIN_LIVE_FLIGHT; u++) {
+                    const bool in = k0 + u < cnt;
+                    const size_t at = (size_t)(k0 + u) * 64;
+                    te4[u] = in ? m_te[at] : INT64_MAX;
+                    qe4[u] = in ? m_qe[at] : INT64_MAX;
+                    ai4[u] = in ? m_ai[at] : 0u;
+                }
+#pragma unroll
+                for (int u = 0; u < CHAIN_LIVE_FLIGHT; u++) {
+                    if (k0 + u >= cnt) break;
+                    const int64_t te = te4[u], qe = qe4[u];
+                    const uint32_t ai = ai4[u];
+                    const bool dead = qs_i >= qe && qs_i - qe > o.max_gap;
+                    const bool visited = is_fresh || (!chain_key_gt(te, qe, ai, ts_i, qs_i, ai_i) && (!has_b || chain_key_gt(te, qe, ai, b_te, b_qe, b_ai)));
+                    if (!(dead && visited)) {
+                        const size_t at = (size_t)(w++) * 64;
+                        m_te[at] = te; m_qe[at] = qe; m_ai[at] = ai;
+                    }
+                }
+            }
+            cnt = w;
+        }
+        if (lane == ((i - g0) & 63u)) {
+            const size_t at = (size_t)(cnt++) * 64;
+            m_te[at] = Q.te[i]; m_qe[at] = Q.qe[i]; m_ai[at] = ai_i;
+        }
+    }
+    if (lane == 0) atomicAdd(&L->n_fresh, (unsigned long long)n_fresh);
+}
+/* links of the result that only the fresh walk gives */
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_fresh_links(ChainPos Q, uint32_t n, ChainLead *L) {
+    const uint32_t i = blockIdx.x * PAFFY_NT + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = Q.pred[i];
+    if (p != CHAIN_NONE && Q.te[p] == Q.ts[i] && Q.qe[p] == Q.qs[i] && Q.ai[p] > Q.ai[i]) atomicAdd(&L->n_links, 1ull);
+}
+
+/*
  * The recurrence, impl/chaining.c:150-205: one wave per group. Lane l looks at the candidates p with (p - g0) % 64 == l and is the
  * one that writes best[] / pred[] of those positions: a lane only ever reads values it wrote itself, so the wave needs no fence.
  */
-__global__ __launch_bounds__(PAFFY_NT) void k_chain_dp(const uint32_t *start, uint32_t n_groups, ChainOpts o, ChainPos Q) {
+__global__ __launch_bounds__(PAFFY_NT) void k_chain_dp(const uint32_t *start, uint32_t n_groups, ChainOpts o, ChainPos Q, const uint8_t *fresh, ChainLead *lead) {
     const uint32_t g = blockIdx.x * PAFFY_NWAVE + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (g >= n_groups) return;
     const uint32_t g0 = start[g], g1 = start[g + 1];
@@ -190,6 +361,7 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_dp(const uint32_t *start, ui
     for (uint32_t i = g0; i < g1; i++) {
         const int64_t qs_i = Q.qs[i], ts_i = Q.ts[i], sc_i = Q.sc[i];
         const uint32_t idx_i = Q.ai[i];
+        const bool fresh_i = fresh && fresh[i]; /* no flags: the walk from a fresh iterator is left out */
         while (lo < i && Q.mq[lo] < qs_i - o.max_gap) lo++;
         int64_t b_cs = INT64_MIN, b_te = 0, b_qe = 0;
         uint32_t b_idx = 0, b_p = CHAIN_NONE;
@@ -199,7 +371,10 @@ __global__ __launch_bounds__(PAFFY_NT) void k_chain_dp(const uint32_t *start, ui
             if (qs_i < qe_p || qs_i - qe_p > o.max_gap) continue;
             if (ts_i < te_p || ts_i - te_p > o.max_gap) continue;
             const uint32_t idx_p = Q.ai[p];
-            if (te_p == ts_i && qe_p == qs_i && idx_p > idx_i) continue; /* sorts after the search key (impl/chaining.c:71-79) */
+            if (te_p == ts_i && qe_p == qs_i && idx_p > idx_i && !fresh_i) { /* sorts after the search key (impl/chaining.c:71-79) */
+                if (lead) chain_note_skip(lead, i);
+                continue;
+            }
             const int64_t gc = chain_gap_cost(o, qs_i - qe_p, ts_i - te_p);
             if (!(gc < sc_i)) continue;
             const int64_t cs = sc_i + Q.best[p] - gc;
@@ -260,10 +435,13 @@ __device__ __forceinline__ void chain_cand_reduce(ChainCand &b, int from_mask) {
 }
 /* candidate p (query / target end, input index, chain score) for the record (qs_i, ts_i, sc_i, idx_i): its chain score, or nothing */
 __device__ __forceinline__ void chain_try(const ChainOpts &o, int64_t qs_i, int64_t ts_i, int64_t sc_i, uint32_t idx_i, int64_t qe_p, int64_t te_p, uint32_t idx_p,
-                                          int64_t best_p, uint32_t p, ChainCand &b) {
+                                          int64_t best_p, uint32_t p, ChainCand &b, bool fresh_i, ChainLead *lead, uint32_t i) {
     if (qs_i < qe_p || qs_i - qe_p > o.max_gap) return;
     if (ts_i < te_p || ts_i - te_p > o.max_gap) return;
-    if (te_p == ts_i && qe_p == qs_i && idx_p > idx_i) return; /* sorts after the search key (impl/chaining.c:71-79) */
+    if (te_p == ts_i && qe_p == qs_i && idx_p > idx_i && !fresh_i) { /* sorts after the search key (impl/chaining.c:71-79) */
+        if (lead) chain_note_skip(lead, i);
+        return;
+    }
     const int64_t gc = chain_gap_cost(o, qs_i - qe_p, ts_i - te_p);
     if (!(gc < sc_i)) return;
     ChainCand c;
@@ -275,7 +453,8 @@ __device__ __forceinline__ void chain_try(const ChainOpts &o, int64_t qs_i, int6
 #ifndef CHAIN_FLIGHT
 #define CHAIN_FLIGHT 4
 #endif
-__global__ __launch_bounds__(CHAIN_BIG_NT) void k_chain_dp_big(const uint32_t *start, const uint32_t *big_list, const uint32_t *n_big, ChainOpts o, ChainPos Q) {
+__global__ __launch_bounds__(CHAIN_BIG_NT) void k_chain_dp_big(const uint32_t *start, const uint32_t *big_list, const uint32_t *n_big, ChainOpts o, ChainPos Q, const uint8_t *fresh,
+                                                               ChainLead *lead) {
     __shared__ int64_t t_cs[CHAIN_TILE], t_te[CHAIN_TILE], t_qe[CHAIN_TILE];
     __shared__ uint32_t t_idx[CHAIN_TILE], t_p[CHAIN_TILE];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -289,6 +468,7 @@ __global__ __launch_bounds__(CHAIN_BIG_NT) void k_chain_dp_big(const uint32_t *s
             if (i < g1) {
                 const int64_t qs_i = Q.qs[i], ts_i = Q.ts[i], sc_i = Q.sc[i];
                 const uint32_t idx_i = Q.ai[i];
+                const bool fresh_i = fresh && fresh[i];
                 while (lo < base && Q.mq[lo] < qs_i - o.max_gap) lo++;
                 ChainCand b;
                 b.cs = INT64_MIN; b.te = 0; b.qe = 0; b.idx = 0; b.p = CHAIN_NONE;
@@ -305,7 +485,7 @@ __global__ __launch_bounds__(CHAIN_BIG_NT) void k_chain_dp_big(const uint32_t *s
                         best4[u] = in ? Q.best[p] : 0;
                     }
 #pragma unroll
-                    for (int u = 0; u < CHAIN_FLIGHT; u++) chain_try(o, qs_i, ts_i, sc_i, idx_i, qe4[u], te4[u], idx4[u], best4[u], p0 + u * 64, b);
+                    for (int u = 0; u < CHAIN_FLIGHT; u++) chain_try(o, qs_i, ts_i, sc_i, idx_i, qe4[u], te4[u], idx4[u], best4[u], p0 + u * 64, b, fresh_i, lead, i);
                 }
                 chain_cand_reduce(b, 32);
                 if (lane == 0) {
@@ -329,9 +509,10 @@ __global__ __launch_bounds__(CHAIN_BIG_NT) void k_chain_dp_big(const uint32_t *s
                     /* record w against the tile records in front of it: lane l < w offers itself */
                     const int64_t qs_w = wave_shfl64(qs_m, (int)w), ts_w = wave_shfl64(ts_m, (int)w), sc_w = wave_shfl64(sc_m, (int)w);
                     const uint32_t idx_w = (uint32_t)__shfl((int)idx_m, (int)w);
+                    const bool fresh_w = fresh && fresh[base + w];
                     ChainCand b;
                     b.cs = INT64_MIN; b.te = 0; b.qe = 0; b.idx = 0; b.p = CHAIN_NONE;
-                    if (lane < w) chain_try(o, qs_w, ts_w, sc_w, idx_w, qe_m, te_m, idx_m, fin, base + lane, b);
+                    if (lane < w) chain_try(o, qs_w, ts_w, sc_w, idx_w, qe_m, te_m, idx_m, fin, base + lane, b, fresh_w, lead, base + w);
                     chain_cand_reduce(b, CHAIN_TILE / 2); /* lanes 0-15 hold the tile (lanes above offer nothing and only mix among themselves) */
                     if (lane == w) {
                         if (chain_cand_better(b, mine)) mine = b;

@@ -1141,6 +1141,7 @@ struct paffy_hip_ctx {
     bool profile = false;
     int64_t flat_left = -1, flat_reasons[16] = {0}; /* paffy_hip_flat_stats */
     bool stats_only = false;      /* paffy_hip_stats_only: the caller will only ask a plan for its sums */
+    bool chain_fresh = false;     /* paffy_hip_chain_fresh_walk: chain_run restates the reference's walk from a fresh iterator */
     bool plan_stats_only = false; /* the last plan took FLAT_MODE_VIEW: it has sums, no ops and no line plan */
     bool plan_split = false;      /* the last plan is paffy_hip_split_plan's: a line plan with a group table (paffy_hip_split_groups) */
     DevBuf view_sums;             /* flat_view_kernel.h: six sums per piece slot */
@@ -2182,7 +2183,7 @@ int paffy_hip_chain_run(paffy_hip_ctx *c, const paffy_chain_opts *opts, paffy_pl
     const uint64_t n = S.n_rec;
     if (n > 0) {
         const ChainOpts o{opts->gap_open, opts->gap_extend, opts->max_gap_length, opts->trim_fraction};
-        int rc = chain_run(c, o, &c->plan.error);
+        int rc = chain_run(c, o, &c->plan.error, c->chain_fresh);
         if (rc) return rc;
         if (c->plan.error.code == 0) {
             int rl = lines_plan(c, S, n);
@@ -2200,6 +2201,10 @@ int paffy_hip_chain_run(paffy_hip_ctx *c, const paffy_chain_opts *opts, paffy_pl
  */
 int paffy_hip_chain_run_part(paffy_hip_ctx *c, const paffy_chain_opts *opts, paffy_plan_info *info) {
     if (!c || !info || !opts) return PAFFY_E_ARG;
+    if (c->chain_fresh) { /* a strand's leading run is a property of the whole input, not of a part */
+        c->last_error = "paffy_hip_chain_run_part: not built under paffy_hip_chain_fresh_walk (a strand's leading run spans the parts)";
+        return PAFFY_E_UNSUPPORTED;
+    }
     CovState &S = cov_state(c);
     plan_begin(c, PLAN_LINES, cov_in_bytes(S), info);
     c->plan.n_records = (int64_t)S.n_rec;
@@ -2208,6 +2213,17 @@ int paffy_hip_chain_run_part(paffy_hip_ctx *c, const paffy_chain_opts *opts, paf
     if (rc) return rc;
     if (c->profile) prof_collect(c);
     *info = c->plan; /* no lines planned: c->planned stays false until paffy_hip_chain_renumber */
+    return 0;
+}
+int paffy_hip_chain_fresh_walk(paffy_hip_ctx *c, int on) {
+    if (!c) return PAFFY_E_ARG;
+    c->chain_fresh = on != 0;
+    return 0;
+}
+int paffy_hip_chain_fresh_stats(paffy_hip_ctx *c, int64_t out[4]) {
+    if (!c || !out) return PAFFY_E_ARG;
+    if (!c->chain) return PAFFY_E_STATE;
+    memcpy(out, c->chain->fresh_stats, sizeof(c->chain->fresh_stats));
     return 0;
 }
 int64_t paffy_hip_chain_tail_keys(paffy_hip_ctx *c, int64_t cap_chains, void *d_keys) {

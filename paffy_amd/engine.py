@@ -125,6 +125,9 @@ def lib():
         L.paffy_hip_chain_run.argtypes = [vp, C.POINTER(ChainOpts), C.POINTER(PlanInfo)]
         L.paffy_hip_chain_tags.restype = i64
         L.paffy_hip_chain_tags.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64)]
+        if hasattr(L, "paffy_hip_chain_fresh_walk"):  # an older library under PAFFY_HIP_LIB has none: the calls then raise
+            L.paffy_hip_chain_fresh_walk.argtypes = [vp, C.c_int]
+            L.paffy_hip_chain_fresh_stats.argtypes = [vp, C.POINTER(i64)]
         L.paffy_hip_chain_add_indexed.argtypes = [vp, vp, i64, vp]
         L.paffy_hip_chain_run_part.argtypes = [vp, C.POINTER(ChainOpts), C.POINTER(PlanInfo)]
         L.paffy_hip_chain_tail_keys.restype = i64
@@ -502,9 +505,27 @@ class Engine:
                            L.paffy_hip_error_exit_status(info.error.code))
         return out, info
 
-    def chain(self, data, gap_open=5000, gap_extend=1, max_gap=1000000, trim=1.0, raise_on_error=True, batch_bytes=None):
+    def chain_fresh_walk(self, on=True):
+        """The reference's walk from a fresh iterator (impl/chaining.c:71-86): an alignment that abuts a record exactly on both sequences
+        but stands later in the input is chained after all. Sticky, off by default; chain_part refuses while it is on."""
+        self._check(lib().paffy_hip_chain_fresh_walk(self._ctx, 1 if on else 0), "paffy_hip_chain_fresh_walk")
+
+    def chain_fresh_stats(self):
+        """Of the last chain run: [records of leading runs the flag kernel processed (0: not launched), flagged fresh, links of the
+        result only the fresh walk gives, such candidates the first recurrence skipped]."""
+        out = (C.c_int64 * 4)()
+        self._check(lib().paffy_hip_chain_fresh_stats(self._ctx, out), "paffy_hip_chain_fresh_stats")
+        return list(out)
+
+    def chain(self, data, gap_open=5000, gap_extend=1, max_gap=1000000, trim=1.0, raise_on_error=True, batch_bytes=None, fresh_walk=False):
         """paffy chain (impl/paf_chain.c, impl/chaining.c) over PAF text; returns (output bytes, PlanInfo). The keyword defaults are
-        the command's (-d, -e, -g, -t)."""
+        the command's (-d, -e, -g, -t). fresh_walk: this run with the switch of chain_fresh_walk on (and off again afterwards)."""
+        if fresh_walk:
+            self.chain_fresh_walk(True)
+            try:
+                return self.chain(data, gap_open, gap_extend, max_gap, trim, raise_on_error, batch_bytes)
+            finally:
+                self.chain_fresh_walk(False)
         pieces = self.split_lines(data, batch_bytes) if batch_bytes else [data]
         bufs = [(self.to_device(p), len(p)) for p in pieces if len(p)]
         self._check(lib().paffy_hip_chain_begin(self._ctx), "paffy_hip_chain_begin")
@@ -1418,9 +1439,9 @@ def tile(data):
     return _engine().tile(data)[0]
 
 
-def chain(data, gap_open=5000, gap_extend=1, max_gap=1000000, trim=1.0):
-    """paffy chain [-d gap_open] [-e gap_extend] [-g max_gap] [-t trim] (impl/paf_chain.c)."""
-    return _engine().chain(data, gap_open, gap_extend, max_gap, trim)[0]
+def chain(data, gap_open=5000, gap_extend=1, max_gap=1000000, trim=1.0, fresh_walk=False):
+    """paffy chain [-d gap_open] [-e gap_extend] [-g max_gap] [-t trim] (impl/paf_chain.c); fresh_walk: Engine.chain_fresh_walk."""
+    return _engine().chain(data, gap_open, gap_extend, max_gap, trim, fresh_walk=fresh_walk)[0]
 
 
 def trim(data, trim_identity=0.05, trim_fraction=1.0, fixed_trim=False):

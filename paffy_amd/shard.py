@@ -766,7 +766,11 @@ class GpuChainWorker(GpuTileWorker):
         return self.gidx[self.eng.torch.tensor(rec, dtype=self.eng.torch.int64, device=self.eng.device)] if rec else self.gidx[:0]
 
 
-def chain_sharded(worker, dist, rank, world, batches, first_record, comm_device="cpu", consume=False):
+_NO_FRESH_IN_PARTS = ("chain in parts does not restate the walk from a fresh iterator: whether a search is fresh depends on the strand's "
+                      "leading single-group run, a property of the whole input and not of a part; chain it in one context (Engine.chain)")
+
+
+def chain_sharded(worker, dist, rank, world, batches, first_record, comm_device="cpu", consume=False, fresh_walk=False):
     """`paffy chain` over an input spread over the ranks (this rank holds `batches`, whose first record is global record
     first_record); one rank runs the same code with world = 1 and dist = None. Returns {"error": None, "offsets": byte offset of every
     local output line in the ordered output, "total": bytes of the whole output, "keys": the [n, 4] line keys (column 3: the line
@@ -775,6 +779,8 @@ def chain_sharded(worker, dist, rank, world, batches, first_record, comm_device=
     and nothing is to be written."""
     import torch
 
+    if fresh_walk:
+        raise ValueError("chain_sharded(fresh_walk=True): " + _NO_FRESH_IN_PARTS)
     dev = worker.eng.device
     empty = {"offsets": torch.zeros(0, dtype=torch.int64, device=comm_device), "total": 0, "keys": torch.zeros(0, 4, dtype=torch.int64, device=dev), "chain_ids": None}
     local, per_batch = worker.query_names(batches)
@@ -803,12 +809,14 @@ def chain_sharded(worker, dist, rank, world, batches, first_record, comm_device=
     return {"error": None, "offsets": offsets, "total": total, "keys": keys, "chain_ids": ids, "owner_of": owner_of}
 
 
-def chain_in_parts(workers, batches, first_record=0):
+def chain_in_parts(workers, batches, first_record=0, fresh_walk=False):
     """chain_sharded without ranks: one process, one GpuChainWorker (one context) per part on the same GPU, taken in turn -- the
     partition with the real query_names / split_to, the keys exchanged in device memory, every part's lines scattered into one
     buffer. Returns {"error": None, "out": uint8 tensor with the ordered output, ...} or {"error": {...}, "out": None}."""
     import torch
 
+    if fresh_walk:
+        raise ValueError("chain_in_parts(fresh_walk=True): " + _NO_FRESH_IN_PARTS)
     k_parts, w0 = len(workers), workers[0]
     local, per_batch = w0.query_names(batches)
     owner_of = owner_table(local, k_parts)

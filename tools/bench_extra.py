@@ -36,6 +36,25 @@ def chunk_encode(text, chunk=1_000_000):
     return b"\n".join(out) + b"\n"
 
 
+def one_group_stream(n, seed=7):
+    """n collinear records of one (query, target, strand) on one diagonal, 200-2000 bases long with gaps of 1-2000, shuffled; the last one
+    in processing order abuts the one before it exactly and stands in front of it in the input (chain --one-group)"""
+    import random
+
+    rng = random.Random(seed)
+    rows, at = [], 0
+    for k in range(n):
+        ln = rng.randrange(200, 2000)
+        if k:
+            at += 0 if k == n - 1 else rng.randrange(1, 2000)
+        rows.append(b"chrA\t4000000000\t%d\t%d\t+\tchrB\t4000000000\t%d\t%d\t%d\t%d\t60\tAS:i:%d\tcg:Z:%dM\n" % (at, at + ln, at, at + ln, ln, ln, rng.randrange(500, 30000), ln))
+        at += ln
+    last, before = rows[n - 1], rows[n - 2]
+    body = rows[:n - 2]
+    rng.shuffle(body)
+    return b"".join([last] + body + [before])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=200000)
@@ -53,6 +72,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the plan (the smallest counts)")
     ap.add_argument("--sha", action="store_true", help="add_trim, add_filter: copy the last repetition's output to the host and print its SHA-256")
     ap.add_argument("--parts", type=int, default=0, help="chain: chain in parts -- this many contexts on the one GPU, taken in turn (0: the plain one-context run)")
+    ap.add_argument("--fresh-walk", action="store_true", help="chain: with paffy_hip_chain_fresh_walk on (the reference's walk from a fresh iterator)")
+    ap.add_argument("--one-group", action="store_true",
+                    help="chain: instead of the synthetic stream, --records collinear records of ONE (query, target, strand), shuffled, chained with -t 0; the "
+                         "last one in processing order abuts its predecessor exactly and stands in front of it in the input, so that under --fresh-walk "
+                         "the flag kernel takes the whole input one record after the other: its worst case")
     a = ap.parse_args()
     if a.cmd == "chain" and a.parts > 0:
         return chain_parts_bench(a)
@@ -100,6 +124,10 @@ def main():
             text = chunk_encode(text)
             nbytes = len(text)
             buf = eng.to_device(text)
+    elif a.cmd == "chain" and a.one_group:
+        text = one_group_stream(a.records)
+        buf, nbytes = eng.to_device(text), len(text)
+        del text
     else:
         buf, nbytes = eng.synth(0x5EED0005, a.mean_ops, 0, a.records, n_contigs=a.contigs)
     rows_cmd = a.cmd in ("shatter", "invert_trim_shatter")
@@ -185,7 +213,8 @@ def main():
             L = paffy_amd.engine.lib()
             assert L.paffy_hip_chain_begin(eng._ctx) == 0 and L.paffy_hip_chain_add(eng._ctx, buf.data_ptr(), nbytes) == 0
             info = paffy_amd.engine.PlanInfo()
-            opts = paffy_amd.engine.ChainOpts(5000, 1, 1000000, 1.0)
+            opts = paffy_amd.engine.ChainOpts(5000, 1, 1000000, 0.0 if a.one_group else 1.0)
+            eng.chain_fresh_walk(a.fresh_walk) if a.fresh_walk else None
             assert L.paffy_hip_chain_run(eng._ctx, opts, info) == 0
         elif a.cmd == "dedupe":
             paffy_amd.engine.lib().paffy_hip_dedupe_reset(eng._ctx)
@@ -214,6 +243,13 @@ def main():
     extra = {"flat_left": eng.flat_stats()[0]} if a.cmd in ("dechunk", "pass", "remove", "remove_eqx", "trimf") or fixed_pipe or view else {}
     if view:
         extra["sums"] = list(sums)
+    if a.cmd == "chain":
+        import statistics
+
+        extra.update(fresh_walk=bool(a.fresh_walk), one_group=bool(a.one_group), median_s=round(statistics.median(res), 5), spread_s=round(max(res) - min(res), 5),
+                     lib=os.path.basename(os.path.dirname(paffy_amd.engine.library_path())) + "/" + os.path.basename(paffy_amd.engine.library_path()))
+        if a.fresh_walk:
+            extra["fresh_stats"] = eng.chain_fresh_stats()
     if rows_cmd:
         left, why = eng.flat_stats()
         extra.update(names=a.names, piece_a_below_16=short_share, flat_left=left, flat_why=list(why), rows=int(info.n_rows))

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Soak test (GPU box): random records through random pipes, HIP path vs the CPU oracle, for a time budget.
 usage: python tools/fuzz_gpu.py [seconds] [seed] [pipe|tile|mism|bed|chain|dedupe]   -- prints the first mismatch (and saves it under gpurun_out/) or a summary."""
+# A further mode, chain_fresh: the chain fuzz under paffy_hip_chain_fresh_walk, every input against the oracle as committed (fuzz_chain).
 import hashlib
 import os
 import random
@@ -192,29 +193,34 @@ def fuzz_mismatches(eng, rng, budget):
     print(f"add_mismatches fuzz ok: {rounds} rounds")
 
 
-def fuzz_chain(eng, rng, budget):
+def fuzz_chain(eng, rng, budget, fresh_walk=False):
     """paffy chain on collinear runs over a few (query, target, strand) groups, random options; inputs where the reference's fresh
     iterator admits a candidate (an address tie, see oracle/paf_oracle.c) are compared with the oracle run WITHOUT that walk: the GPU's
-    documented behaviour there."""
+    default behaviour there. fresh_walk (mode chain_fresh): the run under paffy_hip_chain_fresh_walk, every input against the
+    oracle as committed, none skipped; more of the inputs abut exactly and have one (query, target) pair, so that the walk is taken."""
     from test_gpu_chain import collinear_set
 
-    t0, rounds, skipped = time.time(), 0, 0
+    t0, rounds, skipped, took = time.time(), 0, 0, 0
     while time.time() - t0 < budget:
         n = rng.choice([1, 3, 30, 300, 2500, 12000])
-        data = collinear_set(rng, n, n_q=rng.choice([1, 2, 6]), n_t=rng.choice([1, 3]), span=rng.choice([50_000, 2_000_000]), exact=rng.choice([0.0, 0.0, 0.3]),
-                             score_hi=rng.choice([30, 20000]))
+        data = collinear_set(rng, n, n_q=rng.choice([1, 1, 2, 6] if fresh_walk else [1, 2, 6]), n_t=rng.choice([1, 3]), span=rng.choice([50_000, 2_000_000]),
+                             exact=rng.choice([0.0, 0.3, 0.6] if fresh_walk else [0.0, 0.0, 0.3]), score_hi=rng.choice([30, 20000]))
         kw = dict(gap_open=rng.choice([0, 50, 5000]), gap_extend=rng.choice([0, 1, 3]), max_gap=rng.choice([500, 20000, 1000000]), trim=rng.choice([0.0, 0.3, 1.0]))
         want, werr, fresh = O.chain(data, **kw)
-        if fresh:
+        if fresh and not fresh_walk:
             skipped += 1
             want, werr, _ = O.chain(data, fresh_walk=False, **kw)
-        got, info = eng.chain(data, raise_on_error=False, batch_bytes=rng.choice([None, 50_000]), **kw)
+        took += 1 if fresh else 0
+        got, info = eng.chain(data, raise_on_error=False, batch_bytes=rng.choice([None, 50_000]), fresh_walk=fresh_walk, **kw)
         if got != want or info.error.code != werr.code:
             with open(os.path.join(ROOT, "gpurun_out", "fuzz_chain_fail.paf"), "wb") as fh:
                 fh.write(data)
             print("CHAIN MISMATCH", kw, info.error.code, werr.code, len(got), len(want))
             sys.exit(1)
         rounds += 1
+    if fresh_walk:
+        print(f"chain fuzz, fresh walk on: ok, {rounds} rounds, every one against the oracle as committed ({took} of them took the walk)")
+        return
     print(f"chain fuzz ok: {rounds} rounds ({skipped} of them inputs with an address tie, compared with the oracle without the fresh-iterator walk)")
 
 
@@ -282,6 +288,8 @@ def main():
         return fuzz_mismatches(eng, rng, budget)
     if mode == "chain":
         return fuzz_chain(eng, rng, budget)
+    if mode == "chain_fresh":
+        return fuzz_chain(eng, rng, budget, fresh_walk=True)
     if mode == "dedupe":
         return fuzz_dedupe(eng, rng, budget)
     kinds = [O.INVERT, O.TRIM_IDENTITY, O.TRIM_FIXED, O.REMOVE_MISMATCHES, O.PASS, O.FILTER]
