@@ -672,6 +672,18 @@ int paffy_hip_fasta_index_headers(paffy_hip_ctx *ctx, const void *d_text, int64_
    with_target, as its target -- between its fifth and sixth tab --, else 0. One device lookup per line in the sorted distinct names. */
 int paffy_hip_fasta_seen(paffy_hip_ctx *ctx, const void *d_paf, int64_t paf_len, int with_target, uint8_t *seen);
 /*
+ * The names of the context's index (paffy_hip_fasta_index or paffy_hip_fasta_index_headers) in the order of the name tables: a record's
+ * name is its header up to a NUL byte; names order by unsigned bytes, then the shorter first, then the record's input index. The sort
+ * runs on the device and builds the index's table of distinct names if it is not built. Into device memory, one int32 per record (cap:
+ * the records each array has room for): d_order[k] = the record at place k, d_name_of[r] = the index of record r's name among the
+ * distinct names; either may be NULL. n_names (may be NULL) gets the number of distinct names. PAFFY_E_STATE without an index,
+ * PAFFY_E_CAPACITY when cap < the index's records.
+ */
+int paffy_hip_fasta_name_order(paffy_hip_ctx *ctx, int64_t cap, void *d_order, void *d_name_of, int64_t *n_names);
+/* the last name sort of the context, whichever call ran it (name_order, fasta_seen, the extract plan, set_sequences_fasta): out[0] records,
+   out[1] rounds, out[2] records still tied after the first round, out[3] distinct names; zeros before the first */
+int paffy_hip_name_sort_stats(paffy_hip_ctx *ctx, int64_t out[4]);
+/*
  * Plans over the index: info->out_bytes, info->n_rows (items), info->error (PAFFY_ERR_FAFFY_*: nothing is to be written; record = the
  * record (chunk, merge), the BED line (extract: missing name, short line) or the sorted interval (extract bounds)).
  * chunk: PAFFY_E_ARG where chunk_size > overlap but chunk_size <= 0 or chunk_size + overlap < 0 (the reference loops forever / takes

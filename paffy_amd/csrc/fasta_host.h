@@ -10,12 +10,15 @@
 #include <map>
 
 #include "fasta_extract_kernel.h"
+#include "name_sort_host.h"
 
 struct FastaState {
     struct Dev { /* all of the state's device memory: fasta_release lets it go while the state lives */
         DevBuf starts, tiles, totals, recs, bases, hdr_off, hdr_blob, items, bad;
         DevBuf seen_names, seen_off, seen; /* the distinct names (fa_name_table) and paffy_hip_fasta_seen's flag per name */
         DevBuf name_rec;                   /* per distinct name: the record a BED line of that name means */
+        DevBuf name_of, seen_rec;          /* per record: its name in the table (int32), paffy_hip_fasta_seen's flag */
+        NsDev ns;                          /* the name sort (name_sort_host.h): ns.ord is the records in the names' order */
         /* the extract plan (fasta_extract_kernel.h): the host form's copy of the BED text, per slice, per line, per kept interval */
         DevBuf bed, bed_count, bed_first, bed_iv, bed_sorted, bed_keep, bed_pos, bed_lo, bed_hi, bed_rank, bed_clo, bed_chi, bed_max, bed_run, bed_scan,
             bed_stat, bed_tmp;
@@ -31,7 +34,6 @@ struct FastaState {
     int64_t n_items = 0;           /* items of the plan in dev.items */
     bool names_ready = false;      /* fa_name_table has run for this index */
     int32_t n_names = 0;
-    std::vector<int64_t> name_of;  /* record r's name in the table */
     std::vector<int64_t> file_ends; /* chunk: end of each output file in the output */
     int64_t out_bytes = 0;
 };
@@ -154,10 +156,11 @@ static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t
             for (int64_t r = 0; r < F.n_rec; r++) F.h_hdr_at[r + 1] = F.h_hdr_at[r] + F.h_recs[r].hdr_len;
             const int64_t blob = F.h_hdr_at[F.n_rec];
             F.h_hdr.resize((size_t)blob + 1);
+            /* the name sort reads both, empty headers or not; 16 bytes past the blob are allocated as past the other texts */
+            if (ensure(c, F.dev.hdr_off, sizeof(int64_t) * (size_t)F.n_rec)) return PAFFY_E_HIP;
+            if (ensure(c, F.dev.hdr_blob, (size_t)blob + 16)) return PAFFY_E_HIP;
+            HIPCHK(c, hipMemcpyAsync(F.dev.hdr_off.p, F.h_hdr_at.data(), sizeof(int64_t) * (size_t)F.n_rec, hipMemcpyHostToDevice, c->stream));
             if (blob) {
-                if (ensure(c, F.dev.hdr_off, sizeof(int64_t) * (size_t)F.n_rec)) return PAFFY_E_HIP;
-                if (ensure(c, F.dev.hdr_blob, (size_t)blob)) return PAFFY_E_HIP;
-                HIPCHK(c, hipMemcpyAsync(F.dev.hdr_off.p, F.h_hdr_at.data(), sizeof(int64_t) * (size_t)F.n_rec, hipMemcpyHostToDevice, c->stream));
                 LAUNCH(c, "k_fa_headers", k_fa_headers, dim3((unsigned)((F.n_rec + FA_NT / 64 - 1) / (FA_NT / 64))), dim3(FA_NT), 0, F.text,
                        static_cast<const FaRec *>(F.dev.recs.p), F.n_rec, static_cast<const int64_t *>(F.dev.hdr_off.p), static_cast<uint8_t *>(F.dev.hdr_blob.p));
                 HIPCHK(c, hipMemcpyAsync(F.h_hdr.data(), F.dev.hdr_blob.p, (size_t)blob, hipMemcpyDeviceToHost, c->stream));
@@ -178,9 +181,10 @@ static std::string fa_key(const FastaState &F, int64_t r) {
 
 /*
  * The table of the index's distinct names, once per index: dev.seen_names / dev.seen_off hold them sorted as find_seq expects (bytes,
- * then the shorter first), so a name's index is its strcmp rank; F.name_of[r] is record r's name. dev.name_rec[k] is the record a BED
+ * then the shorter first), so a name's index is its strcmp rank; dev.name_of[r] is record r's name. dev.name_rec[k] is the record a BED
  * line named k means: the last record whose whole header is that name (a header with a NUL byte is keyed up to it for to_bed -q, but
- * no BED token equals it), -1 where there is none. The sort is per FASTA record and stays on the host.
+ * no BED token equals it), -1 where there is none. Sorted and built on the device (name_sort_kernel.h); the host sees the number of
+ * names and the blob's size.
  */
 static int fa_name_table(paffy_hip_ctx *c, FastaState &F) {
     if (F.names_ready) return 0;
@@ -189,46 +193,30 @@ static int fa_name_table(paffy_hip_ctx *c, FastaState &F) {
         c->last_error = "the FASTA index has more than 2^31 - 2 records: no name table";
         return PAFFY_E_UNSUPPORTED;
     }
-    std::vector<std::string> key((size_t)n);
-    std::vector<int64_t> order((size_t)n);
-    F.name_of.assign((size_t)n, 0);
-    for (int64_t r = 0; r < n; r++) {
-        key[(size_t)r] = fa_key(F, r);
-        order[(size_t)r] = r;
+    FastaState::Dev &D = F.dev;
+    int rc = name_sort(c, D.ns, static_cast<const FaRec *>(D.recs.p), static_cast<const int64_t *>(D.hdr_off.p), static_cast<const uint8_t *>(D.hdr_blob.p), n);
+    if (rc) return rc;
+    uint64_t blob = 0;
+    if (n && (rc = name_sort_offsets(c, D.ns, n, true, &blob))) return rc;
+    if (blob >= 0xffffffffull) {
+        c->last_error = "the FASTA names pass 4 GiB";
+        return PAFFY_E_ARG;
     }
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        const std::string &x = key[(size_t)a], &y = key[(size_t)b];
-        const int d = memcmp(x.data(), y.data(), x.size() < y.size() ? x.size() : y.size());
-        if (d) return d < 0;
-        if (x.size() != y.size()) return x.size() < y.size();
-        return a < b; /* records of one name in input order: the last one is the last written below */
-    });
-    std::string blob;
-    std::vector<uint32_t> name_off;
-    std::vector<int64_t> name_rec;
-    for (int64_t k = 0; k < n; k++) {
-        const int64_t r = order[(size_t)k];
-        if (k == 0 || key[(size_t)r] != key[(size_t)order[(size_t)k - 1]]) {
-            name_off.push_back((uint32_t)blob.size());
-            name_rec.push_back(-1);
-            blob += key[(size_t)r];
-            if (blob.size() >= 0xffffffffull) {
-                c->last_error = "the FASTA names pass 4 GiB";
-                return PAFFY_E_ARG;
-            }
-        }
-        F.name_of[(size_t)r] = (int64_t)name_off.size() - 1;
-        if ((int64_t)key[(size_t)r].size() == F.h_hdr_at[r + 1] - F.h_hdr_at[r]) name_rec.back() = r;
-    }
-    F.n_names = (int32_t)name_off.size();
-    name_off.push_back((uint32_t)blob.size());
-    if (ensure(c, F.dev.seen_names, blob.size() + 16) || ensure(c, F.dev.seen_off, sizeof(uint32_t) * name_off.size()) ||
-        ensure(c, F.dev.name_rec, sizeof(int64_t) * (name_rec.size() + 1)))
+    F.n_names = (int32_t)D.ns.n_names;
+    if (ensure(c, D.seen_names, (size_t)blob + 16) || ensure(c, D.seen_off, sizeof(uint32_t) * ((size_t)F.n_names + 1)) ||
+        ensure(c, D.name_rec, sizeof(int64_t) * ((size_t)F.n_names + 1)) || ensure(c, D.name_of, sizeof(int32_t) * ((size_t)n + 1)))
         return PAFFY_E_HIP;
-    if (!blob.empty()) HIPCHK(c, hipMemcpyAsync(F.dev.seen_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(F.dev.seen_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, c->stream));
-    if (!name_rec.empty()) HIPCHK(c, hipMemcpyAsync(F.dev.name_rec.p, name_rec.data(), sizeof(int64_t) * name_rec.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream)); /* the copies read this frame's vectors */
+    if (n) {
+        HIPCHK(c, hipMemsetAsync(D.name_rec.p, 0xff, sizeof(int64_t) * (size_t)F.n_names, c->stream));
+        LAUNCH(c, "k_ns_names", k_ns_names, ns_grid((uint64_t)n), dim3(NS_NT), 0, (uint32_t)n, static_cast<const uint32_t *>(D.ns.ord.p),
+               static_cast<const uint32_t *>(D.ns.klen.p), static_cast<const int64_t *>(D.hdr_off.p), static_cast<const uint8_t *>(D.hdr_blob.p),
+               static_cast<const FaRec *>(D.recs.p), static_cast<const uint32_t *>(D.ns.flag.p), static_cast<const uint32_t *>(D.ns.nidx.p),
+               static_cast<const uint64_t *>(D.ns.off.p), static_cast<uint8_t *>(D.seen_names.p), static_cast<uint32_t *>(D.seen_off.p),
+               static_cast<int32_t *>(D.name_of.p), static_cast<long long *>(D.name_rec.p));
+    } else {
+        HIPCHK(c, hipMemsetAsync(D.seen_off.p, 0, sizeof(uint32_t), c->stream));
+    }
+    if (c->profile) prof_collect(c);
     F.names_ready = true;
     return 0;
 }
@@ -407,6 +395,27 @@ int paffy_hip_fasta_copy_bases(paffy_hip_ctx *c, int64_t first, int64_t n, void 
         return PAFFY_E_ARG;
     if (n) HIPCHK(c, hipMemcpyAsync(d_dst, static_cast<const uint8_t *>(c->fasta->dev.bases.p) + first, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int paffy_hip_fasta_name_order(paffy_hip_ctx *c, int64_t cap, void *d_order, void *d_name_of, int64_t *n_names) {
+    if (!c) return PAFFY_E_ARG;
+    if (!c->fasta || !c->fasta->indexed) return PAFFY_E_STATE;
+    FastaState &F = *c->fasta;
+    if (cap < F.n_rec) return PAFFY_E_CAPACITY;
+    const int rc = fa_name_table(c, F);
+    if (rc) return rc;
+    const size_t bytes = sizeof(int32_t) * (size_t)F.n_rec;
+    if (bytes && d_order) HIPCHK(c, hipMemcpyAsync(d_order, F.dev.ns.ord.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (bytes && d_name_of) HIPCHK(c, hipMemcpyAsync(d_name_of, F.dev.name_of.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_names) *n_names = F.n_names;
+    return 0;
+}
+
+int paffy_hip_name_sort_stats(paffy_hip_ctx *c, int64_t out[4]) {
+    if (!c || !out) return PAFFY_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = c->name_sort_stats[k];
     return 0;
 }
 

@@ -1104,6 +1104,7 @@ struct paffy_hip_ctx {
     const uint8_t *tile_in = nullptr;
     std::unique_ptr<ChainState> chain; /* `paffy chain` (chain_host.h) */
     std::unique_ptr<FastaState> fasta; /* `faffy chunk | extract | merge`: FASTA index and item plan (fasta_host.h) */
+    int64_t name_sort_stats[4] = {0, 0, 0, 0}; /* the last name sort (name_sort_host.h): records, rounds, records tied after the first round, distinct names */
     std::unique_ptr<CovState> cov; /* `paffy tile` / `paffy to_bed` over any number of batches (coverage_host.h) */
     /* the batch paffy_hip_query_names indexed last: paffy_hip_split_by_owner on the same batch reuses the index (one use) */
     const void *indexed_in = nullptr;

@@ -28,18 +28,25 @@ static int seq_store_from_index(paffy_hip_ctx *c, FastaState &F) {
         c->last_error = "sequence store: more than 2^31 - 1 records";
         return PAFFY_E_ARG;
     }
-    std::vector<std::string> names((size_t)n);
-    std::vector<const char *> ptr((size_t)n);
-    std::vector<int64_t> lens((size_t)n), offs((size_t)n);
-    for (int64_t r = 0; r < n; r++) {
-        names[(size_t)r] = fa_key(F, r);
-        ptr[(size_t)r] = names[(size_t)r].c_str();
-        lens[(size_t)r] = F.h_recs[(size_t)r].seq_len;
-        offs[(size_t)r] = F.h_recs[(size_t)r].seq_off;
-    }
-    std::vector<uint64_t> blob_off;
-    int rc = seq_store_layout(c, n, ptr.data(), lens.data(), blob_off, offs.data());
+    /* the store's tables as seq_store_layout lays them out over the compact bases: all n keys in find_seq's order (name_sort_kernel.h),
+       records of one name in input order */
+    c->n_seqs = 0;
+    FastaState::Dev &D = F.dev;
+    int rc = name_sort(c, D.ns, static_cast<const FaRec *>(D.recs.p), static_cast<const int64_t *>(D.hdr_off.p), static_cast<const uint8_t *>(D.hdr_blob.p), n);
     if (rc) return rc;
+    uint64_t blob = 0;
+    if ((rc = name_sort_offsets(c, D.ns, n, false, &blob))) return rc;
+    if (blob >= 0xffffffffull) { /* seq_name_off is 32-bit */
+        c->last_error = "sequence store: the names pass 4 GiB";
+        return PAFFY_E_ARG;
+    }
+    if (ensure(c, c->seq_table, sizeof(SeqEntry) * (size_t)n) || ensure(c, c->seq_names, (size_t)blob + 16) ||
+        ensure(c, c->seq_name_off, sizeof(uint32_t) * ((size_t)n + 1)))
+        return PAFFY_E_HIP;
+    LAUNCH(c, "k_ns_store", k_ns_store, ns_grid((uint64_t)n), dim3(NS_NT), 0, (uint32_t)n, static_cast<const uint32_t *>(D.ns.ord.p),
+           static_cast<const uint32_t *>(D.ns.klen.p), static_cast<const int64_t *>(D.hdr_off.p), static_cast<const uint8_t *>(D.hdr_blob.p),
+           static_cast<const FaRec *>(D.recs.p), static_cast<const uint64_t *>(D.ns.off.p), static_cast<uint8_t *>(c->seq_names.p),
+           static_cast<uint32_t *>(c->seq_name_off.p), static_cast<SeqEntry *>(c->seq_table.p));
     std::swap(c->seq_blob, F.dev.bases); /* the compact bases are the store; the old store goes with F */
     return seq_store_fill(c, F.n_bases);
 }
@@ -102,18 +109,21 @@ int paffy_hip_fasta_seen(paffy_hip_ctx *c, const void *d_paf, int64_t paf_len, i
         if (rc) return rc;
     }
     const int32_t n_names = F.n_names;
-    std::vector<uint8_t> flag((size_t)n_names, 0);
-    if (paf_len > 0) {
-        if (ensure(c, F.dev.seen, (size_t)n_names)) return PAFFY_E_HIP;
-        HIPCHK(c, hipMemsetAsync(F.dev.seen.p, 0, (size_t)n_names, c->stream));
-        const int64_t blocks = (paf_len + FA_TILE - 1) / FA_TILE;
-        LAUNCH(c, "k_fa_seen", k_fa_seen, dim3((unsigned)blocks), dim3(FA_NT), 0, static_cast<const uint8_t *>(d_paf), paf_len, with_target ? 1 : 0,
-               static_cast<const uint8_t *>(F.dev.seen_names.p), static_cast<const uint32_t *>(F.dev.seen_off.p), n_names, static_cast<uint8_t *>(F.dev.seen.p));
-        HIPCHK(c, hipMemcpyAsync(flag.data(), F.dev.seen.p, (size_t)n_names, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->profile) prof_collect(c);
+    if (paf_len == 0) {
+        memset(seen, 0, (size_t)n);
+        return 0;
     }
-    for (int64_t r = 0; r < n; r++) seen[r] = flag[(size_t)F.name_of[(size_t)r]];
+    if (ensure(c, F.dev.seen, (size_t)n_names) || ensure(c, F.dev.seen_rec, (size_t)n)) return PAFFY_E_HIP;
+    HIPCHK(c, hipMemsetAsync(F.dev.seen.p, 0, (size_t)n_names, c->stream));
+    const int64_t blocks = (paf_len + FA_TILE - 1) / FA_TILE;
+    LAUNCH(c, "k_fa_seen", k_fa_seen, dim3((unsigned)blocks), dim3(FA_NT), 0, static_cast<const uint8_t *>(d_paf), paf_len, with_target ? 1 : 0,
+           static_cast<const uint8_t *>(F.dev.seen_names.p), static_cast<const uint32_t *>(F.dev.seen_off.p), n_names, static_cast<uint8_t *>(F.dev.seen.p));
+    /* every record gets its name's flag on the device: n bytes come back */
+    LAUNCH(c, "k_ns_seen", k_ns_seen, ns_grid((uint64_t)n), dim3(NS_NT), 0, (uint32_t)n, static_cast<const int32_t *>(F.dev.name_of.p),
+           static_cast<const uint8_t *>(F.dev.seen.p), static_cast<uint8_t *>(F.dev.seen_rec.p));
+    HIPCHK(c, hipMemcpyAsync(seen, F.dev.seen_rec.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profile) prof_collect(c);
     return 0;
 }
 

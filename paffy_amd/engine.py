@@ -224,6 +224,9 @@ def lib():
         L.paffy_hip_set_intervals_fasta.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64)]
         L.paffy_hip_fasta_index_headers.argtypes = [vp, vp, i64, C.POINTER(i64), i32, C.POINTER(i64)]
         L.paffy_hip_fasta_seen.argtypes = [vp, vp, i64, C.c_int, C.POINTER(C.c_uint8)]
+        if hasattr(L, "paffy_hip_fasta_name_order"):  # an older library under PAFFY_HIP_LIB has neither: the calls then raise
+            L.paffy_hip_fasta_name_order.argtypes = [vp, i64, vp, vp, C.POINTER(i64)]
+            L.paffy_hip_name_sort_stats.argtypes = [vp, C.POINTER(i64)]
         L.paffy_hip_keep_raw_sequences.argtypes = [vp, C.c_int]
         L.paffy_hip_stats_only.argtypes = [vp, C.c_int]
         L.paffy_hip_plan_record_stats.restype = i64
@@ -1091,7 +1094,7 @@ class Engine:
         n = len(file_starts)
         st = (C.c_int64 * max(1, n))(*[int(x) for x in file_starts])
         n_rec, n_bases = C.c_int64(), C.c_int64()
-        self._fasta_text = d_text
+        self._fasta_d_text = d_text  # kept alive with the index (not under the name of the _fasta_text method below)
         self._check(lib().paffy_hip_fasta_index(self._ctx, C.c_void_p(d_text.data_ptr()), text_len, st, n, C.byref(n_rec), C.byref(n_bases)),
                     "paffy_hip_fasta_index")
         return n_rec.value, n_bases.value
@@ -1180,6 +1183,26 @@ class Engine:
             name = data[h:h + hl].split(b"\0", 1)[0]
             out.append((name, sl, bool(seen[k])))
         return out
+
+    def fasta_name_order(self):
+        """The names of the context's FASTA index as the name tables order them (bytes, then the shorter first, then the input index),
+        sorted on the device: (order, name_of, n_names) with order[k] = the record at place k and name_of[r] = the index of record r's
+        name among the distinct names, both lists of int."""
+        n = lib().paffy_hip_fasta_records(self._ctx, 0, 0, None)
+        if n < 0:
+            self._check(n, "paffy_hip_fasta_records")
+        d = self.torch.zeros((2, max(1, n)), dtype=self.torch.int32, device=self.device)
+        n_names = C.c_int64()
+        rc = lib().paffy_hip_fasta_name_order(self._ctx, n, C.c_void_p(d[0].data_ptr()), C.c_void_p(d[1].data_ptr()), C.byref(n_names))
+        self._check(rc, "paffy_hip_fasta_name_order")
+        h = d[:, :n].cpu().numpy()
+        return h[0].tolist(), h[1].tolist(), n_names.value
+
+    def name_sort_stats(self):
+        """The context's last name sort: {records, rounds, tied_after_first, names}."""
+        out = (C.c_int64 * 4)()
+        self._check(lib().paffy_hip_name_sort_stats(self._ctx, out), "paffy_hip_name_sort_stats")
+        return {"records": out[0], "rounds": out[1], "tied_after_first": out[2], "names": out[3]}
 
     def fasta_records(self, files):
         """FASTA files (bytes each) -> [(header, bases)] as the device index reads them."""

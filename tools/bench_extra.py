@@ -69,7 +69,8 @@ def main():
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
     ap.add_argument("--sha256", action="store_true", help="faffy_*: copy the last repetition's output to the host and print its SHA-256")
     ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome")
-    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the plan (the smallest counts)")
+    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the plan (the smallest counts); seqload, faffy_*: repetitions, the first warms up")
+    ap.add_argument("--skip-host-strings", action="store_true", help="seqload: do not time paffy_hip_set_sequences on the records as host strings")
     ap.add_argument("--sha", action="store_true", help="add_trim, add_filter: copy the last repetition's output to the host and print its SHA-256")
     ap.add_argument("--parts", type=int, default=0, help="chain: chain in parts -- this many contexts on the one GPU, taken in turn (0: the plain one-context run)")
     ap.add_argument("--fresh-walk", action="store_true", help="chain: with paffy_hip_chain_fresh_walk on (the reference's walk from a fresh iterator)")
@@ -401,9 +402,9 @@ def faffy_bench(a):
     print(f"{a.cmd}: input of {nbytes / 1e9:.2f} GB resident in HBM ({time.perf_counter() - t0:.1f} s to generate)", file=sys.stderr)
     res, plan = [], []
     out = None
-    for rep in range(3):
+    for rep in range(max(2, a.repeats)):
         if rep == 1:
-            eng.profile(True)  # the first repetition warms up; kernel figures from the other two
+            eng.profile(True)  # the first repetition warms up; kernel figures from the others
         t0 = time.perf_counter()
         n_rec, n_bases = eng.fasta_index(text, nbytes, starts)
         info = E.PlanInfo()
@@ -426,7 +427,7 @@ def faffy_bench(a):
     kernel_ms = {k: round(ms / max(1, cnt), 3) for k, (ms, cnt) in prof.items()}
     total_ms = sum(kernel_ms.values())
     moved = nbytes + int(info.out_bytes)
-    extra = {}
+    extra = name_sort_figures(eng, prof, len(res) - 1) if a.cmd == "faffy_extract" else {}
     if a.sha256:
         import hashlib
 
@@ -443,9 +444,20 @@ def faffy_bench(a):
     eng.close()
 
 
+def name_sort_figures(eng, prof, reps):
+    """The device name sort's share of the profiled repetitions (its kernels and the rocPRIM sorts and scans between them: the k_ns_* and
+    ns_* rows, summed per repetition) and what the last sort took; nothing under a library that has no name sort."""
+    from paffy_amd import engine as E
+
+    if not hasattr(E.lib(), "paffy_hip_name_sort_stats"):
+        return {}
+    ms = sum(v[0] for k, v in prof.items() if k.startswith(("k_ns_", "ns_")))
+    return {"name_sort_ms_per_repetition": round(ms / max(1, reps), 3), "name_sort_stats": eng.name_sort_stats()}
+
+
 def seqload_bench(a):
     """The sequence store of add_mismatches / view from FASTA text: paffy_hip_set_sequences_fasta on text resident in HBM (index + store
-    kernels, names sorted on the host) against paffy_hip_set_sequences on the same records held as host strings (one copy per record +
+    kernels, names sorted on the device: the k_ns_* and ns_* rows) against paffy_hip_set_sequences on the same records held as host strings (one copy per record +
     k_seq_canon; the host parse of the former CLI path is not included). The text is freed by neither call."""
     import ctypes as C
 
@@ -475,7 +487,7 @@ def seqload_bench(a):
     st = (C.c_int64 * 1)(0)
     n_rec = C.c_int64()
     new = []
-    for rep in range(3):
+    for rep in range(max(2, a.repeats)):
         if rep == 1:
             eng.profile(True)
         t0 = time.perf_counter()
@@ -485,6 +497,12 @@ def seqload_bench(a):
     prof = {k: (v[0], v[1]) for k, v in eng.profile_read().items()}
     eng.profile(False)
     kernel_ms = {k: round(ms / max(1, cnt), 3) for k, (ms, cnt) in prof.items()}
+    extra = name_sort_figures(eng, prof, len(new) - 1)
+    if a.skip_host_strings:
+        print(json.dumps({"cmd": "seqload", "text_bytes": nbytes, "records": n_rec.value, "seconds_set_sequences_fasta": round(min(new[1:]), 4),
+                          "seconds_set_sequences_fasta_all": [round(x, 4) for x in new], **extra, "kernel_ms": kernel_ms}))
+        eng.close()
+        return
     # the records as host strings (what the former host parse produced), then the host-string call
     recs = eng.fasta_records([bytes(text[:nbytes].cpu().numpy().tobytes())]) if a.scaffolds else None
     if recs is None:
@@ -512,7 +530,7 @@ def seqload_bench(a):
     moved = 3 * n_bases  # k_seq_store: the bases read once, written upper-cased and complemented (no raw copy here)
     print(json.dumps({"cmd": "seqload", "text_bytes": nbytes, "records": n_rec.value, "bases": n_bases,
                       "seconds_set_sequences_fasta": round(min(new[1:]), 4), "seconds_set_sequences_host_strings": round(min(old[1:]), 4),
-                      "kernel_ms": kernel_ms, "k_seq_store_GBps": round(moved / (store_ms / 1e3) / 1e9, 1) if store_ms else None,
+                      "seconds_set_sequences_fasta_all": [round(x, 4) for x in new], **extra, "kernel_ms": kernel_ms, "k_seq_store_GBps": round(moved / (store_ms / 1e3) / 1e9, 1) if store_ms else None,
                       "k_seq_store_fraction_of_8TBps": round(moved / (store_ms / 1e3) / 8e12, 3) if store_ms else None}))
     eng.close()
 
