@@ -660,13 +660,22 @@ int paffy_hip_fasta_copy_bases(paffy_hip_ctx *ctx, int64_t first, int64_t n, voi
  * returns; n_records (may be NULL) gets the number of FASTA records.
  * set_sequences_fasta: the store paffy_hip_set_sequences builds from the same records (names = the headers up to a NUL byte, in input
  *   order), with the raw copy under paffy_hip_keep_raw_sequences; the bases never leave the device.
- * set_intervals_fasta: paffy_hip_set_intervals over the records' headers and sequence lengths (PAFFY_E_HEADER as there).
+ * set_intervals_fasta: the table paffy_hip_set_intervals makes of the records' headers (up to a NUL byte) and sequence lengths, built on
+ *   the device: the headers are decoded, sorted by (name, start, input index) and printed there, and never come to the host
+ *   (PAFFY_E_HEADER, with no intervals, as there; n_records is set all the same).
  */
 int paffy_hip_set_sequences_fasta(paffy_hip_ctx *ctx, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records);
 int paffy_hip_set_intervals_fasta(paffy_hip_ctx *ctx, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records);
 /* paffy_hip_fasta_index without the compact base buffer (record table and headers only; the faffy plans and copy_bases then refuse) */
 int paffy_hip_fasta_index_headers(paffy_hip_ctx *ctx, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files,
                                   int64_t *n_records);
+/* the interval table of the context as upconvert searches it. out[0] intervals, out[1] bytes of the names blob,
+   out[2] 1 when the last table was built on the device (set_intervals_fasta), 0 from host strings (set_intervals),
+   out[3] name-sort rounds of that build (0 for host strings); zeros before the first table */
+int paffy_hip_intervals_info(paffy_hip_ctx *ctx, int64_t out[4]);
+/* copies the table to host memory: nums[3k..3k+2] = start, end, length; slices[4k..4k+3] = name_off, name_len, out_off, out_len;
+   blob = the names. PAFFY_E_CAPACITY when cap < intervals or blob_cap < blob bytes; any pointer may be NULL */
+int paffy_hip_intervals_read(paffy_hip_ctx *ctx, int64_t cap, int64_t blob_cap, int64_t *nums, uint32_t *slices, void *blob);
 /* to_bed -q: seen[r] (host, one byte per record of the context's index) = 1 when a line of the PAF text d_paf (16-byte aligned, readable
    to the next multiple of 16) names record r's header (up to a NUL byte) as its query -- the bytes before its first tab -- or, with
    with_target, as its target -- between its fifth and sixth tab --, else 0. One device lookup per line in the sorted distinct names. */
@@ -680,8 +689,9 @@ int paffy_hip_fasta_seen(paffy_hip_ctx *ctx, const void *d_paf, int64_t paf_len,
  * PAFFY_E_CAPACITY when cap < the index's records.
  */
 int paffy_hip_fasta_name_order(paffy_hip_ctx *ctx, int64_t cap, void *d_order, void *d_name_of, int64_t *n_names);
-/* the last name sort of the context, whichever call ran it (name_order, fasta_seen, the extract plan, set_sequences_fasta): out[0] records,
-   out[1] rounds, out[2] records still tied after the first round, out[3] distinct names; zeros before the first */
+/* the last name sort of the context, whichever call ran it (name_order, fasta_seen, the extract plan, set_sequences_fasta,
+   set_intervals_fasta, whose keys are the decoded names): out[0] records, out[1] rounds, out[2] records still tied after the first round,
+   out[3] distinct names; zeros before the first */
 int paffy_hip_name_sort_stats(paffy_hip_ctx *ctx, int64_t out[4]);
 /*
  * Plans over the index: info->out_bytes, info->n_rows (items), info->error (PAFFY_ERR_FAFFY_*: nothing is to be written; record = the

@@ -109,8 +109,10 @@ static int fa_plan_end(paffy_hip_ctx *c, paffy_plan_info *info) {
 }
 
 /* The index of the text into F (the context's state, or one of a loader's own). with_bases = false: the record table and the headers
-   only; the compact base buffer is neither allocated nor written (upconvert and to_bed -q need the lengths alone). */
-static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, bool with_bases) {
+   only; the compact base buffer is neither allocated nor written (upconvert and to_bed -q need the lengths alone). host_headers = false:
+   the header blob stays on the device (dev.hdr_blob) and h_hdr is left empty, for a caller that reads the headers there. */
+static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, bool with_bases,
+                    bool host_headers = true) {
     if (!c || text_len < 0 || (text_len > 0 && !d_text) || (reinterpret_cast<uintptr_t>(d_text) & 15u)) return PAFFY_E_ARG;
     if (n_files < 0 || (n_files > 0 && !file_starts)) return PAFFY_E_ARG;
     std::vector<int64_t> starts(file_starts, file_starts + n_files);
@@ -155,7 +157,7 @@ static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t
             F.h_hdr_at.resize((size_t)F.n_rec + 1);
             for (int64_t r = 0; r < F.n_rec; r++) F.h_hdr_at[r + 1] = F.h_hdr_at[r] + F.h_recs[r].hdr_len;
             const int64_t blob = F.h_hdr_at[F.n_rec];
-            F.h_hdr.resize((size_t)blob + 1);
+            if (host_headers) F.h_hdr.resize((size_t)blob + 1);
             /* the name sort reads both, empty headers or not; 16 bytes past the blob are allocated as past the other texts */
             if (ensure(c, F.dev.hdr_off, sizeof(int64_t) * (size_t)F.n_rec)) return PAFFY_E_HIP;
             if (ensure(c, F.dev.hdr_blob, (size_t)blob + 16)) return PAFFY_E_HIP;
@@ -163,7 +165,7 @@ static int fa_index(paffy_hip_ctx *c, FastaState &F, const void *d_text, int64_t
             if (blob) {
                 LAUNCH(c, "k_fa_headers", k_fa_headers, dim3((unsigned)((F.n_rec + FA_NT / 64 - 1) / (FA_NT / 64))), dim3(FA_NT), 0, F.text,
                        static_cast<const FaRec *>(F.dev.recs.p), F.n_rec, static_cast<const int64_t *>(F.dev.hdr_off.p), static_cast<uint8_t *>(F.dev.hdr_blob.p));
-                HIPCHK(c, hipMemcpyAsync(F.h_hdr.data(), F.dev.hdr_blob.p, (size_t)blob, hipMemcpyDeviceToHost, c->stream));
+                if (host_headers) HIPCHK(c, hipMemcpyAsync(F.h_hdr.data(), F.dev.hdr_blob.p, (size_t)blob, hipMemcpyDeviceToHost, c->stream));
             }
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));

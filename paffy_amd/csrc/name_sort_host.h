@@ -69,9 +69,11 @@ static dim3 ns_grid(uint64_t n) { return dim3((unsigned)((n + NS_NT - 1) / NS_NT
 /*
  * The order of n records' keys (n < 2^31): D.ord[k] is the record at place k, D.flag[k] = 1 where the key differs from the one before it,
  * D.nidx its inclusive sum, D.n_names the distinct keys. hdr_off / blob: the headers back to back as fa_index leaves them.
+ * key_len (device, one per record; may be null): the keys' lengths where they are not the headers up to a NUL byte but prefixes of those.
  * The context's name_sort_stats tell what it took.
  */
-static int name_sort(paffy_hip_ctx *c, NsDev &D, const FaRec *recs, const int64_t *hdr_off, const uint8_t *blob, int64_t n_rec) {
+static int name_sort(paffy_hip_ctx *c, NsDev &D, const FaRec *recs, const int64_t *hdr_off, const uint8_t *blob, int64_t n_rec,
+                     const uint32_t *key_len = nullptr) {
     const uint32_t n = (uint32_t)n_rec;
     D.n_names = 0;
     c->name_sort_stats[0] = n_rec;
@@ -90,7 +92,7 @@ static int name_sort(paffy_hip_ctx *c, NsDev &D, const FaRec *recs, const int64_
     uint64_t *word = static_cast<uint64_t *>(D.word.p), *word_s = static_cast<uint64_t *>(D.word_s.p);
     NsScan *scan_in = static_cast<NsScan *>(D.scan_in.p), *scan_out = static_cast<NsScan *>(D.scan_out.p);
     const dim3 block(NS_NT);
-    LAUNCH(c, "k_ns_init", k_ns_init, ns_grid(n), block, 0, recs, hdr_off, blob, n, klen, ord, flag, U32(D.pos[0]), U32(D.run[0]), U32(D.depth[0]), skip);
+    LAUNCH(c, "k_ns_init", k_ns_init, ns_grid(n), block, 0, recs, hdr_off, blob, key_len, n, klen, ord, flag, U32(D.pos[0]), U32(D.run[0]), U32(D.depth[0]), skip);
     uint32_t m = n >= 2u ? n : 0u; /* a run of one record is resolved */
     int64_t rounds = 0;
     int cur = 0;

@@ -1,7 +1,8 @@
 /*
  * name_sort_kernel.h -- the FASTA names of an index in find_seq's order, sorted on the device.
  *
- * Key. Record r's key is its header up to the first NUL byte, so a key holds no NUL. Keys order by unsigned bytes, then the shorter first,
+ * Key. Record r's key is its header up to the first NUL byte, so a key holds no NUL (a caller may give shorter keys: prefixes of that
+ * one, as the upconvert interval table's names are). Keys order by unsigned bytes, then the shorter first,
  * then the record's input index.
  *
  * Rounds over runs. A run is a stretch of the current order whose members are equal in every byte before its depth d; it is named by the
@@ -58,17 +59,22 @@ __device__ __forceinline__ T ns_seg_reduce(T v, uint32_t key, bool &is_first) {
     return v;
 }
 
-/* per record: the key length (saturated: a key of 4 GiB fails the blob's limit on the host); the start of the sort: input order, one run
-   at depth 0. */
-__global__ __launch_bounds__(NS_NT) void k_ns_init(const FaRec *recs, const int64_t *hdr_off, const uint8_t *blob, uint32_t n, uint32_t *klen, uint32_t *ord,
-                                                   uint32_t *flag, uint32_t *pos, uint32_t *run, uint32_t *depth, uint32_t *run_skip) {
+/* per record: the key length (saturated: a key of 4 GiB fails the blob's limit on the host), or key_len[r] where the caller has one (a
+   prefix of the header that holds no NUL: upconvert_build_kernel.h); the start of the sort: input order, one run at depth 0. */
+__global__ __launch_bounds__(NS_NT) void k_ns_init(const FaRec *recs, const int64_t *hdr_off, const uint8_t *blob, const uint32_t *key_len, uint32_t n,
+                                                   uint32_t *klen, uint32_t *ord, uint32_t *flag, uint32_t *pos, uint32_t *run, uint32_t *depth,
+                                                   uint32_t *run_skip) {
     const uint32_t r = blockIdx.x * NS_NT + threadIdx.x;
     if (r >= n) return;
-    const int64_t hl = recs[r].hdr_len;
-    const uint8_t *p = blob + hdr_off[r];
-    int64_t k = 0;
-    while (k < hl && p[k]) k++;
-    klen[r] = k < (int64_t)NS_NONE ? (uint32_t)k : NS_NONE;
+    if (key_len) {
+        klen[r] = key_len[r];
+    } else {
+        const int64_t hl = recs[r].hdr_len;
+        const uint8_t *p = blob + hdr_off[r];
+        int64_t k = 0;
+        while (k < hl && p[k]) k++;
+        klen[r] = k < (int64_t)NS_NONE ? (uint32_t)k : NS_NONE;
+    }
     ord[r] = r;
     flag[r] = r == 0u ? 1u : 0u;
     pos[r] = r;

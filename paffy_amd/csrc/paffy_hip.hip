@@ -1132,6 +1132,11 @@ struct paffy_hip_ctx {
     /* upconvert (paffy_hip_set_intervals): the FASTA intervals sorted by (name, start), their names and output names in one blob */
     DevBuf up_table, up_names;
     uint32_t n_intervals = 0;
+    /* paffy_hip_intervals_info: the bytes of up_names in use, whether the device built the table (upconvert_build_host.h) and the rounds
+       of that build's name sort */
+    uint64_t up_blob_bytes = 0;
+    bool up_on_device = false;
+    int64_t up_rounds = 0;
     DevInfo *h_info = nullptr; /* pinned */
     /* plan state (plan_begin clears it) */
     bool planned = false;
@@ -2894,6 +2899,9 @@ static int up_cmp_intervals(const void *i, const void *j) { /* cmp_intervals, im
 int paffy_hip_set_intervals(paffy_hip_ctx *c, const char *const *headers, const int64_t *seq_lens, int64_t n) {
     if (!c || n < 0 || n >= (1ll << 31) || (n > 0 && (!headers || !seq_lens))) return PAFFY_E_ARG;
     c->n_intervals = 0;
+    c->up_blob_bytes = 0;
+    c->up_on_device = false;
+    c->up_rounds = 0;
     std::vector<UpHost> iv((size_t)n);
     for (int64_t i = 0; i < n; i++) {
         if (!headers[i] || !up_decode(headers[i], iv[(size_t)i].name, iv[(size_t)i].start, iv[(size_t)i].length)) {
@@ -2931,6 +2939,7 @@ int paffy_hip_set_intervals(paffy_hip_ctx *c, const char *const *headers, const 
         if (!blob.empty()) HIPCHK(c, hipMemcpy(c->up_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
     }
     c->n_intervals = (uint32_t)n;
+    c->up_blob_bytes = blob.size();
     return 0;
 }
 

@@ -1,9 +1,11 @@
 /*
- * seqload_host.h -- FASTA files in HBM to the sequence store (add_mismatches, view), the upconvert intervals and the to_bed -q name query
+ * seqload_host.h -- FASTA files in HBM to the sequence store (add_mismatches, view), the upconvert intervals (built by upconvert_build_host.h) and the to_bed -q name query
  * (include/paffy_hip.h). The text is indexed by fa_index (fasta_host.h) into a state of the loader's own, so a faffy index
  * of the context is left alone, and that state is freed before the call returns. Included at the end of paffy_hip.hip.
  */
 #pragma once
+
+#include "upconvert_build_host.h"
 
 /* seq_blob holds the bases (input order) from n_bases on: upper case, complement and the raw copy in one pass */
 static int seq_store_fill(paffy_hip_ctx *c, int64_t n_bases) {
@@ -70,20 +72,10 @@ int paffy_hip_set_intervals_fasta(paffy_hip_ctx *c, const void *d_text, int64_t 
     if (!c) return PAFFY_E_ARG;
     c->n_intervals = 0;
     FastaState F;
-    int rc = fa_index(c, F, d_text, text_len, file_starts, n_files, false);
-    fasta_release(F); /* the host copy of the table and the headers is all that is needed */
+    int rc = fa_index(c, F, d_text, text_len, file_starts, n_files, false, false); /* the headers stay on the device: the table is built there */
     if (rc) return rc;
-    const int64_t n = F.n_rec;
-    std::vector<std::string> hdr((size_t)n);
-    std::vector<const char *> ptr((size_t)n);
-    std::vector<int64_t> lens((size_t)n);
-    for (int64_t r = 0; r < n; r++) {
-        hdr[(size_t)r] = fa_key(F, r);
-        ptr[(size_t)r] = hdr[(size_t)r].c_str();
-        lens[(size_t)r] = F.h_recs[(size_t)r].seq_len;
-    }
-    if (n_records) *n_records = n;
-    return paffy_hip_set_intervals(c, ptr.data(), lens.data(), n);
+    if (n_records) *n_records = F.n_rec;
+    return upconvert_build(c, F);
 }
 
 int paffy_hip_fasta_index_headers(paffy_hip_ctx *c, const void *d_text, int64_t text_len, const int64_t *file_starts, int32_t n_files, int64_t *n_records) {

@@ -227,6 +227,9 @@ def lib():
         if hasattr(L, "paffy_hip_fasta_name_order"):  # an older library under PAFFY_HIP_LIB has neither: the calls then raise
             L.paffy_hip_fasta_name_order.argtypes = [vp, i64, vp, vp, C.POINTER(i64)]
             L.paffy_hip_name_sort_stats.argtypes = [vp, C.POINTER(i64)]
+        if hasattr(L, "paffy_hip_intervals_info"):  # an older library under PAFFY_HIP_LIB has neither: the calls then raise
+            L.paffy_hip_intervals_info.argtypes = [vp, C.POINTER(i64)]
+            L.paffy_hip_intervals_read.argtypes = [vp, i64, i64, C.POINTER(i64), C.POINTER(C.c_uint32), vp]
         L.paffy_hip_keep_raw_sequences.argtypes = [vp, C.c_int]
         L.paffy_hip_stats_only.argtypes = [vp, C.c_int]
         L.paffy_hip_plan_record_stats.restype = i64
@@ -1163,6 +1166,28 @@ class Engine:
         """Intervals for UPCONVERT from FASTA files (paths, or bytes each) read on the device, as `paffy upconvert a.fa b.fa` loads them;
         returns the number of records. A header that does not decode raises (the reference aborts)."""
         return self._load_fasta(lib().paffy_hip_set_intervals_fasta, files, "paffy_hip_set_intervals_fasta")
+
+    def intervals_info(self):
+        """The context's interval table (set_intervals or set_intervals_fasta): {intervals, blob_bytes, on_device, rounds}; on_device is 1
+        when the device built it, rounds are that build's name-sort rounds."""
+        out = (C.c_int64 * 4)()
+        self._check(lib().paffy_hip_intervals_info(self._ctx, out), "paffy_hip_intervals_info")
+        return {"intervals": out[0], "blob_bytes": out[1], "on_device": out[2], "rounds": out[3]}
+
+    def intervals(self):
+        """The interval table as upconvert searches it: [(name, start, end, length, out_name)] in table order."""
+        info = self.intervals_info()
+        n, nb = info["intervals"], info["blob_bytes"]
+        nums = (C.c_int64 * max(1, 3 * n))()
+        slices = (C.c_uint32 * max(1, 4 * n))()
+        blob = C.create_string_buffer(max(1, nb))
+        self._check(lib().paffy_hip_intervals_read(self._ctx, n, nb, nums, slices, blob), "paffy_hip_intervals_read")
+        raw = blob.raw
+        out = []
+        for k in range(n):
+            no, nl, oo, ol = slices[4 * k:4 * k + 4]
+            out.append((raw[no:no + nl], nums[3 * k], nums[3 * k + 1], nums[3 * k + 2], raw[oo:oo + ol]))
+        return out
 
     def fasta_seen(self, files, paf, with_target=False):
         """`paffy to_bed -q`'s query: [(name, sequence length, named)] per FASTA record, named = a line of the PAF text names it as its

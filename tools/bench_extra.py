@@ -61,15 +61,17 @@ def main():
     ap.add_argument("--mean-ops", type=int, default=2048)
     ap.add_argument("--contigs", type=int, default=24, help="contigs of the synthetic stream (chain: fewer contigs = larger groups)")
     ap.add_argument("--cmd", default="tile", choices=["tile", "invert", "trim", "trimf", "trimf_invert", "trimf_filter", "trimf_stats", "shatter", "remove", "remove_eqx", "filter", "add", "add_trim", "add_filter", "view", "view_stats_only", "view_lines", "dedupe", "bed", "stats", "chain",
-                                                    "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload", "invert_trim_shatter"])
+                                                    "dechunk", "upconvert", "pass", "faffy_chunk", "faffy_extract", "faffy_merge", "seqload", "ivload", "invert_trim_shatter"])
     ap.add_argument("--names", default="std", choices=["std", "short"],
                     help="shatter, invert_trim_shatter: `short` renames hs.chrN / pt.chrN to chrN on the host (outside the timed region): chr1-chr9 "
                          "then have a first row piece of 15 bytes, chr10-chr24 one of 16 -- about half and half, like a human assembly")
     ap.add_argument("--genome-gb", type=float, default=3.1, help="faffy_*: bases of the synthetic genome (24 contigs)")
     ap.add_argument("--intervals", type=int, default=1_000_000, help="faffy_extract: BED intervals")
     ap.add_argument("--sha256", action="store_true", help="faffy_*: copy the last repetition's output to the host and print its SHA-256")
-    ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome")
-    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the plan (the smallest counts); seqload, faffy_*: repetitions, the first warms up")
+    ap.add_argument("--scaffolds", type=int, default=0, help="seqload: an assembly of this many scaffolds (1-2000 bases) instead of the genome; ivload: this many chunk records "
+                                                                  "scaf<i>|<len>|<start> (1-200 bases) instead of the genome's 24 contigs")
+    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the plan (the smallest counts); seqload, faffy_*: repetitions, the first warms up; ivload: "
+                                                                "the same, the median counts, and one more repetition under the profile")
     ap.add_argument("--skip-host-strings", action="store_true", help="seqload: do not time paffy_hip_set_sequences on the records as host strings")
     ap.add_argument("--sha", action="store_true", help="add_trim, add_filter: copy the last repetition's output to the host and print its SHA-256")
     ap.add_argument("--parts", type=int, default=0, help="chain: chain in parts -- this many contexts on the one GPU, taken in turn (0: the plain one-context run)")
@@ -85,6 +87,8 @@ def main():
         return faffy_bench(a)
     if a.cmd == "seqload":
         return seqload_bench(a)
+    if a.cmd == "ivload":
+        return ivload_bench(a)
     import torch
 
     import paffy_amd
@@ -323,14 +327,14 @@ def chain_parts_bench(a):
                       "GBps": round((nbytes + res["total"]) / dt / 1e9, 1), "kernel_ms_all_parts_per_run": {k: round(ms / max(1, cnt), 3) for k, (ms, cnt) in prof.items()}}))
 
 
-def synth_genome(torch, dev, gb, n_contigs=24, seed=0x5EED00FA):
+def synth_genome(torch, dev, gb, n_contigs=24, seed=0x5EED00FA, chunk_headers=False):
     """a seeded genome written as FASTA text on the device: 60-column lines, mixed case, runs of N (about 2 % of the lines);
-    returns (text tensor, text bytes, [(name, length)])"""
+    returns (text tensor, text bytes, [(name, length)]). chunk_headers: every contig is named as the chunk chr<k>|<length>|0 of itself"""
     g = torch.Generator(device=dev)
     g.manual_seed(seed)
     w = torch.rand(n_contigs, generator=g, device=dev).cpu() + 0.5
     lens = [int(x) for x in (w / w.sum() * gb * 1e9).tolist()]
-    heads = [b">chr%d\n" % k for k in range(n_contigs)]
+    heads = [b">chr%d|%d|0\n" % (k, n) if chunk_headers else b">chr%d\n" % k for k, n in enumerate(lens)]
     total = sum(len(h) + n + (n + 59) // 60 for h, n in zip(heads, lens))
     text = torch.empty(total + 64, dtype=torch.uint8, device=dev)
     lut = torch.tensor(list(b"ACGTacgt"), dtype=torch.uint8, device=dev)
@@ -532,6 +536,57 @@ def seqload_bench(a):
                       "seconds_set_sequences_fasta": round(min(new[1:]), 4), "seconds_set_sequences_host_strings": round(min(old[1:]), 4),
                       "seconds_set_sequences_fasta_all": [round(x, 4) for x in new], **extra, "kernel_ms": kernel_ms, "k_seq_store_GBps": round(moved / (store_ms / 1e3) / 1e9, 1) if store_ms else None,
                       "k_seq_store_fraction_of_8TBps": round(moved / (store_ms / 1e3) / 8e12, 3) if store_ms else None}))
+    eng.close()
+
+
+def ivload_bench(a):
+    """The interval table of upconvert from FASTA text: paffy_hip_set_intervals_fasta on text resident in HBM (index + the table's build).
+    --repeats R: a warm-up and R - 1 timed repetitions without the profile (median and spread = max - min), then one repetition under
+    the profile for the kernels' times by HIP events. Uses nothing but that call, so it runs on a library that builds the table on the
+    host as well; what the device build reports about itself is added where the library has it."""
+    import ctypes as C
+    import statistics
+
+    import numpy as np
+    import torch
+
+    import paffy_amd
+    from paffy_amd import engine as E
+
+    L = E.lib()
+    eng = paffy_amd.Engine()
+    if a.scaffolds:
+        rng = np.random.default_rng(13)
+        lens = rng.integers(1, 201, a.scaffolds).tolist()
+        starts = rng.integers(0, 1 << 33, a.scaffolds).tolist()
+        host = b"".join(b">scaf%d|%d|%d\n%s\n" % (i, s + n, s, b"A" * n) for i, (n, s) in enumerate(zip(lens, starts)))
+        text = eng.to_device(host)
+        nbytes = len(host)
+        del host
+    else:
+        text, nbytes, _ = synth_genome(torch, eng.device, a.genome_gb, chunk_headers=True)
+    torch.cuda.synchronize()
+    st = (C.c_int64 * 1)(0)
+    n_rec = C.c_int64()
+
+    def load():
+        t0 = time.perf_counter()
+        assert L.paffy_hip_set_intervals_fasta(eng._ctx, C.c_void_p(text.data_ptr()), nbytes, st, 1, C.byref(n_rec)) == 0
+        eng.sync()
+        return time.perf_counter() - t0
+
+    secs = [load() for _ in range(max(2, a.repeats))][1:]
+    eng.profile(True)
+    load()
+    prof = eng.profile_read()
+    eng.profile(False)
+    kernel_ms = {k: {"ms": round(v[0], 3), "launches": v[1]} for k, v in sorted(prof.items())}
+    extra = {}
+    if hasattr(L, "paffy_hip_intervals_info"):
+        extra = {"intervals_info": eng.intervals_info(), "name_sort_stats": eng.name_sort_stats(),
+                 "build_ms": round(sum(v[0] for k, v in prof.items() if k.startswith(("k_up_", "k_ns_", "ns_"))), 3)}
+    print(json.dumps({"cmd": "ivload", "text_bytes": nbytes, "records": n_rec.value, "seconds_median": round(statistics.median(secs), 5),
+                      "seconds_spread": round(max(secs) - min(secs), 5), "seconds_all": [round(x, 5) for x in secs], **extra, "kernel_ms": kernel_ms}))
     eng.close()
 
 
